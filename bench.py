@@ -3,7 +3,19 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode resident|stream]
                     [--workload mse_1024|mse_256|mrf_100|mrf_32] [--scaling weak|strong]
-                    [--only] [--no-cpu-baseline] [--no-extra-legs]
+                    [--dump-outputs DIR] [--full [--only] [--no-cpu-baseline] [--no-extra-legs]]
+
+A plain run measures the headline only: set-up, warm-up (the event-timed launches that take the chip out of its idle
+clocks, then W steps), K timed steps of --mode, the outputs if --dump-outputs is given, and the JSON line with `metric`,
+`value`, `unit`, `higher_is_better`, `dtype` and `ms_per_step`.  Everything else described below -- the other mode, the
+`roofline` objects, the parity check against the C oracle, the extra legs, `cpu_baseline`, the strong-scaling legs and
+gather timings of N > 1 runs -- is measured with --full only (--only / --no-cpu-baseline / --no-extra-legs trim a --full run).
+
+--dump-outputs DIR: what the last timed step wrote, as a caller of `epg.simulate(seq)` receives it (the complex128 signal
+[echo][voxel] of rank 0's voxels), on a fixed sample of at most 32 MB: DIR/signal_real.npy and DIR/signal_imag.npy
+(float64 [echoes, samples]) and DIR/voxel_index.npy (the flat grid index of every sample, float64).  The sample is the
+whole grid when it fits, else 64 runs of consecutive voxels at seeded offsets.  The inputs are fixed grids (and a seeded
+MRF train), so two builds run with the same arguments can be compared output for output.
 
 One "step" = one full pass of the hot path (the fused T/E/S/ADC kernel family of libepgx.so) over one batch of
 synthetic input: the whole sequence of the workload over its parameter grid, i.e. what one `epg.simulate(seq)`
@@ -22,10 +34,10 @@ mode "stream": one launch per echo, the state matrix [nvox][3][64] c128 is read 
   per-timestep kernel whose HBM roofline BASELINE.md quotes (B_alg = 2*64*3*16 + 16 = 6160 B per echo.voxel);
   `roofline` = {"bound": "hbm", ...} over the read+write launches only (the first launch of a pass starts from
   equilibrium and only writes the state: it is timed separately and excluded from both bytes and time).
-Both modes are measured in every run; `value` is the mode selected with --mode, the other mode is reported in
+A --full run measures both modes; `value` is the mode selected with --mode, the other mode is reported in
 an extra object.  Order per mode: event-timed launches (`launch_ms_before_timed_region`), W warm-up steps, K steps
-by the host clock, event-timed launches again (`launch_ms`).  The first set also takes the chip out of the idle clocks
-that plan compilation leaves it in: 3 warm-up launches (3 ms) alone do not (tools/headline_gap_probe.py).  Further objects of the default run (rank 0, N = 1): `configs1` (256 x 256), `configs3` (the
+by the host clock, event-timed launches again (`launch_ms`, --full).  The first set also takes the chip out of the idle clocks
+that plan compilation leaves it in: 3 warm-up launches (3 ms) alone do not (tools/headline_gap_probe.py).  Further objects of a --full run (rank 0, N = 1): `configs1` (256 x 256), `configs3` (the
 1000-TR MRF over 100^3 voxels, with its own roofline and parity check), `configs5` (PGSE, latency-labelled),
 `e2e` (one whole `epg.simulate()` call, host buffers out), `cpu_baseline`.
 
@@ -37,10 +49,12 @@ scalars and the communicator id -- the one RCCL in the process is the one libepg
     kernel-only rate of the whole grid; next to it the rate with the gather of the slabs to rank 0 inside every step --
     libepgx's own RCCL gather -- both ways: `gather_serial` (all kernels, then one gather) and `gather_overlapped`
     (the slab in 4 sub-slabs, sub-slab k on the wire while k + 1 computes), and the gather alone (`gather`).
-  A weak run with N > 1 measures the strong splits of mse_1024 and mrf_100 as well (`strong_mse_1024`, `strong_mrf_100`,
-  each with `kernel_only`, `gather_serial`, `gather_overlapped`), after its headline and behind a watchdog.
+  A --full weak run with N > 1 measures the strong splits of mse_1024 and mrf_100 as well (`strong_mse_1024`, `strong_mrf_100`,
+  each with `kernel_only`, `gather_serial`, `gather_overlapped`), after its headline and behind a watchdog.  A plain
+  --scaling strong run reports the kernel-only rate; the gather timings and the host routes need --full.
 """
 import argparse
+import ctypes
 import hashlib
 import json
 import os
@@ -284,6 +298,31 @@ class Leg:
         got = self.fetch(rows, flat[keep])
         return float(np.max(np.abs(got - ref[rows]))), int(keep.sum())
 
+    def dump(self, out_dir, budget=32 << 20, nrun=64):
+        """--dump-outputs: the signal the last step left in the buffer, [n_adc][voxel] of this rank's slab, on at most `budget`
+        bytes of samples (see the module docstring).  A run of `width` voxels is one 2-D copy of n_adc rows; the runs lie
+        inside [0, count) of the slab, so every copy stays inside the [n_adc][slab] buffer"""
+        sp, ctx = self.sp, self.ctx
+        n_adc, count, ld = sp.n_adc, sp.count, sp.slab
+        most = max(1, budget // (16 * n_adc + 8))          # real + imag float64 per echo, the index per voxel
+        if count <= most:
+            width, starts = count, np.zeros(1, dtype=np.int64)
+        else:
+            width = max(1, most // nrun)
+            slots = count // width
+            starts = width * np.sort(np.random.default_rng(0).choice(slots, size=min(nrun, slots), replace=False))
+        sig = np.empty((n_adc, len(starts) * width), dtype=np.complex128)
+        pitch = 16 * sig.shape[1]
+        for j, s in enumerate(starts):
+            self.lib.check(ctx.lib.epgx_memcpy_d2h_2d(ctx.handle, sig.ctypes.data + 16 * j * width, pitch,
+                                                      ctypes.c_void_p(self.sig_ptr + 16 * int(s)), 16 * ld, 16 * width, n_adc),
+                           "dump-outputs")
+        index = (sp.vox0 + starts[:, None] + np.arange(width)[None, :]).reshape(-1)
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "signal_real.npy"), np.ascontiguousarray(sig.real))
+        np.save(os.path.join(out_dir, "signal_imag.npy"), np.ascontiguousarray(sig.imag))
+        np.save(os.path.join(out_dir, "voxel_index.npy"), index.astype(np.float64))
+
     def free(self):
         if self.own_sig is not None:
             self.own_sig.free()
@@ -502,18 +541,26 @@ def main():
     ap.add_argument("--one-gpu", action="store_true",
                     help="rehearsal on a one-GPU box: every rank uses GPU 0 (the control flow of an N > 1 run -- barriers, status flags, "
                          "watchdog, the strong legs without a communicator: RCCL refuses two ranks on one GPU; no scaling figure)")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip configs1 / configs3 / configs5 / e2e / strong_mrf_100")
-    ap.add_argument("--only", action="store_true", help="measure only --mode of --workload (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline as well: the other mode, roofline objects, parity against the C oracle, "
+                         "the extra legs, cpu_baseline, the strong-scaling legs of N > 1 runs (a plain run times --mode of --workload only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (float64, a seeded sample of at most 32 MB)")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full: skip configs1 / configs3 / configs5 / e2e / strong_mrf_100")
+    ap.add_argument("--only", action="store_true", help="--full: measure only --mode of --workload (profiling runs)")
     ap.add_argument("--cpu-side", type=int, default=1024, help="CPU baseline grid side (default: the workload's own)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget (all-thread leg)")
     ap.add_argument("--no-fuse", action="store_true", help="keep E . T . E as three operators (A/B measurements)")
     ap.add_argument("--stub-leg", action="store_true", help=argparse.SUPPRESS)          # (tests/test_host.py: launcher + line bookkeeping, no GPU)
     ap.add_argument("--stub-fail-rank", type=int, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.stub_leg:
         return stub_leg(args)
-    if args.only:
+    if args.only or not args.full:
         args.no_extra_legs = args.no_cpu_baseline = True
+    full = args.full
 
     # stdout carries ONE JSON line: libraries that print banners from C (RCCL prints its version block on the first
     # communicator) get stderr instead; the line itself goes to the saved descriptor at the end
@@ -543,7 +590,7 @@ def main():
         dist.init_process_group("gloo", timeout=datetime.timedelta(minutes=10))
         dev = torch.device("cpu")
 
-    live_hash = csrc_hash()
+    live_hash = csrc_hash() if full else None
 
     def sync(ctx):
         ctx.synchronize()      # (all device work of this process is on the library's streams)
@@ -603,10 +650,11 @@ def main():
     if args.scaling == "strong":
         make_comm()
 
-    def strong_leg(workload, steps, warmup, fuse=True):
+    def strong_leg(workload, steps, warmup, fuse=True, after_timed=None):
         """BASELINE.json configs[3]: the SAME grid cut into `world` slabs, the signal gathered to rank 0.
-        Returns (leg, info dict): the kernel-only rate, the gather alone, and the rate with the gather inside every step --
-        serial (all kernels, then the gather) and overlapped (sub-slab k travels while k + 1 computes)"""
+        Returns (leg, info dict): the kernel-only rate, and with --full the gather alone and the rate with the gather inside
+        every step -- serial (all kernels, then the gather) and overlapped (sub-slab k travels while k + 1 computes).
+        `after_timed(leg)` runs right after the timed steps (--dump-outputs)"""
         info = {"workload": workload, "scaling": "strong", "n_gpus": world}
         gather = None
         leg = None
@@ -631,6 +679,11 @@ def main():
         info.update({"value": total_units * steps / wall, "ms_per_step": 1e3 * wall / steps, "steps": steps,
                      "voxels_per_gpu": leg.nvox, "voxels_total": leg.sp.nvox})
         info["kernel_only"] = {"value": info["value"], "ms_per_step": info["ms_per_step"], "steps": steps}
+        if after_timed:
+            after_timed(leg)
+        info["_gather_obj"] = gather
+        if not full:
+            return leg, info
         ms, _ = leg.kernel_ms("resident", max(1, min(steps, 5)))
         info["kernel_ms_rank0"] = round(ms, 4)
         if gather is not None:
@@ -714,17 +767,23 @@ def main():
                     info[key] = {"error": repr(exc)}
                 if not all_ok(True):
                     break
-        info["_gather_obj"] = gather
         return leg, info
 
     results, extra = {}, {}
+
+    def dump_outputs(leg):
+        """--dump-outputs, right after the timed steps of the headline (rank 0's voxels)"""
+        if args.dump_outputs and rank == 0:
+            sync(leg.ctx)
+            leg.dump(args.dump_outputs)
+
     if args.scaling == "strong":
-        leg, sinfo = strong_leg(args.workload, args.steps, args.warmup, not args.no_fuse)
+        leg, sinfo = strong_leg(args.workload, args.steps, args.warmup, not args.no_fuse, after_timed=dump_outputs)
         if leg is None:
             raise SystemExit(f"strong-scaling leg failed: {sinfo.get('error')}")
         gobj = sinfo.pop("_gather_obj", None)
         results["resident"] = {"value": sinfo["value"], "wall": sinfo["ms_per_step"] * sinfo["steps"] / 1e3, "steps": sinfo["steps"],
-                               "launch_ms": sinfo["kernel_ms_rank0"], "first_ms": None}
+                               "launch_ms": sinfo.get("kernel_ms_rank0"), "first_ms": None}
         for key in ("kernel_only", "gather", "gather_serial", "gather_overlapped", "gathered_parity_max_abs_err_vs_oracle", "gathered_parity_error"):
             if key in sinfo:
                 extra[key] = sinfo[key]
@@ -732,17 +791,20 @@ def main():
     else:
         leg = Leg(epg, _lib, args.workload, local_rank, rank, world, "weak", not args.no_fuse)
         for mode in ("resident", "stream"):
-            if args.only and mode != args.mode:
+            if (args.only or not full) and mode != args.mode:
                 continue
             steps = args.steps if mode == args.mode else max(3, args.steps // 4)
             # The event-timed launches of the roofline object run on BOTH sides of the wall-clock region.  The first set is
             # also what takes the chip out of its idle clocks: plan compilation and table upload leave the GPU idle for
             # ~0.5 s, after which 3 warm-up launches (3 ms) are not enough to be back at the sustained clock -- 20 launches
             # are (tools/headline_gap_probe.py: 0.980 ms per step with 3 warm-up launches after an idle half second,
-            # 0.897 with 20; no idle: 0.895 either way).  Both event times travel in the line.
+            # 0.897 with 20; no idle: 0.895 either way).  Both event times travel in the line (--full); a plain run keeps
+            # the first set as its warm-up.
             before_ms, _ = leg.kernel_ms(mode, 20 if (mode == "resident" and kind_of(args.workload) == "mse") else 2)
             wall = timed(leg, mode, steps, args.warmup)
-            launch_ms, first_ms = leg.kernel_ms(mode, max(1, min(steps, 10)))
+            if mode == args.mode:
+                dump_outputs(leg)
+            launch_ms, first_ms = leg.kernel_ms(mode, max(1, min(steps, 10))) if full else (None, None)
             results[mode] = {"value": leg.units_per_step * world * steps / wall, "wall": wall, "steps": steps,
                              "launch_ms": launch_ms, "first_ms": first_ms, "before_ms": before_ms}
     kind, grid = leg.kind, leg.grid
@@ -750,7 +812,7 @@ def main():
 
     # parity spot check of what was just computed (rank 0, oracle as checker only)
     parity = parity_error = parity_voxels = None
-    if rank == 0:
+    if rank == 0 and full:
         try:
             leg.step("resident")
             leg.ctx.synchronize()
@@ -1103,8 +1165,11 @@ def main():
             "config": {"workload": wtxt, "mode": args.mode, "voxels_per_gpu": leg.nvox, "echoes": leg.n_adc, "k_states": K_STATES,
                        "launches_per_step": n_launch[args.mode], "parallelism": f"voxel-slabs x{world}",
                        "collective": "none in the timed region (voxel slabs are independent; every GPU's signal slab stays in its HBM)"},
-            "roofline": roof(args.mode),
+            "full": full,
         }
+        if not full:     # a plain run: the headline only
+            return out
+        out["roofline"] = roof(args.mode)
         if world > 1 and comm is None:
             out["rccl_error"] = comm_error
         if other in results:
@@ -1144,7 +1209,7 @@ def main():
                 out["cpu_baseline"] = {"error": repr(exc)}
         return out
 
-    if world > 1 and args.scaling == "weak":
+    if world > 1 and args.scaling == "weak" and full:
         # BASELINE.json configs[3] next to the weak-scaling headline: mrf_100 cut into N slabs + ONE gather.  The
         # headline is already measured: if the communicator or this leg stalls on some rank, the watchdog prints
         # the line without it and every rank leaves, instead of the whole run being lost to the driver's time limit.

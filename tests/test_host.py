@@ -793,6 +793,43 @@ def test_bench_crash_guard_prints_the_held_line_only_when_the_parent_ends_silent
         assert seen == (b"" if printed_own else b'{"value": 2, "strong_mrf_100": {"error": "unfinished"}}\n')
 
 
+@pytest.mark.parametrize("n_adc,count,slab,vox0", [(20, 300000, 300000, 0), (1000, 8000, 8003, 16000), (3, 10, 12, 5)])
+def test_bench_dump_outputs_reads_a_fixed_sample_inside_the_slab(tmp_path, n_adc, count, slab, vox0):
+    """bench.py --dump-outputs: Leg.dump copies runs of voxels out of the [n_adc][slab] signal buffer (a host array stands in for
+    the device one); every copy stays inside the buffer, the sample is the same from run to run, float64, at most 32 MB"""
+    import ctypes
+    import types
+
+    import bench
+
+    buf = (np.arange(n_adc * slab) - 1j * np.arange(n_adc * slab)).astype(np.complex128)
+    lo, hi = buf.ctypes.data, buf.ctypes.data + buf.nbytes
+
+    def memcpy_d2h_2d(handle, host, host_pitch, dptr, dev_pitch, width_bytes, rows):
+        for r in range(rows):
+            src = dptr.value + r * dev_pitch
+            assert lo <= src and src + width_bytes <= hi
+            ctypes.memmove(host + r * host_pitch, src, width_bytes)
+        return 0
+
+    dumps = []
+    for run in range(2):
+        leg = bench.Leg.__new__(bench.Leg)
+        leg.sp = types.SimpleNamespace(n_adc=n_adc, count=count, slab=slab, vox0=vox0)
+        leg.ctx = types.SimpleNamespace(handle=None, lib=types.SimpleNamespace(epgx_memcpy_d2h_2d=memcpy_d2h_2d))
+        leg.lib = types.SimpleNamespace(check=lambda rc, what="": None)
+        leg.sig_ptr = buf.ctypes.data
+        leg.dump(str(tmp_path / str(run)))
+        dumps.append({f: np.load(tmp_path / str(run) / f"{f}.npy") for f in ("signal_real", "signal_imag", "voxel_index")})
+        assert sum(os.path.getsize(tmp_path / str(run) / f"{f}.npy") for f in dumps[-1]) <= 32 << 20
+    d = dumps[0]
+    assert all(a.dtype == np.float64 for a in d.values())
+    local = d["voxel_index"].astype(np.int64) - vox0
+    assert local.min() >= 0 and local.max() < count and len(np.unique(local)) == len(local)
+    assert np.array_equal(d["signal_real"] + 1j * d["signal_imag"], buf.reshape(n_adc, slab)[:, local])
+    assert all(np.array_equal(d[f], dumps[1][f]) for f in d)
+
+
 def _run_bench(args, env_extra=None, launcher=()):
     import subprocess
     import sys

@@ -12,9 +12,9 @@ bash tools/prof_long.sh $TAG > gpurun_out/prof_long.log 2>&1; echo long prof don
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/mfma_f64_coissue.hip -o /tmp/mfma_probe 2>/dev/null && /tmp/mfma_probe > profiles/${TAG}_mfma_f64_coissue.log 2>&1; echo mfma done
 (for a in "--ranks 2" "--ranks 2 --c64" "--ranks 1" "--ranks 2 --workload mrf_100 --calls 3" "--ranks 2 --via rccl --calls 2"; do echo "# tools/sharded_host_probe.py $a"; python tools/sharded_host_probe.py $a 2>&1 | grep "^call\|Error" ; done) > profiles/${TAG}_sharded_host_probe.log 2>&1; echo sharded done
 if [ -f epgpy_amd/csrc/variants/libepgx_timing.so ]; then EPGX_LIBRARY=$PWD/epgpy_amd/csrc/variants/libepgx_timing.so python tools/grow_timeline.py > profiles/${TAG}_grow_timeline.json 2> gpurun_out/timeline.err; echo timeline done; fi
-python bench.py > profiles/${TAG}_bench_line.json 2> gpurun_out/bench.err; echo bench done
-timeout 600 python bench.py --gpus 2 --one-gpu --steps 5 > profiles/${TAG}_bench_line_2ranks_one_gpu.json 2>> gpurun_out/bench.err; echo "two-rank rehearsal done"
-timeout 600 python bench.py --gpus 4 --one-gpu --steps 5 > profiles/${TAG}_bench_line_4ranks_one_gpu.json 2>> gpurun_out/bench.err; echo "four-rank rehearsal done"
-python bench.py --no-extra-legs > profiles/${TAG}_bench_line_no_extra.json 2>> gpurun_out/bench.err
+python bench.py --full > profiles/${TAG}_bench_line.json; echo bench done
+timeout 600 python bench.py --full --gpus 2 --one-gpu --steps 5 > profiles/${TAG}_bench_line_2ranks_one_gpu.json; echo "two-rank rehearsal done"
+timeout 600 python bench.py --full --gpus 4 --one-gpu --steps 5 > profiles/${TAG}_bench_line_4ranks_one_gpu.json; echo "four-rank rehearsal done"
+python bench.py --full --no-extra-legs > profiles/${TAG}_bench_line_no_extra.json
 mkdir -p gpurun_out/profiles_${TAG} && cp profiles/${TAG}_* profiles/traffic.json gpurun_out/profiles_${TAG}/
 tail -c 600 profiles/${TAG}_bench_line.json

@@ -8,7 +8,7 @@ MODE=${1:-resident}; TAG=${2:-r02}; WL=${3:-mse_1024}
 SUF=""; [ "$WL" != "mse_1024" ] && SUF="_$WL"
 OUT=gpurun_out/prof_${TAG}${SUF}_${MODE}; rm -rf $OUT; mkdir -p $OUT
 STEPS=20; WARM=3; [ "$WL" = "mrf_100" ] && STEPS=3 && WARM=1
-ARGS="bench.py --only --mode $MODE --workload $WL --steps $STEPS --warmup $WARM"
+ARGS="bench.py --full --only --mode $MODE --workload $WL --steps $STEPS --warmup $WARM"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ARGS > $OUT.trace.log 2>&1
 echo "trace done"
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAIT_INST_ANY SQ_WAIT_ANY --output-format csv -d $OUT/pmc_sq1 -- python3 $ARGS > $OUT.pmc1.log 2>&1
