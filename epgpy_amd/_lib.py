@@ -25,8 +25,8 @@ def max_vars(K):
     """derivative states one launch carries at capacity K: 3 up to 512 orders (at 512 the registers of a whole SIMD), 1 at 1024"""
     return MAX_VARS if K <= 512 else 1
 
-OP_NOP, OP_T, OP_MAT, OP_E, OP_S, OP_ADC, OP_SPOIL, OP_RESET, OP_PD, OP_D, OP_GS, OP_MAT0, OP_T0 = range(13)
-NCOEF = {OP_T: 8, OP_MAT: 10, OP_E: 4, OP_PD: 1, OP_MAT0: 14, OP_T0: 12}   # OP_D: 3*K, OP_GS: 3*K/2 (depend on the capacity)
+OP_NOP, OP_T, OP_MAT, OP_E, OP_S, OP_ADC, OP_SPOIL, OP_RESET, OP_PD, OP_D, OP_GS, OP_MAT0, OP_T0, OP_X = range(14)
+NCOEF = {OP_T: 8, OP_MAT: 10, OP_E: 4, OP_PD: 1, OP_MAT0: 14, OP_T0: 12}   # OP_D: 3*K, OP_GS: 3*K/2 (depend on the capacity), OP_X: 3*N*N
 GS_ZERO, GS_CONJ = -1, 1 << 30
 
 c_void_pp = ctypes.POINTER(ctypes.c_void_p)
@@ -138,7 +138,7 @@ SYMBOLS = {
     "epgx_run_to_host": (_i, [_p, _p, _i32, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _i32]),
     "epgx_download_2d": (_i, [_p, _p, _i64, _p, _i64, _i64, _i64]),
 }
-ABI_VERSION = 6
+ABI_VERSION = 7
 COMM_ID_BYTES = 128
 
 _lock = threading.Lock()

@@ -33,6 +33,8 @@
 
 #include "epgx_kernels.hip.h"
 #include "epgx_small_kernels.hip.h"
+#include "epgx_exchange_kernels.hip.h"
+#include "epgx_xrun_kernels.hip.h"
 #include "epgx_deriv_kernels.hip.h"
 #include "epgx_launch.h"
 #include "epgx_launch_grow.h"
@@ -70,6 +72,7 @@ struct Knobs {
     bool lead_forward;
     int slab_voxels; // EPGX_SLAB_VOXELS (tests): voxels per slab of the two-leg launch at 2048 orders (0: as many as 8 GiB of scratch hold)
     bool split_grow; // EPGX_SPLIT_GROW (default 1): K = 2048 in two legs where it pays (one wavefront per voxel up to 512 populated orders)
+    bool xrun;      // EPGX_XRUN (default 1): ranges with exchange (EPGX_OP_X) on xrun_kernel where it covers them; 0: always the split path
     int cgrow;      // EPGX_CGROW: 0 off, 1 (default): growing launches at K = 256 .. 1024, at K = 128 when 60 % of the records run below 64 orders; 2: at K = 128 whenever the other capacities would
 };
 int env_int(const char *name, int fallback) {
@@ -82,7 +85,8 @@ const Knobs &knobs() {
                             env_int("EPGX_CONTIG", 1) != 0, env_int("EPGX_SPLIT", 1) != 0,      env_int("EPGX_PREFETCH", 1) != 0,
                             env_int("EPGX_GROW_MIN", 1),    env_int("EPGX_FOLD", 1) != 0,
                             getenv("EPGX_GROW_SHARE") ? atof(getenv("EPGX_GROW_SHARE")) : 0.1, env_int("EPGX_LEAD_FORWARD", 1) != 0,
-                            env_int("EPGX_SLAB_VOXELS", 0), env_int("EPGX_SPLIT_GROW", 1) != 0, env_int("EPGX_CGROW", 1)};
+                            env_int("EPGX_SLAB_VOXELS", 0), env_int("EPGX_SPLIT_GROW", 1) != 0, env_int("EPGX_XRUN", 1) != 0,
+                            env_int("EPGX_CGROW", 1)};
     return k;
 }
 bool tracing() { return getenv("EPGX_TRACE") != nullptr; }
@@ -273,6 +277,9 @@ struct epgx_plan {
     int64_t shape[EPGX_MAX_DIMS];
     int64_t strides[EPGX_MAX_SPACES][EPGX_MAX_DIMS];
     int64_t nvox_total = 0;
+    int64_t x_span = 0;         // EPGX_OP_X in the plan: voxels per block of whole compartment groups (N * ib), else 0
+    int32_t x_ncomp = 0;        // ... and its N
+    epgx_op *d_ops = nullptr;   // device copy of `ops` (xrun_kernel walks the primitive list), made on first use
     uint32_t dense_spaces = 0;  // bit s: space s has the grid's own C-order strides
     // `cache_lock` guards `packed` and the vidx cache (two host threads running ranges of one plan)
     std::mutex cache_lock;
@@ -565,6 +572,7 @@ static int ncoef_expected(int opcode) {
     case EPGX_OP_E: return 4;
     case EPGX_OP_PD: return 1;
     case EPGX_OP_D: case EPGX_OP_GS: return -1;  // depends on K: checked in epgx_run
+    case EPGX_OP_X: return -1;                  // 3 N^2: checked with N below
     default: return 0;
     }
 }
@@ -709,6 +717,23 @@ extern "C" int epgx_plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, epgx_pla
             if (op.ia == 0) why = "shift by 0";
             if (op.ia >= EPGX_MAX_K || op.ia <= -EPGX_MAX_K) why = "shift exceeds EPGX_MAX_K";
             if (op.ib < 0) why = "negative truncation order";
+        }
+        if (!why && op.opcode == EPGX_OP_X) {
+            // N compartments at stride ib: the grid axis of extent N behind which the grid holds ib voxels
+            int ax = -1;
+            int64_t behind = 1;
+            for (int dd = d->ndim - 1; dd >= 0 && ax < 0; --dd) {
+                if (pl->shape[dd] == op.ia && behind == op.ib) ax = dd;
+                behind *= pl->shape[dd];
+            }
+            if (op.ia < 2 || op.ia > 8) why = "exchange between 2 .. 8 compartments";
+            else if (op.ncoef != 3 * op.ia * op.ia) why = "X table needs 3 N^2 doubles per entry";
+            else if (ax < 0) why = "no grid axis of extent N = ia with ib voxels behind it";
+            else if (pl->x_span && pl->x_span != (int64_t)op.ia * op.ib) why = "X operators of one plan must share N and the compartment axis";
+            else {
+                pl->x_span = (int64_t)op.ia * op.ib;
+                pl->x_ncomp = op.ia;
+            }
         }
         if (!why && op.opcode == EPGX_OP_ADC) {
             if (op.ia < 0 || op.ia >= d->n_adc) why = "ADC slot out of range";
@@ -1290,6 +1315,7 @@ extern "C" int epgx_plan_destroy(epgx_plan *pl) {
     }
     dev_free(pl->ctx, pl->d_coef);
     dev_free(pl->ctx, pl->d_vidx);
+    dev_free(pl->ctx, pl->d_ops);
     delete pl;
     return EPGX_OK;
 }
@@ -2572,6 +2598,150 @@ static int choose_kernel(const epgx_plan *pl, const PackedRange *pr, int op_begi
     return EPGX_OK;
 }
 
+static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin, int32_t op_end, int64_t vox0, int64_t nvox,
+                       const epgx_state *in, epgx_state *out, int32_t K, void *signal, int64_t signal_ld, int64_t signal_col0,
+                       char *name_out, int64_t name_bytes);
+
+// xrun_kernel launchers (epgx_xrun.hip, one translation unit per number of compartments): M = K / 64
+hipError_t epgx_launch_xrun_nc2(hipStream_t stream, const epgx::XRunArgs &a, int64_t ngroups, int M);
+hipError_t epgx_launch_xrun_nc3(hipStream_t stream, const epgx::XRunArgs &a, int64_t ngroups, int M);
+hipError_t epgx_launch_xrun_nc4(hipStream_t stream, const epgx::XRunArgs &a, int64_t ngroups, int M);
+
+// one EPGX_OP_X over the groups of voxels [vox0, vox0 + st->nvox) of the grid, state in place
+static int launch_exchange(epgx_ctx *ctx, const epgx_plan *pl, const epgx_op &op, int64_t vox0, epgx_state *st) {
+    XArgs a;
+    memset(&a, 0, sizeof(a));
+    a.state = st->data;
+    a.dens = st->dens;
+    a.tab = pl->d_coef + op.coef_off;
+    a.ngroups = st->nvox / op.ia;
+    a.stride = op.ib;
+    a.vox0 = vox0;
+    int log2K = 0;
+    while ((1 << log2K) < st->K) ++log2K;
+    a.log2K = log2K;
+    a.ndim = pl->ndim;
+    a.space = op.space;
+    for (int d = 0; d < EPGX_MAX_DIMS; ++d) {
+        a.shape[d] = pl->shape[d];
+        a.strides[d] = op.space >= 0 ? pl->strides[op.space][d] : 0;
+    }
+    const int64_t lanes = a.ngroups << log2K;
+    if ((lanes + 255) / 256 > 0x7fffffff) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: exchange over too many voxels in one launch");
+    const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
+    switch (op.ia) {
+    case 2: hipLaunchKernelGGL(exchange_kernel<2>, grid, block, 0, ctx->stream, a); break;
+    case 3: hipLaunchKernelGGL(exchange_kernel<3>, grid, block, 0, ctx->stream, a); break;
+    case 4: hipLaunchKernelGGL(exchange_kernel<4>, grid, block, 0, ctx->stream, a); break;
+    case 5: hipLaunchKernelGGL(exchange_kernel<5>, grid, block, 0, ctx->stream, a); break;
+    case 6: hipLaunchKernelGGL(exchange_kernel<6>, grid, block, 0, ctx->stream, a); break;
+    case 7: hipLaunchKernelGGL(exchange_kernel<7>, grid, block, 0, ctx->stream, a); break;
+    default: hipLaunchKernelGGL(exchange_kernel<8>, grid, block, 0, ctx->stream, a); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return EPGX_OK;
+}
+
+// A range that holds EPGX_OP_X: the records between two X run as pieces with the state in HBM (`out`, or a temporary state
+// when out is NULL), each X on exchange_kernel in between.  The voxel range must hold whole compartment groups.
+static int run_exchange_split(epgx_ctx *ctx, epgx_plan *pl, int32_t op_begin, int32_t op_end, int64_t vox0, int64_t nvox,
+                              const epgx_state *in, epgx_state *out, int32_t K, void *signal, int64_t signal_ld, int64_t signal_col0,
+                              char *name_out, int64_t name_bytes) {
+    if (pl->n_vars > 0) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: exchange (EPGX_OP_X) in a plan with derivative states");
+    if (!supported_K(K))
+        return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: ranges with an exchange (EPGX_OP_X) keep the state in HBM: K = 64 .. 1024, not %d", K);
+    if (vox0 % pl->x_span || nvox % pl->x_span)
+        return fail(EPGX_ERR_INVALID, "epgx_run: voxel range [%lld,%lld) cuts compartment groups (blocks of %lld voxels)", (long long)vox0,
+                    (long long)(vox0 + nvox), (long long)pl->x_span);
+    // xrun_kernel: one wavefront per group, NC = 2 .. 4 compartments, K = 64 NC .. 256 with NC * K / 64 <= 8, no D / gather shifts
+    const int M = K / 64, NC = pl->x_ncomp;
+    bool fused = knobs().xrun && NC >= 2 && NC <= 4 && K <= 256 && NC * M <= 8;
+    bool has_adc = false;
+    for (int i = op_begin; i < op_end && fused; ++i) {
+        fused = pl->ops[i].opcode != EPGX_OP_D && pl->ops[i].opcode != EPGX_OP_GS;
+        has_adc = has_adc || pl->ops[i].opcode == EPGX_OP_ADC;
+    }
+    if (name_out) {
+        if (fused) snprintf(name_out, (size_t)name_bytes, "xrun_kernel<%d, %d, %s>", NC, M, in ? "true" : "false");
+        else snprintf(name_out, (size_t)name_bytes, "split<exchange_kernel>");
+        return EPGX_OK;
+    }
+    if (has_adc && (!signal || signal_col0 < 0 || signal_col0 + nvox > signal_ld))
+        return fail(EPGX_ERR_INVALID, "epgx_run: range contains an ADC but the signal buffer is NULL or too narrow");
+    if (int rc = set_device(ctx)) return rc;
+    if (fused) {
+        if (tracing()) fprintf(stderr, "[epgx] run: xrun_kernel<%d, %d, %s> -- compartment groups in registers\n", NC, M, in ? "true" : "false");
+        {
+            std::lock_guard<std::mutex> plan_guard(pl->cache_lock);
+            if (!pl->d_ops) {
+                HIP_TRY(dev_alloc(ctx, (void **)&pl->d_ops, sizeof(epgx_op) * pl->ops.size()));
+                HIP_TRY(hipMemcpyAsync(pl->d_ops, pl->ops.data(), sizeof(epgx_op) * pl->ops.size(), hipMemcpyHostToDevice, ctx->stream));
+            }
+        }
+        XRunArgs a;
+        memset(&a, 0, sizeof(a));
+        a.ops = pl->d_ops;
+        a.op_begin = op_begin;
+        a.op_end = op_end;
+        a.coef = pl->d_coef;
+        a.in = in ? in->data : nullptr;
+        a.dens_in = in ? in->dens : nullptr;
+        a.out = out ? out->data : nullptr;
+        a.dens_out = out ? out->dens : nullptr;
+        a.signal = signal ? (d2 *)signal + signal_col0 : nullptr;
+        a.signal_ld = signal_ld;
+        a.vox0 = vox0;
+        a.stride = pl->x_span / NC;
+        a.ndim = pl->ndim;
+        a.n_spaces = pl->n_spaces;
+        memcpy(a.shape, pl->shape, sizeof(a.shape));
+        memcpy(a.strides, pl->strides, sizeof(a.strides));
+        const int64_t ngroups = nvox / NC;
+        if (ngroups > 0x7fffffff) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: more than 2^31 compartment groups in one launch");
+        hipError_t e = hipErrorInvalidValue;
+        switch (NC) {
+        case 2: e = epgx_launch_xrun_nc2(ctx->stream, a, ngroups, M); break;
+        case 3: e = epgx_launch_xrun_nc3(ctx->stream, a, ngroups, M); break;
+        default: e = epgx_launch_xrun_nc4(ctx->stream, a, ngroups, M); break;
+        }
+        if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_run: xrun_kernel launch failed: %s", hipGetErrorString(e));
+        return EPGX_OK;
+    }
+    if (tracing()) fprintf(stderr, "[epgx] run: split<exchange_kernel> -- records between exchanges on the per-timestep kernels\n");
+    epgx_state *tmp = nullptr;
+    epgx_state *work = out;
+    if (!work) {
+        if (int rc = epgx_state_create(ctx, nvox, K, &tmp)) return rc;
+        work = tmp;
+    }
+    int rc = EPGX_OK;
+    const epgx_state *src = in;   // the state the next piece starts from (NULL: equilibrium)
+    int begin = op_begin;
+    for (int i = op_begin; i <= op_end && !rc; ++i) {
+        if (i < op_end && pl->ops[i].opcode != EPGX_OP_X) continue;
+        if (i > begin) {
+            rc = run_or_name(ctx, pl, begin, i, vox0, nvox, src, work, K, signal, signal_ld, signal_col0, nullptr, 0);
+            src = work;
+        }
+        if (rc || i == op_end) break;
+        if (src != work) {   // the exchange acts in place: bring the start state into `work`
+            if (src) rc = epgx_state_copy(work, src);
+            else {
+                const int64_t total = nvox * 3 * K;
+                hipLaunchKernelGGL(state_init_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, work->data, (int)K,
+                                   work->dens, nvox);
+                if (hipGetLastError() != hipSuccess) rc = fail(EPGX_ERR_HIP, "epgx_run: state init failed");
+            }
+            src = work;
+        }
+        if (!rc) rc = launch_exchange(ctx, pl, pl->ops[i], vox0, work);
+        begin = i + 1;
+    }
+    if (!rc && out && src != out) rc = epgx_state_copy(out, src);   // (a range of X-free NOPs only: cannot happen, kept for safety)
+    epgx_state_destroy(tmp);
+    return rc;
+}
+
 // The kernel instantiations live in separate translation units (epgx_inst.hip compiled once per
 // M, epgx_deriv.hip ...) so that they build in parallel; see epgx_launch.h.
 // epgx_run, and (name_out != NULL) epgx_kernel_for: the same checks and the same decision, no launch
@@ -2635,6 +2805,10 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
                     return fail(EPGX_ERR_INVALID, "epgx_run: operator %d: gather index %d outside [0,%d)", i, v, K);
         }
     }
+    for (int i = op_begin; i < op_end; ++i)
+        if (pl->ops[i].opcode == EPGX_OP_X)
+            return run_exchange_split(ctx, pl, op_begin, op_end, vox0, nvox, in, out, K, signal, signal_ld, signal_col0, name_out,
+                                      name_bytes);
     if (int rc = set_device(ctx)) return rc;
     // from here to the launch the plan's caches (packed records, table indices of the voxel range) are read and
     // possibly rebuilt: one host thread at a time per plan (the launch itself is asynchronous)
@@ -3444,6 +3618,7 @@ extern "C" int epgx_run_to_host(epgx_ctx *ctx, const epgx_plan *plan, int32_t K,
         slab = (slab + 63) & ~(int64_t)63;
     }
     slab = std::max(slab, (nvox + 63) / 64);   // (one event per slab, 64 of them)
+    if (plan->x_span) slab = (slab + plan->x_span - 1) / plan->x_span * plan->x_span;   // whole compartment groups
     const int n_slabs = (int)((nvox + slab - 1) / slab);
     std::lock_guard<std::mutex> one_at_a_time(ctx->pipeline);
     if (int rc = ensure_copy_stream(ctx, n_slabs)) return rc;

@@ -594,6 +594,8 @@ def simulate_sharded(sequence, *, group=None, dst=0, probe=None, adc_time=False,
         raise NotImplementedError('out="device" keeps complex128 records')
     rank, world = dist.get_rank(group), dist.get_world_size(group)    # ranks of the GROUP
     flat = functions.flatten_sequence(sequence)
+    if functions.has_exchange(flat):
+        raise NotImplementedError("X (exchange) runs on one GPU: simulate_sharded does not carry it")
     probes = []
     if probe:
         probes = probe if isinstance(probe, (tuple, list)) else [probe]

@@ -290,6 +290,8 @@ def simulate(sequence, *, adc_time=False, init=None, squeeze=False, probe=None, 
             raise ValueError(f"Incompatible StateMatrix and operator shapes: {init.shape}, {shape}")
         options = {**init.options, **options}
 
+    if has_exchange(sequence):
+        _check_exchange(sequence, probes, init, out, devices)
     on_device = all((pb or op)._device_kind() is not None
                     for op in sequence if isinstance(op, Probe) for pb in (probes or [op]))
     on_device = on_device and not any(part._on_host() for op in sequence for part in op._parts())   # (user-written operators)
@@ -322,6 +324,26 @@ def simulate(sequence, *, adc_time=False, init=None, squeeze=False, probe=None, 
     if progress is not None:
         progress.close()
     return _pack_values(values, times, asarray=asarray, adc_time=adc_time, stacked_as_is=(out == "device"), dtype=dtype)
+
+
+def has_exchange(sequence):
+    """True if a (flat) sequence holds an exchange operator X"""
+    from .exchange import X
+    return any(isinstance(part, X) for op in sequence for part in op._parts())
+
+
+def _check_exchange(sequence, probes, init, out, devices):
+    """what simulate() does not carry through an exchange (X) yet: NotImplementedError that names X"""
+    from .diff import Jacobian, Hessian
+    if any(isinstance(pb, (Jacobian, Hessian)) for pb in probes) or any(
+            getattr(part, "order1", None) or getattr(part, "order2", None) for op in sequence for part in op._parts()):
+        raise NotImplementedError("X (exchange) has no derivatives: no Jacobian / Hessian / order1 in a sequence with X")
+    if out == "device":
+        raise NotImplementedError('X (exchange): out="device" is not supported')
+    if len(devices) > 1:
+        raise NotImplementedError("X (exchange) runs on one GPU (no ngpu > 1)")
+    if init is not None and getattr(init, "_eq", None) is not None:
+        raise NotImplementedError("X (exchange) with a general equilibrium: only [0, 0, density] is supported")
 
 
 def _pack_values(values, times, *, asarray=True, adc_time=False, stacked_as_is=False, dtype=None):

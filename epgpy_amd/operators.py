@@ -9,3 +9,4 @@ from .transition import T, Tx, Ty, Phi
 from .shift import S
 from .diffusion import D
 from .diff import Jacobian, Hessian, PartialsPruner
+from .exchange import X

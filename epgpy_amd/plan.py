@@ -52,6 +52,9 @@ class Encoder:
         self.fuse_partials = []    # partials of generated tables (epgx_fuse_partial), same tagged offsets
         # tables the library assembles on the device from per-axis columns (epgx_assemble)
         self.assembles = []
+        # exchange (X): (compartment axis, N) shared by every X of the plan; lead shapes of the n-D shift vectors
+        self.exchange = None
+        self.shift_shapes = []
         self._arrays_lock = threading.RLock()     # plan_arrays() mutates the encoder: one thread at a time
 
     # -- tables ------------------------------------------------------------------------
@@ -197,7 +200,7 @@ class Encoder:
     # -- records -----------------------------------------------------------------------
     def add(self, opcode, *, table=None, key=None, ia=0, ib=0, entry=None):
         space, off, ncoef = entry if entry is not None else ((-1, 0, 0) if table is None else self._table(table, key))
-        if ncoef != _lib.NCOEF.get(opcode, 0):
+        if ncoef != (3 * ia * ia if opcode == _lib.OP_X else _lib.NCOEF.get(opcode, 0)):
             raise ValueError(f"opcode {opcode}: table has {ncoef} coefficients")
         self.records.append((opcode, space, int(ia), int(ib), off, ncoef))
 
@@ -230,9 +233,28 @@ class Encoder:
             return self.kspace.with_kdim(max(kdim, self.kspace.kdim))
         return kspace.KSpace.from_orders(self.nstate, kdim)
 
+    def note_exchange(self, axis, ncomp):
+        """an X over `ncomp` compartments along grid axis `axis`: one layout of compartment groups per plan, and the
+        compartments of a group share their k-space coordinates (X mixes order slot i of every compartment)"""
+        if self.exchange is not None and self.exchange != (axis, ncomp):
+            raise NotImplementedError(f"X operators of one sequence with different axes or numbers of compartments: "
+                                      f"{self.exchange} and {(axis, ncomp)}")
+        self.exchange = (axis, ncomp)
+        self._check_shift_axes()
+
+    def _check_shift_axes(self):
+        if self.exchange is None:
+            return
+        axis = self.exchange[0]
+        if any(len(lead) > axis and lead[axis] > 1 for lead in self.shift_shapes):
+            raise NotImplementedError("X with n-D shift vectors that vary along the compartment axis (the compartments of a "
+                                      "group must share their k-space coordinates)")
+
     def add_gather_shift(self, delta, nmax):
         """S(k) with an integer vector k  (shift.py:103-118 'shift-nd')"""
         delta = np.atleast_1d(np.asarray(delta))             # [kdim] or [*lead, kdim]
+        self.shift_shapes.append(delta.shape[:-1])
+        self._check_shift_axes()
         if self.kspace is None:
             # first n-D shift on a state that so far only knew 1-D orders (statematrix.py:314-329);
             # nothing is known about which orders are populated, so all of them are assumed to be
@@ -278,7 +300,7 @@ class Encoder:
             return 0
         if bool(self.variables) != bool(derivatives):
             return 0
-        ok = all(rec[0] not in (_lib.OP_D, _lib.OP_GS, _lib.OP_MAT, _lib.OP_MAT0) and (rec[0] != _lib.OP_S or abs(rec[2]) == 1)
+        ok = all(rec[0] not in (_lib.OP_D, _lib.OP_GS, _lib.OP_MAT, _lib.OP_MAT0, _lib.OP_X) and (rec[0] != _lib.OP_S or abs(rec[2]) == 1)
                  for rec in self.records)
         return next(K for K in _lib.PACKED_K if K >= self.peak + 1) if ok else 0
 
@@ -288,7 +310,7 @@ class Encoder:
         general matrices, no derivative states; else 0"""
         if (self.kspace is None and not self.deferred) or self.peak + 1 > _lib.PACKED_K[0] or self.variables:
             return 0
-        ok = all(rec[0] not in (_lib.OP_MAT, _lib.OP_MAT0) and (rec[0] != _lib.OP_S or abs(rec[2]) == 1) for rec in self.records)
+        ok = all(rec[0] not in (_lib.OP_MAT, _lib.OP_MAT0, _lib.OP_X) and (rec[0] != _lib.OP_S or abs(rec[2]) == 1) for rec in self.records)
         return _lib.PACKED_K[0] if ok else 0
 
     def capacity(self, at_least=0, resident=False):
@@ -298,7 +320,7 @@ class Encoder:
         for K in _lib.SUPPORTED_K:
             if K >= need:
                 return K
-        plain = (self.kspace is None and not self.deferred and not self.variables
+        plain = (self.kspace is None and not self.deferred and not self.variables and self.exchange is None
                  and all(rec[0] != _lib.OP_S or abs(rec[2]) == 1 for rec in self.records))
         if resident and plain and need <= _lib.RESIDENT_ONLY_K:
             return _lib.RESIDENT_ONLY_K

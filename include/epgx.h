@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define EPGX_ABI_VERSION 6
+#define EPGX_ABI_VERSION 7
 #define EPGX_MAX_DIMS 8    /* grid dimensions                        */
 #define EPGX_MAX_SPACES 4  /* distinct operator broadcast patterns   */
 #define EPGX_WAVE 64       /* k-states per lane-register (wave64)    */
@@ -95,6 +95,22 @@ enum epgx_opcode {
                           symmetry and real m00 (the diagonal of E is real), and the recoveries become
                           (o0, conj o0, o2) * density on the k = 0 order.  Emitted by the host's
                           peephole fusion (epgpy_amd/fusion.py); same idea as `E @ T` in the reference */
+    EPGX_OP_X = 13,    /* exchange between the N = ia (2 .. 8) compartments of a voxel group -- exchange.py:89-120, 154-207.
+                          The compartments of a group are the voxels v, v + ib, .., v + (N-1) ib of the grid (ib = the
+                          compartment stride in voxels: the product of the grid extents behind the compartment axis).  One
+                          table entry per GROUP (an index space with stride 0 on the compartment axis, evaluated at any of
+                          its voxels), 3 N^2 doubles: Re/Im of mT row-major (2 N^2), then mL row-major (N^2).  mL is stored
+                          real: the reference's expm of a real matrix carries an imaginary part that is rounding noise of
+                          its eigendecomposition.  At every order k, with rho_c the density of compartment c:
+                            A_c <- sum_c' mT[c][c'] A_c'                (A = F_k)
+                            B_c <- sum_c' conj(mT[c][c']) B_c'          (B = conj F_-k)
+                            Z_c <- sum_c' mL[c][c'] (Z_c' - d_k0 rho_c') + d_k0 rho_c
+                          A range that holds X runs in ONE launch of xrun_kernel<NC, M, HAS_IN> (NC = N = 2 .. 4, K / 64 = M
+                          with NC M <= 8, no D / gather shifts; one wavefront per group, the state in registers); otherwise
+                          (or with EPGX_XRUN=0 in the environment) as pieces: the records between two X on the per-timestep
+                          kernels with the state in HBM (a temporary state from equilibrium when `in` is NULL),
+                          exchange_kernel in between.  epgx_kernel_for names the first "xrun_kernel<2, 2, false>" (etc.),
+                          the second "split<exchange_kernel>".  Voxel ranges must hold whole groups. */
     EPGX_OP__COUNT
 };
 
