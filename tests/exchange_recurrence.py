@@ -1,6 +1,9 @@
-"""A small NumPy EPG-X recurrence (full state matrix, rows k = -n .. n) for T / E / S / X / SPOILER / ADC sequences: the
-checker of the exchange tests and of tools/bench_exchange.py.  It follows the reference's operator algebra
-(exchange.py:89-120 for X) on the host, with the operators' own tables."""
+"""A small NumPy EPG-X recurrence (full state matrix, rows k = -n .. n) for matrix (T, T @ R) / scalar (E, R) / S / X /
+SPOILER / RESET / PD / probe sequences: the checker of the exchange tests and of tools/bench_exchange.py.  It follows the
+reference's operator algebra (exchange.py:89-120 for X) on the host, with the operators' own tables.
+
+`dtype=np.clongdouble` runs the same recurrence in extended precision (64-bit mantissas on x86-64) on those float64
+tables: it then measures the kernels' arithmetic, not the tables'.  The float64 default is what the tests always used."""
 import numpy as np
 
 from epgpy_amd import epg
@@ -14,19 +17,44 @@ def _bcast(arr, lead, grid):
     return np.broadcast_to(arr, tuple(grid) + tail)
 
 
-def recurrence(seq, grid, density, nmax):
-    """full state matrix [*grid, 2 nmax + 1, 3] (rows k = -nmax .. nmax), from equilibrium, no truncation within nmax"""
+def _grid_array(arr, grid, dtype):
+    """a per-voxel array (the reference's trailing-axes broadcasting) -> [*grid] of `dtype`"""
+    arr = np.asarray(arr)
+    return np.broadcast_to(arr.reshape(np.shape(arr) + (1,) * (len(grid) - np.ndim(arr))), grid).astype(dtype)
+
+
+def _truncate(st, nmax, kmax):
+    """F+ / F- above order kmax <- 0 (the library's truncate(): Z is left alone, it stays 0 there)"""
+    if kmax is not None and kmax < nmax:
+        st[..., : nmax - kmax, :2] = 0
+        st[..., nmax + kmax + 1:, :2] = 0
+    return st
+
+
+def recurrence(seq, grid, density, nmax, *, dtype=np.complex128, max_nstate=None, init=None):
+    """probe records [n_probe, *grid] of `seq` from the full state matrix [*grid, 2 nmax + 1, 3] (rows k = -nmax .. nmax)
+
+    `nmax` must hold every order the sequence reaches (after truncation).  Shifts truncate F+ / F- at `max_nstate` (the
+    plan option, which wins) or at the shift's own `nmax`.  `init`: (states [*grid, n, 3] in the StateMatrix layout,
+    rows k = -(n-1)/2 .. (n-1)/2) to start from instead of the equilibrium; `density` is then that state's density.
+    Probes record F0, or Z0 for `Adc("Z0")` / `Probe("Z0")`."""
     grid = tuple(grid)
-    dens = np.broadcast_to(np.asarray(density, dtype=np.float64).reshape(
-        np.shape(density) + (1,) * (len(grid) - np.ndim(density))), grid)
-    st = np.zeros(grid + (2 * nmax + 1, 3), dtype=np.complex128)
-    st[..., nmax, 2] = dens
+    real = np.finfo(dtype).dtype
+    dens = _grid_array(density, grid, real)
+    st = np.zeros(grid + (2 * nmax + 1, 3), dtype=dtype)
+    if init is None:
+        st[..., nmax, 2] = dens
+    else:
+        init = np.asarray(init)
+        half = (init.shape[-2] - 1) // 2
+        assert half <= nmax, (half, nmax)
+        st[..., nmax - half: nmax + half + 1, :] = np.broadcast_to(init, grid + init.shape[-2:])
     out = []
     for op in seq:
         if isinstance(op, epg.X):
             ax, n = op.axis, op.ncomp
-            mT = np.moveaxis(op.mat[..., 0], (ax, ax + 1), (-2, -1))          # [*lead, N, N], lead has 1 at ax
-            mL = np.moveaxis(op.mat[..., 2], (ax, ax + 1), (-2, -1))
+            mT = np.moveaxis(op.mat[..., 0], (ax, ax + 1), (-2, -1)).astype(dtype)     # [*lead, N, N], lead has 1 at ax
+            mL = np.moveaxis(op.mat[..., 2], (ax, ax + 1), (-2, -1)).astype(dtype)
             lead = mT.shape[:-2]
             mT = _bcast(np.expand_dims(mT, ax), lead[:ax] + (1,) + lead[ax:], grid)   # [*grid(1 at ax), N, N]
             mL = _bcast(np.expand_dims(mL, ax), lead[:ax] + (1,) + lead[ax:], grid)
@@ -41,14 +69,16 @@ def recurrence(seq, grid, density, nmax):
             new[..., 2, :] = np.einsum("...ij,...rj->...ri", mLm.real, sub[..., 2, :])
             st = np.moveaxis(new, -1, ax)
             st[..., nmax, 2] += dens
-        elif isinstance(op, epg.T):
-            mat = _bcast(op.mat, op.mat.shape[:-2], grid)
+        elif isinstance(op, epg.MatrixOp):          # T, and products such as T @ R (general 3x3, with mat0)
+            mat = _bcast(op.mat, op.mat.shape[:-2], grid).astype(dtype)
             st = np.einsum("...ij,...rj->...ri", mat, st)
-        elif isinstance(op, epg.E):
-            arr = _bcast(op.arr, op.arr.shape[:-1], grid)
+            if op.mat0 is not None:                    # mat0 acts on the equilibrium [0, 0, density]
+                st[..., nmax, :] += _bcast(op.mat0, op.mat0.shape[:-2], grid)[..., :, 2].astype(dtype) * dens[..., None]
+        elif isinstance(op, epg.ScalarOp):          # E, R, P
+            arr = _bcast(op.arr, op.arr.shape[:-1], grid).astype(dtype)
             st = st * arr[..., None, :]
             if op.arr0 is not None:
-                st[..., nmax, 2] += _bcast(op.arr0, op.arr0.shape[:-1], grid)[..., 2] * dens
+                st[..., nmax, 2] += _bcast(op.arr0, op.arr0.shape[:-1], grid)[..., 2].astype(dtype) * dens
         elif isinstance(op, epg.S):
             k = int(op.k)
             new = np.zeros_like(st)
@@ -60,12 +90,65 @@ def recurrence(seq, grid, density, nmax):
                 new[..., : rows + k, 0] = st[..., -k:, 0]
                 new[..., -k:, 1] = st[..., : rows + k, 1]
             new[..., 2] = st[..., 2]
-            st = new
+            st = _truncate(new, nmax, max_nstate or op.nmax or None)
         elif op is epg.SPOILER:
             st = st.copy()
             st[..., :2] = 0
+        elif op is epg.RESET:
+            st = np.zeros_like(st)
+            st[..., nmax, 2] = dens
+        elif isinstance(op, epg.PD):
+            dens = _grid_array(op.pd, grid, real)
+            if op.reset:
+                st = np.zeros_like(st)
+                st[..., nmax, 2] = dens
         elif isinstance(op, epg.Probe):
-            out.append(st[..., nmax, 0].copy())
+            out.append(st[..., nmax, 2 if op._device_kind() == 1 else 0].copy())
         else:
             raise TypeError(op)
     return np.stack(out)
+
+
+def conserving_khi(rng, dens, scale):
+    """random kinetic matrix whose columns sum to 0 and that conserves `dens` (detailed balance)"""
+    n = len(dens)
+    s = rng.uniform(0.2, 1.0, (n, n)) * scale
+    s = s + s.T
+    khi = -s / np.asarray(dens)[None, :]
+    np.fill_diagonal(khi, 0)
+    np.fill_diagonal(khi, -khi.sum(axis=0))
+    return khi
+
+
+def random_case(seed):
+    """(sequence, grid, densities, nmax) of test_gpu_exchange.test_random_sequences: 2 .. 4 compartments on axis 0 of a
+    grid of 3 .. 8 groups, T / E / S / X / SPOILER / ADC in random order"""
+    rng = np.random.default_rng(1000 + seed)
+    n = 2 + seed % 3
+    M = int(rng.integers(3, 9))
+    dens = rng.uniform(0.2, 1.0, n)
+    khi = conserving_khi(rng, dens, rng.uniform(1e-3, 5e-2))
+    x = epg.X(rng.uniform(1, 8), khi, T1=rng.uniform(300, 1500, n), T2=rng.uniform(10, 150, n),
+              g=rng.uniform(-0.05, 0.05, n))
+    nsteps = int(rng.integers(12, 24))
+    # long shifts push the capacity to K = 64 .. 1024
+    big = [1, 2, 8, 20, 40, 60][seed % 6]
+    seq, peak = [], 0
+    for _ in range(nsteps):
+        r = rng.uniform()
+        if r < 0.25:
+            seq.append(epg.T([rng.uniform(5, 150, M)], rng.uniform(0, 360)))
+        elif r < 0.4:
+            seq.append(epg.E(rng.uniform(1, 10), [[t] for t in rng.uniform(300, 2000, n)], rng.uniform(20, 200)))
+        elif r < 0.65:
+            k = int(rng.choice([1, -1, 2, -2, big]))
+            seq.append(epg.S(k))
+            peak += abs(k)
+        elif r < 0.85:
+            seq.append(x)
+        elif r < 0.9:
+            seq.append(epg.SPOILER)
+        else:
+            seq.append(epg.ADC)
+    seq = [epg.T([rng.uniform(30, 120, M)], 90), x] + seq + [epg.ADC]
+    return seq, (n, M), dens, peak + 1

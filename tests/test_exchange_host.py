@@ -111,3 +111,78 @@ def test_out_of_scope_raises_naming_x():
     with pytest.raises(NotImplementedError, match="X"):
         _functions._check_exchange(seq, [], None, "host", [0, 1])
     assert _functions.has_exchange(seq) and not _functions.has_exchange([epg.T(10, 90), epg.ADC])
+
+
+# ------------------------------------------------------------------------------------------------ extended-precision reference
+def _golden_sim_case(name):
+    from tests.test_gpu_exchange import _sim_cases     # (the G17 sequences; that module's tests stay GPU-marked)
+    seq, opts, dens = _sim_cases()[name]
+    flat = _functions.flatten_sequence(seq)
+    nshift = sum(abs(op.k) for op in flat if isinstance(op, epg.S))
+    nmax = min(nshift, opts.get("max_nstate", nshift)) + 1
+    reduce = [op.reduce for op in flat if isinstance(op, epg.Probe)][0]
+    return flat, _functions.getshape(flat), dens, nmax, opts.get("max_nstate"), reduce
+
+
+@pytest.mark.parametrize("name", ["sim_spgr_bm", "sim_spgr_bm_sum", "sim_spgr_mt_sum", "sim_bssfp_bm", "sim_se3", "sim_axis1"])
+def test_extended_recurrence_matches_golden(name):
+    """the clongdouble recurrence (with truncation at max_nstate and T @ R matrices) reproduces the G17 signals to 1e-13"""
+    from tests.exchange_recurrence import recurrence
+    seq, grid, dens, nmax, max_nstate, reduce = _golden_sim_case(name)
+    want = GOLDEN[name]
+    got = recurrence(seq, grid, dens, nmax, dtype=np.clongdouble, max_nstate=max_nstate)
+    assert got.dtype == np.clongdouble
+    if reduce is not None:
+        got = got.sum(axis=tuple(1 + int(ax) for ax in np.atleast_1d(reduce)))
+    assert float(np.max(np.abs(got - want))) <= 1e-13 * max(1.0, float(np.max(np.abs(want))))
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_extended_against_float64_recurrence(seed):
+    """the float64 recurrence (the checker of test_random_sequences) within 1e-13 of the extended-precision one: the
+    float64 rounding the GPU tolerance has to absorb"""
+    from tests.exchange_recurrence import recurrence, random_case
+    seq, grid, dens, nmax = random_case(seed)
+    r64 = recurrence(seq, grid, dens, nmax)
+    rext = recurrence(seq, grid, dens, nmax, dtype=np.clongdouble)
+    assert r64.dtype == np.complex128
+    assert float(np.max(np.abs(r64 - rext))) <= 1e-13 * max(1.0, float(np.max(np.abs(rext))))
+
+
+def test_recurrence_reset_pd_z0_truncation():
+    """the operators the device tests lean on, against hand-derived states: RESET / PD restore [0, 0, rho]; PD(reset=False)
+    changes only the equilibrium X and E relax to; Z0 probes; F+ / F- cut above max_nstate; a start state"""
+    from tests.exchange_recurrence import recurrence
+    dens = np.array([0.7, 0.3])
+    x = epg.X(4.0, exchange.exchange_matrix(0.05, densities=dens), T1=[900, 300], T2=[80, 20], g=[0.01, -0.02])
+    seq = [epg.T(90, 0), epg.S(1), epg.RESET, epg.ADC, epg.Adc("Z0"), epg.T(30, 0), epg.PD([0.2, 0.5]), epg.Adc("Z0")]
+    r = recurrence(seq, (2,), dens, 2, dtype=np.clongdouble)
+    assert np.array_equal(r[0], [0, 0]) and np.array_equal(r[1], dens) and np.array_equal(r[2], [0.2, 0.5])
+    # PD without reset: X then relaxes Z0 towards the new densities (a fixed point of X)
+    seq = [epg.PD([0.2, 0.5], reset=False), x, epg.Adc("Z0")]
+    r = recurrence(seq, (2,), dens, 1, dtype=np.clongdouble)
+    mL = np.moveaxis(x.mat[..., 2], (0, 1), (-2, -1)).real
+    want = mL @ (dens - [0.2, 0.5]) + [0.2, 0.5]
+    assert float(np.max(np.abs(r[0] - want))) <= 1e-15
+    # truncation: a 90 pulse then S(1), S(1): F+ at order 2 is dropped with max_nstate=1, kept without
+    seq = [epg.T(90, 90), epg.S(1), epg.S(1), epg.S(-1), epg.S(-1), epg.ADC]
+    full = recurrence(seq, (1,), 1.0, 3, dtype=np.clongdouble)
+    cut = recurrence(seq, (1,), 1.0, 3, dtype=np.clongdouble, max_nstate=1)
+    assert abs(full[0, 0] - 1) <= 1e-15 and cut[0, 0] == 0
+    cut_op = recurrence([epg.T(90, 90), epg.S(1, nmax=1), epg.S(1, nmax=1), epg.S(-1), epg.S(-1), epg.ADC], (1,), 1.0, 3)
+    assert cut_op[0, 0] == 0
+    # a start state: F+(1) = 1 comes back to k = 0 after S(-1), with the density of the start state
+    init = np.zeros((3, 3), dtype=complex)
+    init[2, 0] = 1.0       # F+(1)
+    init[0, 1] = 1.0       # F-(-1) = conj(F+(1))
+    r = recurrence([epg.S(-1), epg.ADC, epg.RESET, epg.Adc("Z0")], (1,), 0.4, 2, init=init, dtype=np.clongdouble)
+    assert r[0, 0] == 1 and r[1, 0] == 0.4
+
+
+def test_recurrence_float64_default_unchanged():
+    """dtype=complex128 (the default) keeps the recurrence's float64 results"""
+    from tests.exchange_recurrence import recurrence, random_case
+    seq, grid, dens, nmax = random_case(3)
+    a = recurrence(seq, grid, dens, nmax)
+    b = recurrence(seq, grid, dens, nmax, dtype=np.complex128)
+    assert a.dtype == np.complex128 and np.array_equal(a, b)

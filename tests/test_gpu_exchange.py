@@ -7,7 +7,7 @@ import pytest
 
 from epgpy_amd import epg, exchange, magnettransfer, _lib, EpgxError
 from epgpy_amd import functions as _functions
-from tests.exchange_recurrence import recurrence
+from tests.exchange_recurrence import recurrence, random_case
 
 pytestmark = pytest.mark.gpu
 
@@ -19,17 +19,6 @@ def maxerr(a, b):
     a, b = np.asarray(a), np.asarray(b)
     assert a.shape == b.shape, (a.shape, b.shape)
     return float(np.max(np.abs(a - b)))
-
-
-def conserving_khi(rng, dens, scale):
-    """random kinetic matrix whose columns sum to 0 and that conserves `dens` (detailed balance)"""
-    n = len(dens)
-    s = rng.uniform(0.2, 1.0, (n, n)) * scale
-    s = s + s.T
-    khi = -s / np.asarray(dens)[None, :]
-    np.fill_diagonal(khi, 0)
-    np.fill_diagonal(khi, -khi.sum(axis=0))
-    return khi
 
 
 # ------------------------------------------------------------------------------------------------ op(sm): G17 scenarios
@@ -208,35 +197,8 @@ def test_voxel_ranges_whole_groups():
 # ------------------------------------------------------------------------------------------------ random sequences
 @pytest.mark.parametrize("seed", range(24))
 def test_random_sequences(seed):
-    rng = np.random.default_rng(1000 + seed)
-    n = 2 + seed % 3
-    M = int(rng.integers(3, 9))
-    dens = rng.uniform(0.2, 1.0, n)
-    khi = conserving_khi(rng, dens, rng.uniform(1e-3, 5e-2))
-    x = epg.X(rng.uniform(1, 8), khi, T1=rng.uniform(300, 1500, n), T2=rng.uniform(10, 150, n),
-              g=rng.uniform(-0.05, 0.05, n))
-    nsteps = int(rng.integers(12, 24))
-    # long shifts push the capacity to K = 64 .. 1024
-    big = [1, 2, 8, 20, 40, 60][seed % 6]
-    seq, peak = [], 0
-    for _ in range(nsteps):
-        r = rng.uniform()
-        if r < 0.25:
-            seq.append(epg.T([rng.uniform(5, 150, M)], rng.uniform(0, 360)))
-        elif r < 0.4:
-            seq.append(epg.E(rng.uniform(1, 10), [[t] for t in rng.uniform(300, 2000, n)], rng.uniform(20, 200)))
-        elif r < 0.65:
-            k = int(rng.choice([1, -1, 2, -2, big]))
-            seq.append(epg.S(k))
-            peak += abs(k)
-        elif r < 0.85:
-            seq.append(x)
-        elif r < 0.9:
-            seq.append(epg.SPOILER)
-        else:
-            seq.append(epg.ADC)
-    seq = [epg.T([rng.uniform(30, 120, M)], 90), x] + seq + [epg.ADC]
-    want = recurrence(seq, (n, M), dens, peak + 1)
+    seq, grid, dens, nmax = random_case(seed)
+    want = recurrence(seq, grid, dens, nmax)
     for mode in ("resident", "stream"):
         got = epg.simulate(seq, init=epg.StateMatrix(density=dens), mode=mode)
         assert maxerr(got, want) <= ATOL, (mode, seed)
