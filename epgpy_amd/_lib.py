@@ -17,6 +17,10 @@ MAX_DIMS = 8
 MAX_SPACES = 4
 SUPPORTED_K = (64, 128, 256, 512, 1024)
 RESIDENT_ONLY_K = 2048   # state-resident launches from equilibrium only: four wavefronts per voxel (csrc/epgx_split.hip)
+# state matrices above these capacities: the tiled path (csrc/epgx_tiled.hip) -- windows of 64 TILED_M orders per wavefront,
+# a halo of TILED_H orders on either side, interiors of TILED_W orders; the state in HBM at a multiple of 64 orders
+TILED_M, TILED_H = 8, 32
+TILED_W = 64 * TILED_M - 2 * TILED_H
 PACKED_K = (16, 32)  # state-resident only: four / two voxels per wavefront (csrc/epgx_packed_kernels.hip.h)
 MAX_DERIV_K = 1024  # derivative plans: the state and its derivative states of a voxel live in registers (one wavefront per voxel)
 
@@ -118,6 +122,9 @@ SYMBOLS = {
     "epgx_state_axpy": (_i, [_p, _p, ctypes.c_double, _i32]),
     "epgx_run": (_i, [_p, _p, _i32, _i32, _i64, _i64, _p, _p, _i32, _p, _i64, _i64]),
     "epgx_kernel_for": (_i, [_p, _p, _i32, _i32, _i32, _p, _p, ctypes.c_char_p, _i64]),
+    "epgx_run_tiled": (_i, [_p, _p, _i64, _i64, _p, _i32, _p, _i64, _i64, _i64]),
+    "epgx_tiled_info": (_i, [_p, _p, _i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i64),
+                             ctypes.POINTER(_i32), ctypes.c_char_p, _i64]),
     "epgx_signal_reduce": (_i, [_p, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _i64, _i64]),
     "epgx_simulate_f64": (_i, [_p, ctypes.POINTER(PlanDesc), _i32, _p, _p, _p, _p, _i32]),
     "epgx_simulate_sharded_f64": (_i, [ctypes.POINTER(PlanDesc), _i32, _i32, _p, _p, _i32]),
@@ -138,7 +145,7 @@ SYMBOLS = {
     "epgx_run_to_host": (_i, [_p, _p, _i32, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _i32]),
     "epgx_download_2d": (_i, [_p, _p, _i64, _p, _i64, _i64, _i64]),
 }
-ABI_VERSION = 7
+ABI_VERSION = 8
 COMM_ID_BYTES = 128
 
 _lock = threading.Lock()
@@ -701,3 +708,20 @@ def run(ctx, plan, op_begin, op_end, vox0, nvox, state_in, state_out, K, signal_
                            state_out.handle if state_out is not None else None, int(K),
                            ctypes.c_void_p(signal_ptr) if signal_ptr else None, int(signal_ld),
                            int(signal_col0)), "epgx_run")
+
+
+def run_tiled(ctx, plan, vox0, nvox, state_in, Kbuf, signal_ptr, signal_ld, signal_col0, slab_voxels=0):
+    """the whole plan on the tiled path (state matrices of any length, include/epgx.h epgx_run_tiled)"""
+    check(ctx.lib.epgx_run_tiled(ctx.handle, plan.handle, int(vox0), int(nvox), state_in.handle if state_in is not None else None,
+                                 int(Kbuf), ctypes.c_void_p(signal_ptr) if signal_ptr else None, int(signal_ld), int(signal_col0),
+                                 int(slab_voxels)), "epgx_run_tiled")
+
+
+def tiled_info(ctx, plan, Kbuf, top0=0):
+    """the schedule epgx_run_tiled follows: dict(blocks, shifts, tile_launches, peak, names)"""
+    blocks, shifts, peak = _i32(), _i32(), _i32()
+    tiles = _i64()
+    buf = ctypes.create_string_buffer(160)
+    check(ctx.lib.epgx_tiled_info(ctx.handle, plan.handle, int(Kbuf), int(top0), ctypes.byref(blocks), ctypes.byref(shifts),
+                                  ctypes.byref(tiles), ctypes.byref(peak), buf, len(buf)), "epgx_tiled_info")
+    return dict(blocks=blocks.value, shifts=shifts.value, tile_launches=tiles.value, peak=peak.value, names=buf.value.decode())

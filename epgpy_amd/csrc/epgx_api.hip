@@ -38,6 +38,7 @@
 #include "epgx_deriv_kernels.hip.h"
 #include "epgx_launch.h"
 #include "epgx_launch_grow.h"
+#include "epgx_launch_tiled.h"
 
 using namespace epgx;
 
@@ -3043,6 +3044,288 @@ extern "C" int epgx_kernel_for(epgx_ctx *ctx, const epgx_plan *plan, int32_t op_
     if (!ctx || !plan) return fail(EPGX_ERR_INVALID, "epgx_kernel_for: NULL argument");
     const int64_t nvox = in ? in->nvox : (out ? out->nvox : plan->nvox_total);
     return run_or_name(ctx, plan, op_begin, op_end, 0, nvox, in, out, K, nullptr, 0, 0, name_out, name_bytes);
+}
+
+// ------------------------------------------------------------------------------ tiled runs: state matrices of any length
+// (epgx_tiled.hip).  The plan's records are packed as for any capacity, with every truncation explicit (no capacity drops
+// orders here), then
+//   * a shift by 2 .. H orders becomes |n| records of S(+-1) (the same moves, the truncation and the probe on the last);
+//   * a shift by more than H becomes a step of its own (tiled_shift_kernel): the stages in front of it stay a record, the
+//     probe behind it becomes one;
+// and the list is cut into blocks whose shifts add up to at most H.  `top` = the highest order that can hold anything, as in
+// get_packed plus truncations and resets; a launch covers the tiles up to the top after its block, and at least the tiles the
+// launch before the previous one wrote into the same buffer (so no tile of the output buffer keeps a stale value).
+struct TiledStep {
+    int rec0 = 0, rec1 = 0;    // block: records [rec0, rec1); a shift step has none
+    int shift = 0;             // shift step: n, |n| > H
+    int kmax = INT32_MAX;      // shift step: truncation above kmax
+    int tiles = 0;             // tiles the launch covers
+    int top = 0;               // highest order that can hold anything after the step
+};
+struct TiledSchedule {
+    std::vector<Rec> recs;
+    std::vector<TiledStep> steps;
+    int peak = 0, n_shift = 0;
+    int64_t tile_launches = 0;
+    bool has_adc = false;
+};
+
+static void tiled_knobs(int &M, int &H) {   // EPGX_TILED_M=16: 16 orders per lane, halo 64 (measurements)
+    static const int m = env_int("EPGX_TILED_M", 8);
+    M = m == 16 ? 16 : 8;
+    H = M == 16 ? 64 : 32;
+}
+
+static Rec with_leaf(Rec r) {
+    r.flags &= 0xffffffu;
+    r.flags |= record_leaf<false>(r.flags, r.shift) << 24;
+    return r;
+}
+
+static int tiled_schedule(const epgx_plan *pl, int Kbuf, int top0, int M, int H, TiledSchedule &ts) {
+    std::vector<Rec> packed;
+    std::vector<DRec> drecs;
+    std::vector<ELog> elog;
+    bool use_lds = false;
+    const int n_ops = (int)pl->ops.size();
+    pack_records(pl->ops, pl->zero_pattern, pl->dops, pl->dpattern, 0, n_ops, 1 << 30, pl->fold, (uint32_t)(pl->n_pool * 8), packed, drecs,
+                 use_lds, ts.has_adc, &pl->log_of, &elog);
+    const int W = 64 * M - 2 * H;
+    struct Item { Rec r; int big; };    // big: 0, or the shift of a step of its own
+    std::vector<Item> items;
+    const uint32_t probe = F_ADC | F_ADC_Z;
+    for (const Rec &r : packed) {
+        const int n = ((r.flags & F_S) && !(r.flags & F_FOLD)) ? r.shift : 1;
+        if (!(r.flags & F_S) || std::abs(n) <= 1) {
+            items.push_back({r, 0});
+            continue;
+        }
+        Rec head = r;
+        head.flags &= ~(F_TRUNC | probe);
+        if (std::abs(n) > H) {
+            head.flags &= ~F_S;
+            head.shift = 0;
+            if (head.flags & 0xffffffu) items.push_back({with_leaf(head), 0});
+            Rec step;
+            memset(&step, 0, sizeof(step));
+            step.flags = r.flags & F_TRUNC;
+            step.kmax = r.kmax;
+            items.push_back({step, n});
+        } else {
+            head.shift = n > 0 ? 1 : -1;
+            items.push_back({with_leaf(head), 0});
+            for (int j = 1; j < std::abs(n); ++j) {
+                Rec one;
+                memset(&one, 0, sizeof(one));
+                one.flags = F_S | (j + 1 == std::abs(n) ? (r.flags & F_TRUNC) : 0u);
+                one.shift = n > 0 ? 1 : -1;
+                one.kmax = r.kmax;
+                items.push_back({with_leaf(one), 0});
+            }
+            if (!(r.flags & probe)) continue;
+            Rec &last = items.back().r;
+            last.flags |= r.flags & probe;
+            last.slot = r.slot;
+            last = with_leaf(last);
+            continue;
+        }
+        if (r.flags & probe) {
+            Rec adc;
+            memset(&adc, 0, sizeof(adc));
+            adc.flags = r.flags & probe;
+            adc.slot = r.slot;
+            items.push_back({with_leaf(adc), 0});
+        }
+    }
+    ts.recs.clear();
+    ts.steps.clear();
+    ts.peak = top0;
+    ts.n_shift = 0;
+    ts.tile_launches = 0;
+    int top = top0, units = 0;
+    int cov[2] = {top0 / W + 1, 0};   // tiles the latest step wrote into buffer 0 / 1 (the start state is in buffer 0)
+    TiledStep cur;
+    auto close = [&](TiledStep st) {
+        const int buf = (int)(ts.steps.size() + 1) & 1;      // the buffer this step writes
+        st.top = top;
+        st.tiles = std::max(top / W + 1, cov[buf]);
+        cov[buf] = st.tiles;
+        ts.tile_launches += st.tiles;
+        ts.steps.push_back(st);
+    };
+    for (const Item &it : items) {
+        const Rec &r = it.r;
+        if (it.big) {
+            if (cur.rec1 > cur.rec0) close(cur);
+            TiledStep st;
+            st.shift = it.big;
+            top += std::abs(it.big);
+            if (r.flags & F_TRUNC) {
+                st.kmax = r.kmax;
+                top = std::min(top, r.kmax);
+            }
+            ts.peak = std::max(ts.peak, top);
+            close(st);
+            ++ts.n_shift;
+            cur = TiledStep();
+            cur.rec0 = cur.rec1 = (int)ts.recs.size();
+            units = 0;
+            continue;
+        }
+        const int u = ((r.flags & F_S0) ? 1 : 0) + ((r.flags & F_S) ? 1 : 0);
+        if (units + u > H && cur.rec1 > cur.rec0) {
+            close(cur);
+            cur = TiledStep();
+            cur.rec0 = cur.rec1 = (int)ts.recs.size();
+            units = 0;
+        }
+        units += u;
+        if (r.flags & (F_RESET | F_PD_RESET)) top = 0;
+        if (r.flags & F_S0) top += 1;
+        if (r.flags & F_S) top += 1;
+        if (r.flags & F_TRUNC) top = std::min(top, r.kmax);
+        ts.peak = std::max(ts.peak, top);
+        ts.recs.push_back(r);
+        cur.rec1 = (int)ts.recs.size();
+    }
+    if (cur.rec1 > cur.rec0) close(cur);
+    if (ts.peak >= Kbuf)
+        return fail(EPGX_ERR_INVALID, "epgx_run_tiled: the plan populates orders up to %d, Kbuf=%d", ts.peak, Kbuf);
+    return EPGX_OK;
+}
+
+static int tiled_check(epgx_ctx *ctx, const epgx_plan *pl, int32_t Kbuf, const char *who) {
+    if (!ctx || !pl) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
+    if (pl->ctx != ctx) return fail(EPGX_ERR_INVALID, "%s: plan belongs to another context", who);
+    if (Kbuf < 64 || Kbuf % 64 != 0 || Kbuf > (1 << 24)) return fail(EPGX_ERR_INVALID, "%s: Kbuf=%d is not a multiple of 64 in [64, 2^24]", who, Kbuf);
+    if (pl->n_vars > 0) return fail(EPGX_ERR_UNSUPPORTED, "%s: plans with derivative states run at K <= 1024 (epgx_run)", who);
+    for (size_t i = 0; i < pl->ops.size(); ++i) {
+        const int oc = pl->ops[i].opcode;
+        if (oc == EPGX_OP_X || oc == EPGX_OP_GS || oc == EPGX_OP_D)
+            return fail(EPGX_ERR_UNSUPPORTED, "%s: operator %zu: exchange, gather shifts and diffusion run at K <= 1024 (epgx_run)", who, i);
+    }
+    return EPGX_OK;
+}
+
+extern "C" int epgx_tiled_info(epgx_ctx *ctx, const epgx_plan *plan, int32_t Kbuf, int32_t top0, int32_t *blocks, int32_t *shifts,
+                               int64_t *tile_launches, int32_t *peak, char *names, int64_t name_bytes) {
+    if (int rc = tiled_check(ctx, plan, Kbuf, "epgx_tiled_info")) return rc;
+    if (top0 < 0 || top0 >= Kbuf) return fail(EPGX_ERR_INVALID, "epgx_tiled_info: top0=%d outside [0, Kbuf)", top0);
+    int M, H;
+    tiled_knobs(M, H);
+    TiledSchedule ts;
+    if (int rc = tiled_schedule(plan, Kbuf, top0, M, H, ts)) return rc;
+    const int nb = (int)ts.steps.size() - ts.n_shift;
+    if (blocks) *blocks = nb;
+    if (shifts) *shifts = ts.n_shift;
+    if (tile_launches) *tile_launches = ts.tile_launches;
+    if (peak) *peak = ts.peak;
+    if (names && name_bytes > 1) {
+        std::string n = nb ? "tiled_kernel<" + std::to_string(M) + ", " + std::to_string(H) + ">" : std::string();
+        if (ts.n_shift) n += std::string(n.empty() ? "" : " + ") + "tiled_shift";
+        snprintf(names, (size_t)name_bytes, "%s", n.empty() ? "none" : n.c_str());
+    }
+    return EPGX_OK;
+}
+
+extern "C" int epgx_run_tiled(epgx_ctx *ctx, const epgx_plan *plan_c, int64_t vox0, int64_t nvox, const epgx_state *in, int32_t Kbuf,
+                              void *signal, int64_t signal_ld, int64_t signal_col0, int64_t slab_voxels) {
+    if (int rc = tiled_check(ctx, plan_c, Kbuf, "epgx_run_tiled")) return rc;
+    epgx_plan *pl = const_cast<epgx_plan *>(plan_c);
+    if (nvox < 0 || vox0 < 0 || vox0 + nvox > pl->nvox_total)
+        return fail(EPGX_ERR_INVALID, "epgx_run_tiled: voxel range [%lld,%lld) outside the grid (%lld voxels)", (long long)vox0,
+                    (long long)(vox0 + nvox), (long long)pl->nvox_total);
+    if (slab_voxels < 0) return fail(EPGX_ERR_INVALID, "epgx_run_tiled: slab_voxels < 0");
+    if (in) {
+        if (in->ctx != ctx) return fail(EPGX_ERR_INVALID, "epgx_run_tiled: `in` belongs to another context");
+        if (in->nvox != nvox)
+            return fail(EPGX_ERR_INVALID, "epgx_run_tiled: `in` holds %lld voxels, range has %lld", (long long)in->nvox, (long long)nvox);
+        if (in->K > 1024) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run_tiled: `in` has %d orders (at most 1024)", in->K);
+        if (in->K > Kbuf) return fail(EPGX_ERR_INVALID, "epgx_run_tiled: `in` has %d orders, Kbuf=%d", in->K, Kbuf);
+    }
+    int M, H;
+    tiled_knobs(M, H);
+    TiledSchedule ts;
+    if (int rc = tiled_schedule(pl, Kbuf, in ? in->K - 1 : 0, M, H, ts)) return rc;
+    if (ts.has_adc) {
+        if (!signal) return fail(EPGX_ERR_INVALID, "epgx_run_tiled: the plan contains an ADC but signal is NULL");
+        if (signal_col0 < 0 || signal_col0 + nvox > signal_ld)
+            return fail(EPGX_ERR_INVALID, "epgx_run_tiled: signal columns [%lld,%lld) exceed signal_ld=%lld", (long long)signal_col0,
+                        (long long)(signal_col0 + nvox), (long long)signal_ld);
+    }
+    if (nvox == 0 || ts.steps.empty()) return EPGX_OK;
+    if (int rc = set_device(ctx)) return rc;
+    std::lock_guard<std::mutex> plan_guard(pl->cache_lock);
+    if (int rc = ensure_vidx(pl, vox0, nvox)) return rc;
+    // two buffers [slab][3][Kbuf] + the density: at most 8 GiB per slab (as the two legs at 2048 orders)
+    const int64_t per_voxel = (int64_t)2 * 3 * Kbuf * sizeof(d2) + sizeof(double);
+    int64_t slab = std::min<int64_t>((nvox + 3) & ~(int64_t)3, std::max<int64_t>(4, (((int64_t)8 << 30) / per_voxel) & ~(int64_t)3));
+    if (knobs().slab_voxels > 0) slab = std::min<int64_t>(slab, (knobs().slab_voxels + 3) & ~3);
+    if (slab_voxels > 0) slab = std::min<int64_t>(slab, slab_voxels);
+    const size_t buf_bytes = (size_t)slab * 3 * Kbuf * sizeof(d2);
+    void *mem = nullptr, *d_recs = nullptr;
+    const size_t rec_bytes = (ts.recs.size() + 2) * sizeof(Rec);     // two padding records (the kernel fetches ahead)
+    hipError_t e = dev_alloc(ctx, &d_recs, rec_bytes);
+    if (e == hipSuccess) e = dev_alloc(ctx, &mem, 2 * buf_bytes + (size_t)slab * sizeof(double));
+    if (e != hipSuccess) {
+        dev_free(ctx, d_recs);
+        return fail(EPGX_ERR_NOMEM, "epgx_run_tiled: %lld voxels x 2 x %d orders: %s", (long long)slab, Kbuf, hipGetErrorString(e));
+    }
+    ts.recs.resize(ts.recs.size() + 2);
+    memset(&ts.recs[ts.recs.size() - 2], 0, 2 * sizeof(Rec));
+    e = hipMemcpyAsync(d_recs, ts.recs.data(), rec_bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);     // (the host vector goes away with this call)
+    d2 *buf[2] = {(d2 *)mem, (d2 *)((char *)mem + buf_bytes)};
+    double *dens = (double *)((char *)mem + 2 * buf_bytes);
+    if (tracing())
+        fprintf(stderr, "[epgx] run_tiled: %zu records, %zu steps (%d shifts by more than %d), %lld tile launches, peak order %d, Kbuf %d, "
+                        "slabs of %lld voxels\n", ts.recs.size() - 2, ts.steps.size(), ts.n_shift, H, (long long)ts.tile_launches, ts.peak,
+                Kbuf, (long long)slab);
+    const int W = 64 * M - 2 * H;
+    for (int64_t c0 = 0; c0 < nvox && e == hipSuccess; c0 += slab) {
+        const int64_t nv = std::min(slab, nvox - c0);
+        const size_t used = (size_t)nv * 3 * Kbuf * sizeof(d2);
+        e = hipMemsetAsync(buf[0], 0, used, ctx->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(buf[1], 0, used, ctx->stream);
+        if (e == hipSuccess && in)
+            e = hipMemcpy2DAsync(buf[0], (size_t)Kbuf * sizeof(d2), in->data + (size_t)c0 * 3 * in->K, (size_t)in->K * sizeof(d2),
+                                 (size_t)in->K * sizeof(d2), (size_t)nv * 3, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e == hipSuccess && in) e = hipMemcpyAsync(dens, in->dens + c0, (size_t)nv * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
+        if (e == hipSuccess && !in) e = epgx_launch_tiled_equilibrium(ctx->stream, buf[0], dens, nullptr, nv, Kbuf);
+        for (size_t j = 0; j < ts.steps.size() && e == hipSuccess; ++j) {
+            const TiledStep &st = ts.steps[j];
+            const d2 *src = buf[j & 1];
+            d2 *dst = buf[(j + 1) & 1];
+            if (st.shift) {
+                e = epgx_launch_tiled_shift(ctx->stream, src, dst, nv, Kbuf, (int32_t)std::min<int64_t>(Kbuf, (int64_t)st.tiles * W), st.shift,
+                                            st.kmax);
+                continue;
+            }
+            TiledArgs a;
+            memset(&a, 0, sizeof(a));
+            a.in = src;
+            a.out = dst;
+            a.dens = dens;
+            a.nvox = nv;
+            a.recs = (const Rec *)d_recs;
+            a.coef = pl->d_coef;
+            a.signal = signal ? (d2 *)signal + signal_col0 + c0 : nullptr;
+            a.signal_ld = signal_ld;
+            a.rec0 = st.rec0;
+            a.rec1 = st.rec1;
+            a.Kbuf = Kbuf;
+            a.tiles = st.tiles;
+            a.t.vidx = pl->d_vidx ? pl->d_vidx + c0 : nullptr;
+            a.t.vidx_ld = pl->vidx_nvox;
+            a.t.vox0 = vox0 + c0;
+            a.t.dense_spaces = pl->dense_spaces;
+            e = epgx_launch_tiled(ctx->stream, a, M, H, pl->n_spaces);
+        }
+    }
+    dev_free(ctx, mem);
+    dev_free(ctx, d_recs);
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_run_tiled: %s", hipGetErrorString(e));
+    return EPGX_OK;
 }
 
 // ------------------------------------------------------------------------------ RCCL (loaded on first use)

@@ -736,7 +736,15 @@ def _simulate_device(sequence, probes, init, mode, devices, options, exact_parti
                                             nstate0=init.nstate if init is not None else 0,
                                             kspace0=init._kspace if init is not None else None,
                                             dense_start=init is not None, fuse=fuse)
-    K = enc.capacity(at_least=(init.nstate + 1) if init is not None else 0, resident=(init is None and mode == "resident"))
+    try:
+        K = enc.capacity(at_least=(init.nstate + 1) if init is not None else 0, resident=(init is None and mode == "resident"))
+    except NotImplementedError:
+        # above the capacity classes: the tiled path (state in HBM, any length) -- state-resident plans of 1-D shifts on one
+        # GPU, from equilibrium or from a start state that itself fits a capacity class
+        if not (mode == "resident" and len(devices) == 1 and enc.tiled_ok()
+                and (init is None or init.nstate < _lib.SUPPORTED_K[-1])):
+            raise
+        return _simulate_tiled(sequence, enc, records, init, devices, to_host, dtype)
     if init is not None:
         K = max(K, init._state.K)
     elif mode == "resident" and packed and enc.packable_nd():
@@ -765,11 +773,7 @@ def _simulate_device(sequence, probes, init, mode, devices, options, exact_parti
             begin = end
     # Adc(weights=..., reduce=...): the weighted sums over grid axes run on the device
     # (epgx_signal_reduce), only the reduced records travel to the host
-    groups = _reduction_groups(records, enc.grid)
-    need_raw = any(id(pb) not in groups for _, slots in records for pb, _ in slots)
-    plain = bool(records) and all(op._is_plain() and pb._is_plain() for op, slots in records for pb, _ in slots)
-    if not to_host and not plain:
-        raise NotImplementedError('out="device" returns raw F0 / Z0 records: no weights / reduce / phase / post on the probes')
+    groups, need_raw = _device_records(records, enc, to_host)
     raw = None
     if mode != "stream":
         # short state matrices (max_nstate <= 15, the reference's usual MRF setting): 4 voxels per wave
@@ -783,6 +787,38 @@ def _simulate_device(sequence, probes, init, mode, devices, options, exact_parti
             fleet.run_to_host(K_run, raw)
         else:
             fleet.run(K_run, state_in)
+    return _finish_device(sequence, records, enc, fleet, groups, need_raw, raw, to_host, dtype)
+
+
+def _device_records(records, enc, to_host):
+    """(the device reductions of the probes, whether raw records are downloaded too); out="device" takes plain probes only"""
+    groups = _reduction_groups(records, enc.grid)
+    need_raw = any(id(pb) not in groups for _, slots in records for pb, _ in slots)
+    plain = bool(records) and all(op._is_plain() and pb._is_plain() for op, slots in records for pb, _ in slots)
+    if not to_host and not plain:
+        raise NotImplementedError('out="device" returns raw F0 / Z0 records: no weights / reduce / phase / post on the probes')
+    return groups, need_raw
+
+
+def _simulate_tiled(sequence, enc, records, init, devices, to_host, dtype):
+    """a state matrix longer than the capacity classes (include/epgx.h epgx_run_tiled): one GPU; the start state, if any,
+    is read as it is (its K orders count as populated)"""
+    state_in, top0 = None, None
+    if init is not None:
+        work = init.copy()  # never mutate the caller's init (functions.py:149)
+        work._broadcast_to(enc.grid)
+        state_in = work._state
+        top0 = state_in.K - 1
+    Kbuf = enc.tiled_capacity(top0)
+    groups, need_raw = _device_records(records, enc, to_host)
+    fleet = _Fleet(enc, None, devices, init._ctx if init is not None else None)
+    _lib.run_tiled(fleet.ctxs[0], fleet.plans[0], 0, enc.nvox, state_in, Kbuf, fleet.sigs[0].ptr.value, enc.nvox, 0)
+    return _finish_device(sequence, records, enc, fleet, groups, need_raw, None, to_host, dtype)
+
+
+def _finish_device(sequence, records, enc, fleet, groups, need_raw, raw, to_host, dtype):
+    """the probes' values (or out="device" handles) from the signal buffers of a finished run"""
+    ctx, sig = fleet.ctxs[0], fleet.sigs[0]
     reduced = _reduce_groups(groups, fleet.reduce)
     if not to_host:
         # out="device": the signal stays in HBM (dictionary matching, further reductions ...): per probe a handle on

@@ -33,6 +33,7 @@ class Encoder:
         self.pool = []
         self.pool_size = 0
         self.nstate = int(nstate0)
+        self.nstate0 = int(nstate0)
         self.peak = int(nstate0)
         self.n_adc = 0
         # n-D integer shifts: the coordinate set is planned on the host (kspace.py); None while
@@ -328,6 +329,60 @@ class Encoder:
             f"{need} phase states per voxel exceed the device capacity {_lib.SUPPORTED_K[-1]} "
             f"({_lib.RESIDENT_ONLY_K} for simulate() of rotations / relaxation / shifts by one from equilibrium); "
             "bound the state matrix with max_nstate=...")
+
+    def tiled_ok(self):
+        """True if the plan can run on the tiled path (state matrices above the capacity classes, include/epgx.h
+        epgx_run_tiled): integer 1-D shifts, no derivative states, no n-D shifts / diffusion / gathers, no X"""
+        return (self.kspace is None and not self.deferred and not self.variables and self.exchange is None
+                and all(rec[0] not in (_lib.OP_D, _lib.OP_GS, _lib.OP_X) for rec in self.records))
+
+    def tiled_blocks(self, H=None, W=None, top0=None):
+        """the tiled path's schedule at operator level: [(op_begin, op_end, tiles_after)].  A block ends before the shift
+        that would take the sum of its |n| above H; a shift by more than H is a block of its own; tiles_after = the tiles of
+        W orders a launch of the block covers: up to the highest order that can hold anything after it, and at least as
+        many as the block before the previous one wrote (the buffers alternate).  `top0`: the highest order of the start
+        state (default: the encoder's nstate0).  The library cuts the fused records the same way (epgx_run_tiled); the
+        fusion of operators into records can only move its cuts, not the populated top they follow"""
+        return self._tiled_walk(H, W, top0)[0]
+
+    def tiled_capacity(self, top0=None):
+        """Kbuf of the tiled path: the highest order the plan can populate + 1, rounded up to a multiple of 64"""
+        peak = self._tiled_walk(None, None, top0)[1]
+        return (peak + 1 + 63) // 64 * 64
+
+    def _tiled_walk(self, H, W, top0):
+        H = _lib.TILED_H if H is None else int(H)
+        W = _lib.TILED_W if W is None else int(W)
+        top = self.nstate0 if top0 is None else int(top0)
+        peak, units, begin, blocks = top, 0, 0, []
+        cov = [top // W + 1, 0]          # tiles last written into buffer 0 (the start state) / 1
+
+        def close(end):
+            buf = (len(blocks) + 1) & 1
+            tiles = max(top // W + 1, cov[buf])
+            cov[buf] = tiles
+            blocks.append((begin, end, tiles))
+
+        for i, rec in enumerate(self.records):
+            opcode, ia, ib = rec[0], rec[2], rec[3]
+            if opcode == _lib.OP_RESET:
+                top = 0
+            if opcode != _lib.OP_S:
+                continue
+            n = abs(int(ia))
+            if n > H or units + n > H:
+                if i > begin:
+                    close(i)
+                begin, units = i, 0
+            top = min(top + n, int(ib))
+            peak = max(peak, top)
+            units += n
+            if n > H:
+                close(i + 1)
+                begin, units = i + 1, 0
+        if begin < len(self.records):
+            close(len(self.records))
+        return blocks, peak
 
     def arrays(self, K=None):
         if self.deferred:

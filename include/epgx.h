@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define EPGX_ABI_VERSION 7
+#define EPGX_ABI_VERSION 8
 #define EPGX_MAX_DIMS 8    /* grid dimensions                        */
 #define EPGX_MAX_SPACES 4  /* distinct operator broadcast patterns   */
 #define EPGX_WAVE 64       /* k-states per lane-register (wave64)    */
@@ -345,7 +345,7 @@ int epgx_state_axpy(epgx_state *dst, const epgx_state *src, double alpha, int32_
  *         plans with derivative states: up to 1024, at 1024 with ONE variable per plan (EPGX_ERR_UNSUPPORTED otherwise);
  *         or 16 / 32 for short state matrices (state-resident only; shifts by +-1,
  *         T / T0 / E operators and probes, at K = 16 also EPGX_OP_GS / EPGX_OP_D whose tables are then
- *         laid out [3][16] -- EPGX_ERR_UNSUPPORTED otherwise)
+ *         laid out [3][16] -- EPGX_ERR_UNSUPPORTED otherwise).  Longer state matrices: epgx_run_tiled
  * With in = out = NULL the state never leaves registers (state-resident mode); calling it once
  * per echo with in = out streams the state through HBM once per call (per-timestep mode).
  * State-resident launches from equilibrium at K >= 256 whose records mostly run while the state matrix is still short (every
@@ -366,6 +366,29 @@ int epgx_run(epgx_ctx *ctx, const epgx_plan *plan, int32_t op_begin, int32_t op_
  * number of voxels.  For tests and tools that pin the kernel of a configuration. */
 int epgx_kernel_for(epgx_ctx *ctx, const epgx_plan *plan, int32_t op_begin, int32_t op_end, int32_t K, const epgx_state *in,
                     epgx_state *out, char *name_out, int64_t name_bytes);
+
+/* The whole plan over voxels [vox0, vox0 + nvox) for state matrices of ANY length (the reference's unbounded growth,
+ * epgpy/shift.py:86,98): the state lives in HBM as two buffers [nvox][3][Kbuf] c128 that alternate, cut into tiles of W
+ * orders; one wavefront owns one (voxel, tile) and runs a BLOCK of records in registers on a window of the tile plus H orders
+ * on either side (every shift by one spoils one order at each edge of the window, so the tile is exact after a block whose
+ * shifts add up to at most H).  Only the tiles that can hold anything after a block are launched.  A record that shifts by
+ * more than H orders is a launch of its own (a copy with the k = 0 fold).  The library cuts the plan into blocks.
+ *   in     : start state (any epgx_state, K <= 1024, nvox voxels) or NULL = equilibrium; it is not modified
+ *   Kbuf   : a multiple of 64, at least the highest order the plan can populate + 1 (counted from in->K - 1 with a start state)
+ *   signal : as for epgx_run (column signal_col0 + j)
+ *   slab_voxels : voxels per slab (0: the library's choice -- two buffers of at most 8 GiB; EPGX_SLAB_VOXELS lowers it)
+ * Plans: T / T0 / MAT / MAT0 / E / S (any integer shift) / probes / SPOILER / RESET / PD; one GPU.
+ * Errors: EPGX_ERR_INVALID (arguments, Kbuf too small or not a multiple of 64, in->K > Kbuf), EPGX_ERR_UNSUPPORTED
+ * (derivative states, EPGX_OP_X / EPGX_OP_GS / EPGX_OP_D in the plan, in->K > 1024), EPGX_ERR_NOMEM (the buffers of one slab), EPGX_ERR_HIP. */
+int epgx_run_tiled(epgx_ctx *ctx, const epgx_plan *plan, int64_t vox0, int64_t nvox, const epgx_state *in, int32_t Kbuf,
+                   void *signal, int64_t signal_ld, int64_t signal_col0, int64_t slab_voxels);
+
+/* The schedule epgx_run_tiled would follow for `plan` at Kbuf (no launch): blocks = launches of the tiled kernel, shifts =
+ * launches of the copy kernel for shifts by more than H orders, tile_launches = sum over all launches of the tiles covered,
+ * peak = the highest order that can hold anything, names = the kernel names separated by " + ", e.g.
+ * "tiled_kernel<8, 32> + tiled_shift".  top0: highest order of the start state (0 from equilibrium).  Any output may be NULL. */
+int epgx_tiled_info(epgx_ctx *ctx, const epgx_plan *plan, int32_t Kbuf, int32_t top0, int32_t *blocks, int32_t *shifts,
+                    int64_t *tile_launches, int32_t *peak, char *names, int64_t name_bytes);
 
 /* The whole plan, state-resident, over voxels [vox0, vox0 + nvox) in SLABS whose signal columns travel to the host while
  * the next slab computes (second stream + events): what a caller with host buffers waits for is then the PCIe copy
