@@ -74,6 +74,7 @@ struct Knobs {
     int slab_voxels; // EPGX_SLAB_VOXELS (tests): voxels per slab of the two-leg launch at 2048 orders (0: as many as 8 GiB of scratch hold)
     bool split_grow; // EPGX_SPLIT_GROW (default 1): K = 2048 in two legs where it pays (one wavefront per voxel up to 512 populated orders)
     bool xrun;      // EPGX_XRUN (default 1): ranges with exchange (EPGX_OP_X) on xrun_kernel where it covers them; 0: always the split path
+    bool reach;     // EPGX_REACH (default 1): a range of rows_grow_kernel runs at the orders that can still reach a probe (grow_reach); 0: at 16 / 32 / 64
     int cgrow;      // EPGX_CGROW: 0 off, 1 (default): growing launches at K = 256 .. 1024, at K = 128 when 60 % of the records run below 64 orders; 2: at K = 128 whenever the other capacities would
 };
 int env_int(const char *name, int fallback) {
@@ -87,7 +88,7 @@ const Knobs &knobs() {
                             env_int("EPGX_GROW_MIN", 1),    env_int("EPGX_FOLD", 1) != 0,
                             getenv("EPGX_GROW_SHARE") ? atof(getenv("EPGX_GROW_SHARE")) : 0.1, env_int("EPGX_LEAD_FORWARD", 1) != 0,
                             env_int("EPGX_SLAB_VOXELS", 0), env_int("EPGX_SPLIT_GROW", 1) != 0, env_int("EPGX_XRUN", 1) != 0,
-                            env_int("EPGX_CGROW", 1)};
+                            env_int("EPGX_REACH", 1) != 0,  env_int("EPGX_CGROW", 1)};
     return k;
 }
 bool tracing() { return getenv("EPGX_TRACE") != nullptr; }
@@ -220,7 +221,8 @@ struct PackedRange {
     Rec *d_runs = nullptr;    // the same records with runs of identical ones folded (rows_kernel<.., RUNS>), or null
     int n_runs = 0;
     Rec *d_grow = nullptr;    // K = 64: the run-folded records cut where the populated orders outgrow 16 and 32 (rows_grow_kernel), or null
-    int n_grow = 0, grow1 = 0, grow2 = 0;   // records [0, grow1) run at 16 orders per voxel, [grow1, grow2) at 32, the rest at 64
+    int n_grow = 0, grow1 = 0, grow2 = 0;   // records [0, grow1) run at 16 orders per voxel, [grow1, grow2) at 32, the rest at 64 ...
+    int grow_cap[3] = {16, 32, 64};         // ... or at fewer, where fewer can still reach a probe (grow_reach)
     Rec *d_druns = nullptr;   // derivative plans, K = 64: the records with a header in front of every run of same-shape
     DRec *d_ddruns = nullptr; // fused-echo records (drun_kernel), and their DRecs (a header's is all zero); or null
     DRecB *d_bdruns = nullptr; // ... and, when the runs are of records folded at run time (DRUN_FOLD), E_b's logarithmic partials
@@ -1793,13 +1795,13 @@ static void pack_records(const std::vector<epgx_op> &all, const std::vector<uint
 // outgrow 16 and 32 (rows_grow_kernel: the reference grows its state matrix the same way, functions.py:135 / shift.py:86).
 // `top` = the highest order that can hold anything: every S(+-1) of a record adds one (resets and truncations are ignored:
 // `top` only ever over-estimates, which is safe).  Repeat-count records and header runs are cut at the boundaries.
-// Returns the share of record executions that run below 64 orders.
-static double grow_split(const std::vector<Rec> &runs, std::vector<Rec> &out, int &n1, int &n2) {
+// work[p] = the record executions of range p.
+static void grow_split(const std::vector<Rec> &runs, std::vector<Rec> &out, int &n1, int &n2, double work[3]) {
     auto shifts_of = [](const Rec &r) { return ((r.flags & F_S0) ? 1 : 0) + ((r.flags & F_S) ? 1 : 0); };
     static const int cap[3] = {15, 31, 1 << 30};
     int top = 0, phase = 0;
     n1 = n2 = -1;
-    double work[3] = {0, 0, 0};
+    work[0] = work[1] = work[2] = 0.0;
     auto next_phase = [&]() {
         if (phase == 0) n1 = (int)out.size();
         else n2 = (int)out.size();
@@ -1854,8 +1856,48 @@ static double grow_split(const std::vector<Rec> &runs, std::vector<Rec> &out, in
     if (n1 < 0) n1 = (int)out.size();
     if (n2 < 0) n2 = (int)out.size();
     n1 = std::min(n1, n2);
-    const double all = work[0] + work[1] + work[2];
-    return all > 0 ? (work[0] + work[1]) / all : 0.0;
+}
+
+// The orders per voxel the three ranges [0, n1), [n1, n2), [n2, end) of a cut list NEED (rows_grow_kernel writes no state: its
+// only outputs are the order-0 probes).  A coefficient of order k reaches order 0 through k shifts and through nothing else, so
+// at a record execution with `rem` shifts left up to the last probe of the list (its own included: a record shifts before it
+// probes) the orders above `rem` are dead, and the orders above `top` (grow_split) are empty: the execution needs
+// 1 + min(top, rem) orders, a range the maximum over its executions.  Like `top`, `rem` only ever over-estimates (resets,
+// spoilers and truncations are ignored).  Records behind the last probe need nothing; a list without a probe keeps 16 / 32 / 64.
+// cap[p] = the smallest of 16 / 32 / 64 that holds the need of range p, never more than the range has today.
+static void grow_reach(const std::vector<Rec> &list, int n1, int n2, int cap[3]) {
+    auto shifts_of = [](const Rec &r) { return ((r.flags & F_S0) ? 1 : 0) + ((r.flags & F_S) ? 1 : 0); };
+    struct Exec { int range, d, rep, top0; bool adc; };   // a record of the list: `rep` executions of `d` shifts each from top0 on
+    std::vector<Exec> ex;
+    int top = 0;
+    for (size_t i = 0, members = 0; i < list.size(); ++i) {
+        const Rec &r = list[i];
+        const uint32_t head = r.flags >> 24;
+        const int count = (int)((uint32_t)r.kmax >> 16);
+        if (!members && (head == LEAF_PAIR || head == LEAF_SINGLE)) {   // (a header's low flag bits are a shape code, not flags)
+            members = (size_t)(head == LEAF_PAIR ? 2 : 1) * (size_t)count;
+            continue;
+        }
+        const int rep = members ? 1 : std::max(count, 1);
+        if (members) --members;
+        ex.push_back({(int)i < n1 ? 0 : ((int)i < n2 ? 1 : 2), shifts_of(r), rep, top, (r.flags & F_ADC) != 0});
+        top += rep * ex.back().d;
+    }
+    static const int today[3] = {16, 32, 64};
+    int need[3] = {0, 0, 0};
+    bool probed = false;
+    long rem = 0;   // shifts behind the record at hand up to the last probe
+    for (size_t q = ex.size(); q-- > 0;) {
+        const Exec &x = ex[q];
+        if (!probed && !x.adc) continue;
+        probed = true;
+        for (int e = x.rep - 1; e >= 0; --e) {
+            rem += x.d;
+            const long t = (long)x.top0 + (long)x.d * (e + 1);
+            need[x.range] = (int)std::max<long>(need[x.range], 1 + std::min(t, rem));
+        }
+    }
+    for (int p = 0; p < 3; ++p) cap[p] = !probed ? today[p] : std::min(today[p], need[p] <= 16 ? 16 : (need[p] <= 32 ? 32 : 64));
 }
 
 static int get_packed(epgx_plan *pl, int begin, int end, int K, const PackedRange **out) {
@@ -2012,9 +2054,14 @@ static int get_packed(epgx_plan *pl, int begin, int end, int K, const PackedRang
     // when at least a tenth of the record executions run below 64 orders (a 20-echo train: 15 of 20; a 1000-TR train: 30 of 1000)
     std::vector<Rec> grow;
     if (K == 64 && !runs.empty()) {
-        const double early = grow_split(runs, grow, pr.grow1, pr.grow2);
-        if (early < knobs().grow_share) grow.clear();   // (EPGX_GROW_SHARE, measurements)
+        double work[3];
+        grow_split(runs, grow, pr.grow1, pr.grow2, work);
         if (knobs().grow_min >= 2) pr.grow1 = 0;   // (EPGX_GROW_MIN=2, measurements: first phase at 2 orders per lane)
+        if (knobs().reach) grow_reach(grow, pr.grow1, pr.grow2, pr.grow_cap);   // (EPGX_REACH=0, measurements: 16 / 32 / 64)
+        // the share of record executions that run below 64 orders: the first two ranges, and the last where it runs short
+        const double all = work[0] + work[1] + work[2];
+        const double early = all > 0 ? (work[0] + work[1] + (pr.grow_cap[2] < 64 ? work[2] : 0.0)) / all : 0.0;
+        if (early < knobs().grow_share) grow.clear();   // (EPGX_GROW_SHARE, measurements)
         if (tracing())
             for (size_t i = 0; i < grow.size(); ++i)
                 fprintf(stderr, "[epgx] grow list %zu: leaf %u flags %06x x %u (orders <= %d)%s\n", i, grow[i].flags >> 24, grow[i].flags & 0xffffffu,
@@ -2951,13 +2998,13 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
         a.recs = pr->d_grow;
         a.t.n_rec = pr->n_grow;
         if (tracing())
-            fprintf(stderr, "[epgx] run: %d records: [0, %d) at 16 orders per voxel, [%d, %d) at 32, the rest at 64\n", pr->n_grow, pr->grow1,
-                    pr->grow1, pr->grow2);
+            fprintf(stderr, "[epgx] run: %d records: [0, %d) at %d orders per voxel, [%d, %d) at %d, the rest at %d\n", pr->n_grow, pr->grow1,
+                    pr->grow_cap[0], pr->grow1, pr->grow2, pr->grow_cap[1], pr->grow_cap[2]);
         switch (pl->n_spaces) {
-        case 0: e = epgx_launch_rows_grow_nsp0(ctx->stream, a, pr->grow1, pr->grow2); break;
-        case 1: e = epgx_launch_rows_grow_nsp1(ctx->stream, a, pr->grow1, pr->grow2); break;
-        case 2: e = epgx_launch_rows_grow_nsp2(ctx->stream, a, pr->grow1, pr->grow2); break;
-        default: e = epgx_launch_rows_grow_nsp4(ctx->stream, a, pr->grow1, pr->grow2); break;
+        case 0: e = epgx_launch_rows_grow_nsp0(ctx->stream, a, pr->grow1, pr->grow2, pr->grow_cap); break;
+        case 1: e = epgx_launch_rows_grow_nsp1(ctx->stream, a, pr->grow1, pr->grow2, pr->grow_cap); break;
+        case 2: e = epgx_launch_rows_grow_nsp2(ctx->stream, a, pr->grow1, pr->grow2, pr->grow_cap); break;
+        default: e = epgx_launch_rows_grow_nsp4(ctx->stream, a, pr->grow1, pr->grow2, pr->grow_cap); break;
         }
         break;
     case FAM_ROWS:

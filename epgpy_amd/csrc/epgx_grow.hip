@@ -14,7 +14,7 @@
 
 using namespace epgx;
 
-hipError_t EPGX_CAT(epgx_launch_rows_grow_nsp, EPGX_NSP)(hipStream_t stream, const RunArgs &a, int n1, int n2) {
+hipError_t EPGX_CAT(epgx_launch_rows_grow_nsp, EPGX_NSP)(hipStream_t stream, const RunArgs &a, int n1, int n2, const int cap[3]) {
     const unsigned logical = (unsigned)((a.nvox + 4 * EPGX_GROW_WPB - 1) / (4 * EPGX_GROW_WPB));   // EPGX_GROW_WPB waves x 4 voxels per block
     unsigned blocks = logical;
     static const int gpw_env = getenv("EPGX_GPW") ? atoi(getenv("EPGX_GPW")) : 0;
@@ -22,7 +22,8 @@ hipError_t EPGX_CAT(epgx_launch_rows_grow_nsp, EPGX_NSP)(hipStream_t stream, con
     if ((uint64_t)logical * EPGX_GROW_WPB > 4u * 16u * 256u * 8u) blocks = (logical + gpw - 1) / gpw;
     RunTail t = a.t;
     t.n_blocks = logical;
-    hipLaunchKernelGGL((rows_grow_kernel<EPGX_NSP>), dim3(blocks), dim3(64 * EPGX_GROW_WPB), 0, stream, a.nvox, a.recs, a.coef, a.signal, a.signal_ld, t, n1, n2);
+    hipLaunchKernelGGL((rows_grow_kernel<EPGX_NSP>), dim3(blocks), dim3(64 * EPGX_GROW_WPB), 0, stream, a.nvox, a.recs, a.coef, a.signal, a.signal_ld, t, n1, n2,
+                       cap[0] / 16, cap[1] / 16, cap[2] / 16);   // (orders per voxel -> orders per lane)
     return hipGetLastError();
 }
 

@@ -612,7 +612,10 @@ __device__ __forceinline__ int32_t pool_i32(const __amdgpu_buffer_rsrc_t pool, u
 }
 // table int32 [3][16] at byte offset `tab` of the pool (the same for all voxels): for each new order the old order its F /
 // conj(F-) / Z comes from; GS_ZERO = nothing, | GS_CONJ = conjugate of the partner array (cf. gather_shift, epgx_kernels.hip.h)
-__device__ __forceinline__ void rows_gather_shift(State<1> &s, const __amdgpu_buffer_rsrc_t pool, uint32_t tab, int k16) {
+// (the lane's order computed HERE, cf. lane_now: the three table offsets derived from k16 at kernel entry were kept across all
+// record loops of rows_grow_kernel for this one leaf -- in scratch)
+__device__ __forceinline__ void rows_gather_shift(State<1> &s, const __amdgpu_buffer_rsrc_t pool, uint32_t tab) {
+    const int k16 = lane_now() & 15;
     const int32_t ia = pool_i32(pool, tab + 4u * (uint32_t)k16), ib = pool_i32(pool, tab + 4u * (uint32_t)(16 + k16)),
                   iz = pool_i32(pool, tab + 4u * (uint32_t)(32 + k16));
     const int row = lane_now() & 48;
@@ -631,7 +634,8 @@ __device__ __forceinline__ void rows_gather_shift(State<1> &s, const __amdgpu_bu
     s.Zi[0] = iz < 0 ? 0.0 : zi;
 }
 // table entry double [3][16] at byte offset `tab` (this lane's voxel): F_k *= c[0][k], conj(F_-k) *= c[1][k], Z_k *= c[2][k]
-__device__ __forceinline__ void rows_apply_D(State<1> &s, const __amdgpu_buffer_rsrc_t pool, uint32_t tab, int k16) {
+__device__ __forceinline__ void rows_apply_D(State<1> &s, const __amdgpu_buffer_rsrc_t pool, uint32_t tab) {
+    const int k16 = lane_now() & 15;     // (as in rows_gather_shift)
     const double dt = pool_f64(pool, tab + 8u * (uint32_t)k16), dm = pool_f64(pool, tab + 8u * (uint32_t)(16 + k16)),
                  dl = pool_f64(pool, tab + 8u * (uint32_t)(32 + k16));
     s.Ar[0] *= dt; s.Ai[0] *= dt;
@@ -647,11 +651,11 @@ __device__ __forceinline__ void rows_generic(State<R> &s, const Rec &r, double c
     const uint32_t f = r.flags;
     if constexpr (R == 1) {     // (K = 16 only: `tab` = this lane's entry of the record's table; own record each, no other stage)
         if (f & F_GS) {
-            rows_gather_shift(s, pool, tab, k16);
+            rows_gather_shift(s, pool, tab);
             return;
         }
         if (f & F_D) {
-            rows_apply_D(s, pool, tab, k16);
+            rows_apply_D(s, pool, tab);
             return;
         }
     }
@@ -859,6 +863,37 @@ __device__ __forceinline__ void rows_widen(const State<RA> &a, State<2 * RA> &b,
         b.Zr[j] = live ? zr0 : 0.0; b.Zi[j] = live ? zi0 : 0.0;
         b.Ar[RA + j] = live ? ar1 : 0.0; b.Ai[RA + j] = live ? ai1 : 0.0; b.Br[RA + j] = live ? br1 : 0.0; b.Bi[RA + j] = live ? bi1 : 0.0;
         b.Zr[RA + j] = live ? zr1 : 0.0; b.Zi[RA + j] = live ? zi1 : 0.0;
+    }
+}
+
+// ... and back, when the orders that still matter fit fewer slots (rows_grow_kernel: the tail of a train, where only the
+// orders that can reach a probe are computed).  State<2 R> (order 2 R * lane + j) -> State<R> (order R * lane + j): lane l takes
+// slot (l % 2) * R + j of old lane l / 2; the orders from 16 R on (old lanes 8 .. 15) are dropped.  One pull per slot, half of
+// what the widening costs: old lane m first hands its upper slot to lane m + 8 of the row (DPP row_ror:8 written to lanes
+// 8 .. 15 only, no crossbar), then even lanes pull from lane l / 2 and odd lanes from lane l / 2 + 8 in the same permutation
+__device__ __forceinline__ double row_pair(double lower, double upper) {
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(lower), __double2loint(upper), 0x128, 0xf, 0xc, false);   // row_ror:8, banks 2 and 3
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(lower), __double2hiint(upper), 0x128, 0xf, 0xc, false);
+    return __hiloint2double(hi, lo);
+}
+template <int R>
+__device__ __forceinline__ void rows_narrow(const State<2 * R> &a, State<R> &b, int k16) {
+    const int row = lane_now() & 48;
+    const int from = (row | (k16 >> 1) | ((k16 & 1) << 3)) << 2;
+#define EPGX_NARROW(X) b.X[j] = row_pull(row_pair(a.X[j], a.X[R + j]), from)
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        EPGX_NARROW(Ar); EPGX_NARROW(Ai); EPGX_NARROW(Br); EPGX_NARROW(Bi); EPGX_NARROW(Zr); EPGX_NARROW(Zi);
+    }
+#undef EPGX_NARROW
+}
+
+// the first slots of a state as a state of their own, and back (rows_grow_kernel keeps one set of registers for R = 1 and 2)
+template <int RA, int RB>
+__device__ __forceinline__ void rows_slots(const State<RA> &a, State<RB> &b) {
+#pragma unroll
+    for (int j = 0; j < (RA < RB ? RA : RB); ++j) {
+        b.Ar[j] = a.Ar[j]; b.Ai[j] = a.Ai[j]; b.Br[j] = a.Br[j]; b.Bi[j] = a.Bi[j]; b.Zr[j] = a.Zr[j]; b.Zi[j] = a.Zi[j];
     }
 }
 
