@@ -14,7 +14,7 @@ There is no CPU execution path: without libepgx.so and a GPU every computation r
 """
 from .core import *  # noqa: F401,F403
 from . import core as epg
-from . import operators, functions, statematrix, common, utils, exchange, magnettransfer
+from . import operators, functions, statematrix, common, utils, exchange, magnettransfer, rfpulse
 from ._lib import EpgxError
 
 

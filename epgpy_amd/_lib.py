@@ -79,6 +79,22 @@ ASM_SRC_DTYPE = np.dtype([("off", "<i8"), ("ncol", "<i4"), ("reserved", "<i4"), 
 ASSEMBLE_DTYPE = np.dtype([("dst_off", "<i8"), ("dst_space", "<i4"), ("ncoef", "<i4"), ("n_src", "<i4"), ("reserved", "<i4"),
                            ("src", ASM_SRC_DTYPE, (MAX_ASM_SRC,)), ("col_src", "u1", (MAX_ASM_COLS,)), ("col_idx", "u1", (MAX_ASM_COLS,))])
 assert ASM_SRC_DTYPE.itemsize == 80 and ASSEMBLE_DTYPE.itemsize == 376
+# device-collapsed tables (epgx_chain): steps in groups that are repeated; one chain = (destination, its steps)
+CHAIN_GROUP = 4
+CHAIN_STEP_DTYPE = np.dtype([("off", "<i8"), ("stride", "<i8"), ("kind", "<i4"), ("space", "<i4"), ("count", "<i4"), ("group", "<i4")])
+assert CHAIN_STEP_DTYPE.itemsize == 32
+
+
+class Chain(ctypes.Structure):
+    _fields_ = [("dst_off", ctypes.c_int64), ("dst_space", ctypes.c_int32), ("n_steps", ctypes.c_int32), ("steps", ctypes.c_void_p)]
+
+
+class PlanExt(ctypes.Structure):
+    """epgx_plan_ext: the lists epgx_plan_desc has no room for (epgx_plan_create_ext)"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_chain", ctypes.c_int32), ("chain", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(Chain) == 24 and ctypes.sizeof(PlanExt) == 16
 DOP_DTYPE = np.dtype([("space", "<i4", (MAX_VARS,)), ("reserved", "<i4"), ("coef_off", "<i8", (MAX_VARS,))])
 assert DOP_DTYPE.itemsize == 40
 
@@ -111,6 +127,7 @@ SYMBOLS = {
     "epgx_timer_start": (_i, [_p]),
     "epgx_timer_stop": (_i, [_p, ctypes.POINTER(ctypes.c_float)]),
     "epgx_plan_create": (_i, [_p, ctypes.POINTER(PlanDesc), c_void_pp]),
+    "epgx_plan_create_ext": (_i, [_p, ctypes.POINTER(PlanDesc), _p, c_void_pp]),
     "epgx_plan_destroy": (_i, [_p]),
     "epgx_state_create": (_i, [_p, _i64, _i32, c_void_pp]),
     "epgx_state_destroy": (_i, [_p]),
@@ -145,7 +162,7 @@ SYMBOLS = {
     "epgx_run_to_host": (_i, [_p, _p, _i32, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _i32]),
     "epgx_download_2d": (_i, [_p, _p, _i64, _p, _i64, _i64, _i64]),
 }
-ABI_VERSION = 8
+ABI_VERSION = 9
 COMM_ID_BYTES = 128
 
 _lock = threading.Lock()
@@ -536,10 +553,17 @@ def drop_comms():
         comm.destroy()
 
 
+def plan_ext(chain):
+    """(epgx_plan_ext, what it points into) from the chains of plan.Encoder.chain_list: [(dst_off, dst_space, steps)]"""
+    steps = [np.ascontiguousarray(st, dtype=CHAIN_STEP_DTYPE) for _, _, st in chain]
+    chains = (Chain * len(chain))(*[Chain(int(dst), int(space), len(st), st.ctypes.data) for (dst, space, _), st in zip(chain, steps)])
+    return PlanExt(ctypes.sizeof(PlanExt), len(chain), ctypes.addressof(chains)), (chains, steps)
+
+
 def plan_desc(ops, grid_shape, space_strides, coef, n_adc, dops=None, n_vars=0, deriv_flags=0,
-              fuse=None, n_coef_generated=0, assemble=None, fuse_partial=None):
+              fuse=None, n_coef_generated=0, assemble=None, fuse_partial=None, chain=None):
     """(epgx_plan_desc, the arrays it points into -- keep them alive as long as the struct is used) from the host arrays of
-    plan.Encoder.plan_arrays"""
+    plan.Encoder.plan_arrays (`chain` travels next to the struct: plan_ext)"""
     ops = np.ascontiguousarray(ops, dtype=OP_DTYPE)
     if dops is not None:
         dops = np.ascontiguousarray(dops, dtype=DOP_DTYPE)
@@ -568,13 +592,18 @@ def plan_desc(ops, grid_shape, space_strides, coef, n_adc, dops=None, n_vars=0, 
 class DevicePlan:
     """epgx_plan handle built from host arrays (see plan.py)"""
 
-    def __init__(self, ctx, ops, grid_shape, space_strides, coef, n_adc, **more):
+    def __init__(self, ctx, ops, grid_shape, space_strides, coef, n_adc, chain=None, **more):
         self.ctx = ctx
         desc, keep = plan_desc(ops, grid_shape, space_strides, coef, n_adc, **more)
         ops, grid = keep[0], keep[5]
         handle = ctypes.c_void_p()
-        check(ctx.lib.epgx_plan_create(ctx.handle, ctypes.byref(desc), ctypes.byref(handle)),
-              "epgx_plan_create")
+        if chain:
+            ext, keep_ext = plan_ext(chain)
+            check(ctx.lib.epgx_plan_create_ext(ctx.handle, ctypes.byref(desc), ctypes.addressof(ext), ctypes.byref(handle)),
+                  "epgx_plan_create_ext")
+        else:
+            check(ctx.lib.epgx_plan_create(ctx.handle, ctypes.byref(desc), ctypes.byref(handle)),
+                  "epgx_plan_create")
         self.handle = handle
         self.n_ops, self.n_adc = len(ops), int(n_adc)
         self.nvox = int(np.prod(grid))

@@ -37,6 +37,7 @@
 #include "epgx_xrun_kernels.hip.h"
 #include "epgx_deriv_kernels.hip.h"
 #include "epgx_launch.h"
+#include "epgx_chain.h"
 #include "epgx_launch_grow.h"
 #include "epgx_launch_tiled.h"
 
@@ -580,9 +581,24 @@ static int ncoef_expected(int opcode) {
     }
 }
 
-extern "C" int epgx_plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, epgx_plan **out) {
+static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_ext *ext, epgx_plan **out);
+
+extern "C" int epgx_plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, epgx_plan **out) { return plan_create(ctx, d, nullptr, out); }
+
+extern "C" int epgx_plan_create_ext(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_ext *ext, epgx_plan **out) {
+    if (out) *out = nullptr;
+    if (ext && ext->struct_size != sizeof(epgx_plan_ext))
+        return fail(EPGX_ERR_INVALID, "epgx_plan_create_ext: struct_size = %u, but epgx_plan_ext has %zu bytes in this library (ABI %d)",
+                    ext->struct_size, sizeof(epgx_plan_ext), EPGX_ABI_VERSION);
+    if (ext && (ext->n_chain < 0 || (ext->n_chain && !ext->chain)))
+        return fail(EPGX_ERR_INVALID, "epgx_plan_create_ext: n_chain = %d without a list", ext->n_chain);
+    return plan_create(ctx, d, ext, out);
+}
+
+static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_ext *ext, epgx_plan **out) {
     if (!ctx || !d || !out) return fail(EPGX_ERR_INVALID, "epgx_plan_create: NULL argument");
     *out = nullptr;
+    const int n_chain = ext ? ext->n_chain : 0;
     // (the first member: readable whatever the caller's idea of the struct is)
     if (d->struct_size != sizeof(epgx_plan_desc))
         return fail(EPGX_ERR_INVALID, "epgx_plan_create: struct_size = %u, but epgx_plan_desc has %zu bytes in this library (ABI %d): "
@@ -699,6 +715,48 @@ extern "C" int epgx_plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, epgx_pla
         const auto hit = assembled.find(off);
         return hit != assembled.end() && hit->second.ncoef == ncoef && hit->second.space == space;
     };
+    // device-collapsed tables (epgx_chain): EPGX_OP_MAT0 operators may refer to their destinations
+    std::map<int64_t, int32_t> chained;   // dst_off -> dst_space
+    for (int i = 0; i < n_chain; ++i) {
+        const epgx_chain &ch = ext->chain[i];
+        const char *why = nullptr;
+        auto space_ok = [&](int sp) { return sp >= -1 && sp < d->n_spaces; };
+        auto entries_of = [&](int sp) { return (sp < 0 ? 0 : space_extent[sp]) + 1; };
+        if (!space_ok(ch.dst_space)) why = "index space of the destination out of range";
+        if (!why && (ch.n_steps < 1 || !ch.steps)) why = "no steps";
+        if (!why && (ch.dst_off < d->n_coef || ch.dst_off + entries_of(ch.dst_space) * 14 > n_pool)) why = "destination outside the generated part of the pool";
+        int64_t reps = 1;   // repetitions of the group the current step belongs to
+        for (int k = 0, left = 0; !why && k < ch.n_steps; ++k, --left) {
+            const epgx_chain_step &st = ch.steps[k];
+            if (left == 0) {   // first step of a group
+                if (st.group < 1 || st.group > EPGX_CHAIN_GROUP || k + st.group > ch.n_steps || st.count < 1) why = "malformed group (1 .. EPGX_CHAIN_GROUP steps inside the list, count >= 1)";
+                left = st.group;
+                reps = st.count;
+            }
+            if (why) break;
+            const int nc = st.kind == EPGX_OP_T ? 8 : (st.kind == EPGX_OP_MAT ? 10 : (st.kind == EPGX_OP_MAT0 ? 14 : (st.kind == EPGX_OP_E ? 4 : 0)));
+            if (!nc) why = "unknown kind of source (EPGX_OP_T, EPGX_OP_MAT, EPGX_OP_MAT0 or EPGX_OP_E)";
+            if (!why && !space_ok(st.space)) why = "index space of a source out of range";
+            if (!why && (st.off < 0 || st.stride < 0)) why = "negative source offset or stride";
+            if (!why && !(is_assembled(st.off, nc, st.space) && (st.stride == 0 || reps == 1)) &&
+                st.off + (reps - 1) * st.stride + entries_of(st.space) * nc > d->n_coef)
+                why = "source neither inside the host part of the pool nor an assembled table";
+            for (int dd = 0; dd < d->ndim && !why; ++dd) {
+                const int64_t ds = ch.dst_space < 0 ? 0 : pl->strides[ch.dst_space][dd];
+                const int64_t ss = st.space < 0 ? 0 : pl->strides[st.space][dd];
+                if (pl->shape[dd] > 1 && ds == 0 && ss != 0) why = "a source varies along an axis the destination does not";
+            }
+        }
+        if (why) {
+            delete pl;
+            return fail(EPGX_ERR_INVALID, "epgx_plan_create: collapsed table %d: %s", i, why);
+        }
+        chained[ch.dst_off] = ch.dst_space;
+    }
+    auto is_chained = [&](const epgx_op &op) {
+        const auto hit = chained.find(op.coef_off);
+        return op.opcode == EPGX_OP_MAT0 && hit != chained.end() && hit->second == op.space;
+    };
     pl->ops.assign(d->ops, d->ops + d->n_ops);
     for (int i = 0; i < d->n_ops; ++i) {
         const epgx_op &op = pl->ops[i];
@@ -713,9 +771,9 @@ extern "C" int epgx_plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, epgx_pla
             if (!why && (op.coef_off < 0 || op.coef_off + (last + 1) * (int64_t)op.ncoef > n_pool))
                 why = "coefficient table exceeds the pool";
         }
-        if (!why && need && op.opcode != EPGX_OP_T0 && !is_assembled(op.coef_off, op.ncoef, op.space) &&
+        if (!why && need && op.opcode != EPGX_OP_T0 && !is_assembled(op.coef_off, op.ncoef, op.space) && !is_chained(op) &&
             op.coef_off + (op.space < 0 ? 1 : space_extent[op.space] + 1) * (int64_t)op.ncoef > d->n_coef)
-            why = "a table in the generated part of the pool needs a recipe (epgx_assemble, or epgx_fuse for EPGX_OP_T0)";
+            why = "a table in the generated part of the pool needs a recipe (epgx_assemble, epgx_chain for EPGX_OP_MAT0, or epgx_fuse for EPGX_OP_T0)";
         if (!why && op.opcode == EPGX_OP_S) {
             if (op.ia == 0) why = "shift by 0";
             if (op.ia >= EPGX_MAX_K || op.ia <= -EPGX_MAX_K) why = "shift exceeds EPGX_MAX_K";
@@ -1206,6 +1264,36 @@ extern "C" int epgx_plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, epgx_pla
         // so wait here only for the upload)
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         dev_free(ctx, d_recipes);
+    }
+    if (n_chain > 0 && e == hipSuccess) {   // collapsed tables: the steps of all chains in one upload, one launch per chain
+        std::vector<epgx_chain_step> steps;
+        for (int i = 0; i < n_chain; ++i) steps.insert(steps.end(), ext->chain[i].steps, ext->chain[i].steps + ext->chain[i].n_steps);
+        epgx_chain_step *d_steps = nullptr;
+        e = dev_alloc(ctx, (void **)&d_steps, sizeof(epgx_chain_step) * steps.size());
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(d_steps, steps.data(), sizeof(epgx_chain_step) * steps.size(), hipMemcpyHostToDevice, ctx->stream);
+        size_t at = 0;
+        for (int i = 0; i < n_chain && e == hipSuccess; ++i) {
+            const epgx_chain &ch = ext->chain[i];
+            ChainArgs ca;
+            memset(&ca, 0, sizeof(ca));
+            ca.pool = pl->d_coef;
+            ca.steps = d_steps + at;
+            ca.dst_off = ch.dst_off;
+            ca.n_entries = (ch.dst_space < 0 ? 0 : space_extent[ch.dst_space]) + 1;
+            ca.n_steps = ch.n_steps;
+            ca.ndim = d->ndim;
+            for (int dd = 0; dd < d->ndim; ++dd) {
+                ca.shape[dd] = pl->shape[dd];
+                ca.dst_str[dd] = ch.dst_space < 0 ? 0 : pl->strides[ch.dst_space][dd];
+                for (int sp = 0; sp < d->n_spaces; ++sp) ca.sp_str[sp][dd] = pl->strides[sp][dd];
+            }
+            e = epgx_launch_chain(ctx->stream, ca);
+            at += (size_t)ch.n_steps;
+        }
+        // (`steps` is a local: its upload must have left the host before it goes; the kernels have read d_steps by then too)
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        dev_free(ctx, d_steps);
     }
     for (int i = 0; i < d->n_fuse && e == hipSuccess; ++i) {
         const epgx_fuse &fu = d->fuse[i];

@@ -17,19 +17,22 @@ import os
 
 import numpy as np
 
-from . import common, operator as _operator, probe as _probe, statematrix, plan as _plan, shift as _shift, _lib
+from . import common, operator as _operator, probe as _probe, statematrix, plan as _plan, shift as _shift, collapse as _collapse, _lib
 
 LOGGER = common.LOGGER
 Probe = _probe.Probe
 
 
-def flatten_sequence(seq, flatten_multi=True):
-    """flat list of operators from nested lists / MultiOperators (functions.py:355-369)"""
+def flatten_sequence(seq, flatten_multi=True, keep_collapsible=False):
+    """flat list of operators from nested lists / MultiOperators (functions.py:355-369).  `keep_collapsible`: a MultiOperator
+    flagged `collapsible` whose members are all state-wise matrix / scalar operators stays whole (collapse.py)"""
     seq = [seq] if isinstance(seq, _operator.Operator) else seq
     flat = []
     for item in seq:
         if isinstance(item, list):
-            flat.extend(flatten_sequence(item))
+            flat.extend(flatten_sequence(item, keep_collapsible=keep_collapsible))
+        elif keep_collapsible and isinstance(item, _operator.MultiOperator) and item.collapsible and _collapse.eligible(item):
+            flat.append(item)
         elif flatten_multi and isinstance(item, _operator.MultiOperator):
             flat.extend(flatten_sequence(item.operators))
         elif isinstance(item, _operator.Operator):
@@ -87,7 +90,10 @@ def modify(sequence, modifier=None, *, expand=True, **params):
         newseq.append(done[op])
     LOGGER.info(f"Modify sequence: {shape}->{getshape(newseq)}")
     if isinstance(sequence, _operator.MultiOperator):
-        return _operator.MultiOperator(newseq, name=sequence.name)
+        modified = _operator.MultiOperator(newseq, name=sequence.name)
+        if sequence.collapsible:
+            modified.collapsible = True
+        return modified
     return newseq
 
 
@@ -181,12 +187,14 @@ def _fusion_pays(sequence, variables, nstate0, options, from_state=False):
 
 
 def compile_sequence(sequence, probes=None, *, shape=None, options=None, nstate0=0, kspace0=None,
-                     dense_start=False, variables=(), fuse=True):
+                     dense_start=False, variables=(), fuse=True, collapse=True):
     """flatten + encode; returns (encoder, records) with records = [(op, [(probe, slot)...])]
 
     variables: names of the (at most 3) order1 variables whose derivative states the plan
-    propagates; every probe then owns 1 + len(variables) consecutive signal rows from `slot`"""
-    sequence = flatten_sequence(sequence)
+    propagates; every probe then owns 1 + len(variables) consecutive signal rows from `slot`
+    collapse: operators flagged `collapsible` (RF pulses) become ONE record each, their table multiplied up on the device
+    (collapse.py); False: their members, one by one"""
+    sequence = flatten_sequence(sequence, keep_collapsible=collapse)
     grid = getshape(sequence)
     if shape is not None:
         grid = common.broadcast_shapes(grid, tuple(shape), append=True)
@@ -201,6 +209,7 @@ def compile_sequence(sequence, probes=None, *, shape=None, options=None, nstate0
     if not fuse:     # operator-by-operator arithmetic: no host-side E.T.E tables, no run-time fold in the library either
         enc.deriv_flags |= _lib.PLAN_NO_FOLD
     records, bounds = [], []
+    sequence = _collapse.resolve(sequence, grid, variables, FUSED_TABLE_BUDGET)      # Collapsed operators, or the members
     if fuse and kspace0 is None and _fusion_pays(sequence, variables, nstate0, options, dense_start):
         from . import fusion
         if fusion.fusable(sequence):                    # probes keep their place: records / bounds are unaffected
@@ -209,7 +218,7 @@ def compile_sequence(sequence, probes=None, *, shape=None, options=None, nstate0
             # coefficient pool (32-bit byte offsets: 4 GB; the four-voxels-per-wavefront kernels reach 2 GB).  Past the budget
             # the sequence stays as it is: the library then folds the relaxations into the rotations at run time (no
             # tables: include/epgx.h EPGX_PLAN_NO_FOLD), or runs them as stages
-            if fusion.generated_bytes(fused, len(variables)) <= FUSED_TABLE_BUDGET:
+            if fusion.generated_bytes(fused, len(variables)) + _collapse.generated_bytes(sequence) <= FUSED_TABLE_BUDGET:
                 sequence = fused
     for op in sequence:
         if isinstance(op, Probe):
@@ -228,7 +237,7 @@ def compile_sequence(sequence, probes=None, *, shape=None, options=None, nstate0
 
 def simulate(sequence, *, adc_time=False, init=None, squeeze=False, probe=None, callback=None,
              asarray=True, disp=False, device=None, ngpu=None, mode="auto", exact_partials=False, fuse=True, packed=True,
-             out="host", dtype=None, **options):
+             out="host", dtype=None, collapse=True, **options):
     """simulate a sequence; values are returned for every Probe/ADC (functions.py:50-170)
 
     Extra keywords (not in the reference): `device` (GPU index, or a list of indices); `ngpu=N`: cut the parameter grid
@@ -250,6 +259,10 @@ def simulate(sequence, *, adc_time=False, init=None, squeeze=False, probe=None, 
     variables, one GPU) leaves a `DeviceJacobian`: per ADC the probed state and its derivative rows, `.column(var)` a
     `DeviceSignal` on one of them.
 
+    `collapse`: shaped RF pulses (rfpulse.RFPulse, and what `modify` / `encode_phase` make of one) run as ONE operator each,
+    their members multiplied up on the device once per voxel (collapse.py; results differ from the member-by-member run by
+    rounding only); False: member by member.  Affects operators flagged `collapsible` only.
+
     `dtype`: np.complex64 returns single-precision records: the simulation itself stays float64 (complex128 states, as the
     reference), every record is rounded ONCE when it leaves the device (<= 6e-8 relative), and half the bytes cross PCIe --
     which is what a caller of a large grid waits for.  Default: complex128, the reference's.
@@ -259,7 +272,7 @@ def simulate(sequence, *, adc_time=False, init=None, squeeze=False, probe=None, 
     block returns to the pool when the last reference is dropped.  A caller that holds more than two large results at a
     time receives ordinary arrays for the further ones (filled by the library's copy threads at nearly the same rate).
     """
-    sequence = flatten_sequence(sequence)
+    sequence = flatten_sequence(sequence, keep_collapsible=collapse)
     nshift, shape = getnshift(sequence), getshape(sequence)
     if options.get("shape") is not None:      # (extension: a grid larger than the operators span -- the reference's simulate passes its own
         options = dict(options)               #  `shape` to the state matrix and would reject the keyword)
@@ -320,7 +333,7 @@ def simulate(sequence, *, adc_time=False, init=None, squeeze=False, probe=None, 
         values, times = _simulate_stepwise(sequence, probes, init, shape, callback, device, options, progress)
     else:
         values, times = _simulate_device(sequence, probes, init, mode, devices, options, exact_partials, fuse, packed, progress,
-                                         to_host=(out != "device"), dtype=dtype, shape=shape)
+                                         to_host=(out != "device"), dtype=dtype, shape=shape, collapse=collapse)
     if progress is not None:
         progress.close()
     return _pack_values(values, times, asarray=asarray, adc_time=adc_time, stacked_as_is=(out == "device"), dtype=dtype)
@@ -402,7 +415,7 @@ def _jacobian_variables(sequence, probes):
                 for var in getattr(pb or op, "_device_variables", list)():
                     if var not in wanted:
                         wanted.append(var)
-    known = {var for op in sequence for var in (getattr(op, "order1", None) or {})}
+    known = {var for op in flatten_sequence(sequence) for var in (getattr(op, "order1", None) or {})}
     return [var for var in wanted if var in known]
 
 
@@ -418,7 +431,7 @@ def slab_bounds(nvox, parts):
 
 def _probe_times(sequence):
     times, tic = [], 0
-    for op in sequence:
+    for op in flatten_sequence(sequence):
         tic = tic + op.duration
         if isinstance(op, Probe):
             times.append(tic)
@@ -611,7 +624,7 @@ def _jacobian_views(sequence, records, raw, chunk, grid):
 
 
 def _simulate_jacobian(sequence, probes, variables, init, devices, options, exact_partials=False, packed=True, fuse=True,
-                       to_host=True, dtype=np.complex128, shape=None):
+                       to_host=True, dtype=np.complex128, shape=None, collapse=True):
     """derivative passes: the state and up to 3 derivative states per launch (diff.py:119-139);
     the derivative states start from zero (an `init` state matrix carries no partials here).
     `to_host=False` (simulate(out="device")): one pass on one GPU, the rows stay in HBM -- per probe a DeviceJacobian"""
@@ -629,7 +642,7 @@ def _simulate_jacobian(sequence, probes, variables, init, devices, options, exac
                                            shape=init.shape if init is not None else shape,
                                            nstate0=init.nstate if init is not None else 0,
                                            kspace0=init._kspace if init is not None else None,
-                                           dense_start=init is not None, fuse=fuse)
+                                           dense_start=init is not None, fuse=fuse, collapse=collapse)
         enc.deriv_flags |= _lib.DERIV_THROUGH_PLAIN_OPS if exact_partials else 0
         K = enc.capacity(at_least=(init.nstate + 1) if init is not None else 0)
         state_in = None
@@ -722,12 +735,13 @@ def _finish_jacobian(sequence, records, base, partials):
 
 
 def _simulate_device(sequence, probes, init, mode, devices, options, exact_partials=False, fuse=True, packed=True,
-                     progress=None, to_host=True, dtype=np.complex128, shape=None):
+                     progress=None, to_host=True, dtype=np.complex128, shape=None, collapse=True):
     variables = _jacobian_variables(sequence, probes)
     if variables:
         if mode == "stream":
             raise NotImplementedError("derivatives run state-resident (no mode='stream')")
-        return _simulate_jacobian(sequence, probes, variables, init, devices, options, exact_partials, packed, fuse, to_host, dtype, shape)
+        return _simulate_jacobian(sequence, probes, variables, init, devices, options, exact_partials, packed, fuse, to_host, dtype, shape,
+                                  collapse)
     grid0 = init.shape if init is not None else shape
     options = dict(options)
     if init is not None:
@@ -735,7 +749,7 @@ def _simulate_device(sequence, probes, init, mode, devices, options, exact_parti
     enc, records, bounds = compile_sequence(sequence, probes, shape=grid0, options=options,
                                             nstate0=init.nstate if init is not None else 0,
                                             kspace0=init._kspace if init is not None else None,
-                                            dense_start=init is not None, fuse=fuse)
+                                            dense_start=init is not None, fuse=fuse, collapse=collapse)
     try:
         K = enc.capacity(at_least=(init.nstate + 1) if init is not None else 0, resident=(init is None and mode == "resident"))
     except NotImplementedError:
@@ -950,6 +964,7 @@ class _Stacked(tuple):
 def _simulate_stepwise(sequence, probes, init, shape, callback, device, options, progress=None):
     """reference-shaped loop (functions.py:173-192) over device launches; used for callbacks
     and for probes that need the full state on the host"""
+    sequence = flatten_sequence(sequence)
     if init is None:
         sm = statematrix.StateMatrix([0, 0, 1], shape=shape, device=device, **options)
     else:

@@ -112,7 +112,13 @@ class Operator:
 
 class MultiOperator(Operator):
     """several operators used as one (operator.py:118-203): its footprint, shift count and duration are those of its
-    members, which a plan sees flattened"""
+    members, which a plan sees flattened.
+
+    `collapsible`: the operator holds no shift and no probe and is used again and again (a sampled RF pulse): a plan may
+    keep it whole and have the device multiply its members up once per voxel (collapse.py).  Set by RFPulse, handed on by
+    `modify` / `encode_phase`; never set on anything else"""
+
+    collapsible = False
 
     def __init__(self, operators=None, *, name=None, duration=None):
         self.operators = []

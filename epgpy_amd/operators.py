@@ -10,3 +10,4 @@ from .shift import S
 from .diffusion import D
 from .diff import Jacobian, Hessian, PartialsPruner
 from .exchange import X
+from .rfpulse import RFPulse

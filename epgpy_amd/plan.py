@@ -53,6 +53,9 @@ class Encoder:
         self.fuse_partials = []    # partials of generated tables (epgx_fuse_partial), same tagged offsets
         # tables the library assembles on the device from per-axis columns (epgx_assemble)
         self.assembles = []
+        # tables the library multiplies up on the device from a run of state-wise operators (epgx_chain; collapse.py)
+        self.chains = []           # (tagged destination offset, destination space, steps)
+        self.table_runs = {}       # key -> ((space, offset, ncoef), stride): equal-shaped tables laid out one after the other
         # exchange (X): (compartment axis, N) shared by every X of the plan; lead shapes of the n-D shift vectors
         self.exchange = None
         self.shift_shapes = []
@@ -115,6 +118,48 @@ class Encoder:
         if key is not None:
             self.tables[key] = entry
         return entry
+
+    def table_run(self, tables, key):
+        """equal-shaped tables [*opshape, ncoef] stored one after the other (the rotations of a sampled RF pulse): returns
+        ((space, offset of the first, ncoef), doubles from one table to the next)"""
+        if key in self.table_runs:
+            return self.table_runs[key]
+        first = np.ascontiguousarray(tables[0], dtype=np.float64)
+        opshape, ncoef = first.shape[:-1], first.shape[-1]
+        space, strides = self._space_of(opshape)
+        borrowed = space >= 0 and strides != self._strides_of(opshape)
+        blocks = []
+        for table in tables:
+            table = np.ascontiguousarray(table, dtype=np.float64)
+            if table.shape != first.shape:
+                raise ValueError(f"table_run: shapes {table.shape} and {first.shape}")
+            if borrowed:     # (as in _table: materialise the broadcast over the extra axes of the borrowed space)
+                lead = tuple(opshape) + (1,) * (len(self.grid) - len(opshape))
+                target = tuple(g if st else 1 for g, st in zip(self.grid, strides))
+                table = np.ascontiguousarray(np.broadcast_to(table.reshape(lead + (ncoef,)), target + (ncoef,)))
+            blocks.append(table.reshape(-1))
+        run = ((space, self.pool_size, ncoef), blocks[0].size)
+        self.pool.extend(blocks)
+        self.pool_size += sum(block.size for block in blocks)
+        self.table_runs[key] = run
+        return run
+
+    def add_chain(self, dst, steps):
+        """dst <- the product of `steps` = [((space, offset, ncoef), stride, kind, count, group)] (collapse.Collapsed._entry)"""
+        self.chains.append((dst[1], dst[0], [(entry[1], stride, kind, entry[0], count, group)
+                                             for entry, stride, kind, count, group in steps]))
+
+    def chain_list(self):
+        """the epgx_chain list with final offsets (call after arrays()): [(dst_off, dst_space, steps as CHAIN_STEP_DTYPE)]"""
+        host_size = self.pool_size
+        fix = lambda off: off if off >= 0 else host_size + (-off - 1)
+        out = []
+        for dst, space, steps in self.chains:
+            arr = np.zeros(len(steps), dtype=_lib.CHAIN_STEP_DTYPE)
+            for i, (off, stride, kind, sp, count, group) in enumerate(steps):
+                arr[i] = (fix(off), stride, kind, sp, count, group)
+            out.append((fix(dst), space, arr))
+        return out
 
     def _generated(self, shape, ncoef, key, sources=()):
         """reserve a device-generated table [*shape, ncoef]; returns ((space, tagged offset, ncoef), new).
@@ -476,6 +521,8 @@ class Encoder:
                               fuse=self.fuse_array() if self.fuses else None, n_coef_generated=self.generated_size,
                               assemble=self.assemble_array() if self.assembles else None,
                               fuse_partial=self.fuse_partial_array() if self.fuse_partials else None))
+            if self.chains:      # (only plans with a collapsed operator carry the key: every other plan's arrays are as before)
+                cached[1]["chain"] = self.chain_list()
             self._plan_arrays = cached
         return cached[1]
 

@@ -30,6 +30,23 @@ def get_wavenumber(grad, duration, gamma=gamma_1H):
     return 2 * np.pi * gamma * np.asarray(grad) * 1e-3 * np.asarray(duration)
 
 
+def spatial_range(fov, nvalue=100):
+    """`nvalue` positions across a field of view of `fov` mm, centred (utils.py:175-183)"""
+    return fov * np.linspace(-0.5, 0.5, nvalue)
+
+
+def space_to_freq(grad, positions, *, gamma=gamma_1H):
+    """off-resonance frequencies (kHz) of positions (mm) under a gradient (mT/m) (utils.py:186-208)"""
+    if not np.isscalar(positions):
+        positions = np.asarray(positions)
+    return grad * 1e-6 * gamma * positions
+
+
+def freq_to_space(grad, frequencies, *, gamma=gamma_1H):
+    """the reverse of space_to_freq (utils.py:211-213)"""
+    return frequencies / grad / gamma * 1e6
+
+
 class Progress:
     """text progress display behind `simulate(disp=True)` (the reference wraps its operator loop in a progress
     bar, functions.py:175-176 / utils.py:219-236).  Here the unit of progress is a device launch: one per

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define EPGX_ABI_VERSION 8
+#define EPGX_ABI_VERSION 9
 #define EPGX_MAX_DIMS 8    /* grid dimensions                        */
 #define EPGX_MAX_SPACES 4  /* distinct operator broadcast patterns   */
 #define EPGX_WAVE 64       /* k-states per lane-register (wave64)    */
@@ -89,7 +89,8 @@ enum epgx_opcode {
                           index | 1<<30 = conjugate of the partner array -- shift.py:297-364 (shiftnd) */
     EPGX_OP_MAT0 = 11, /* EPGX_OP_MAT plus a constant term, 14 coef: the 10 of MAT, then Re/Im o0, o2, pad:
                           (o0, conj o0, o2) * density is added to (F_0, conj F_0, Z_0) -- the effect of
-                          `mat0 @ equilibrium` (opmatrix.py:199-205); produced by `E @ T` combinations  */
+                          `mat0 @ equilibrium` (opmatrix.py:199-205); produced by `E @ T` combinations, and by
+                          the library itself for a collapsed run of operators (epgx_chain)            */
     EPGX_OP_T0 = 12,   /* EPGX_OP_T plus a constant term, 12 coef: the 8 of T, then Re/Im o0, o2, pad.  What a
                           T between two precession-free relaxations collapses to: E2 T E1 keeps T's
                           symmetry and real m00 (the diagonal of E is real), and the recoveries become
@@ -200,6 +201,44 @@ typedef struct epgx_assemble {
     epgx_asm_src src[EPGX_MAX_ASM_SRC];
     uint8_t col_src[EPGX_MAX_ASM_COLS], col_idx[EPGX_MAX_ASM_COLS];
 } epgx_assemble; /* 376 bytes */
+
+/* A table that the library COLLAPSES on the device when the plan is created: the affine map of a run of state-wise operators
+ * that holds no shift and no probe -- a sampled RF pulse (rfpulse.py: N small rotations with relaxation / precession in
+ * between, 2 N to 3 N operators) is the same map (M, o) at every order of a voxel, so it is multiplied up ONCE per table entry
+ * and applied as one EPGX_OP_MAT0 record (chain_kernel, csrc/epgx_chain.hip: one lane per destination entry, the running map
+ * in registers, every step a left-multiplication (M, o) <- (A M, A o + a)).
+ * A step names a source table of the pool by the opcode whose layout it has: EPGX_OP_T (8 per entry), EPGX_OP_MAT (10),
+ * EPGX_OP_MAT0 (14) or EPGX_OP_E (4, e0 complex: precession allowed).  Steps come in GROUPS that are repeated: the `group`
+ * steps from a group's first step on are executed `count` times in order, repetition r reading the table at off + r * stride
+ * -- the N rotation tables of a pulse lie one after the other in the pool and share one relaxation table, so a whole pulse is
+ * one group {T: stride = one table, E: stride 0} with count = N.  `count` / `group` are read from the first step of a group
+ * (0 in the others); a group has at most EPGX_CHAIN_GROUP steps.
+ * Sources lie in the host part of the pool or are assembled tables (the list is executed after `assemble` and before `fuse`);
+ * the destination lies in the generated part, 14 per entry (EPGX_OP_MAT0 layout).  Every axis a source varies along must be
+ * one the destination varies along. */
+#define EPGX_CHAIN_GROUP 4
+typedef struct epgx_chain_step {
+    int64_t off;     /* first double of the source table (of repetition 0)                              */
+    int64_t stride;  /* doubles from the table of one repetition to that of the next (0: the same table) */
+    int32_t kind;    /* EPGX_OP_T, EPGX_OP_MAT, EPGX_OP_MAT0 or EPGX_OP_E                                */
+    int32_t space;   /* index space of the source (-1: one entry for all voxels)                         */
+    int32_t count;   /* first step of a group: repetitions (>= 1)                                        */
+    int32_t group;   /* first step of a group: steps in the group (1 .. EPGX_CHAIN_GROUP)                */
+} epgx_chain_step; /* 32 bytes */
+typedef struct epgx_chain {
+    int64_t dst_off;              /* doubles, in the generated part; 14 coefficients per entry          */
+    int32_t dst_space;            /* index space of the destination (-1: one entry)                     */
+    int32_t n_steps;
+    const epgx_chain_step *steps; /* [n_steps]                                                          */
+} epgx_chain; /* 24 bytes */
+
+/* What epgx_plan_desc cannot take up without changing its size: passed to epgx_plan_create_ext next to it.  Set
+ * struct_size = sizeof(epgx_plan_ext) and zero every member you do not use. */
+typedef struct epgx_plan_ext {
+    uint32_t struct_size;
+    int32_t n_chain;              /* device-collapsed tables (executed after `assemble`, before `fuse`)  */
+    const epgx_chain *chain;      /* [n_chain]                                                           */
+} epgx_plan_ext; /* 16 bytes */
 
 /* Host-side description of a compiled sequence ("plan").  The parameter grid has `ndim`
  * axes of extent grid_shape[d] (C order, last axis fastest); voxel v has coordinates
@@ -318,6 +357,10 @@ int epgx_timer_stop(epgx_ctx *ctx, float *elapsed_ms); /* synchronises */
 
 /* ---- plan ---------------------------------------------------------------------------- */
 int epgx_plan_create(epgx_ctx *ctx, const epgx_plan_desc *desc, epgx_plan **out);
+/* The same with the lists of an epgx_plan_ext next to the description; ext = NULL: none.  EPGX_ERR_INVALID with epgx_last_error() text for a chain whose
+ * offsets leave the pool, whose destination is not in the generated part, with an unknown kind, a malformed group, or a
+ * source that varies along an axis the destination does not. */
+int epgx_plan_create_ext(epgx_ctx *ctx, const epgx_plan_desc *desc, const epgx_plan_ext *ext, epgx_plan **out);
 int epgx_plan_destroy(epgx_plan *plan);
 
 /* ---- state (device-resident StateMatrix storage) -------------------------------------- */
