@@ -137,6 +137,7 @@ SYMBOLS = {
     "epgx_state_broadcast": (_i, [_p, _p, _p]),
     "epgx_state_info": (_i, [_p, ctypes.POINTER(_i64), ctypes.POINTER(_i32), c_void_pp, c_void_pp]),
     "epgx_state_axpy": (_i, [_p, _p, ctypes.c_double, _i32]),
+    "epgx_state_dft": (_i, [_p, _p, _i64, _i64, _i32, _p, _p, _i32, _p, _i64, _d, _d, _p]),
     "epgx_run": (_i, [_p, _p, _i32, _i32, _i64, _i64, _p, _p, _i32, _p, _i64, _i64]),
     "epgx_kernel_for": (_i, [_p, _p, _i32, _i32, _i32, _p, _p, ctypes.c_char_p, _i64]),
     "epgx_run_tiled": (_i, [_p, _p, _i64, _i64, _p, _i32, _p, _i64, _i64, _i64]),
@@ -162,7 +163,7 @@ SYMBOLS = {
     "epgx_run_to_host": (_i, [_p, _p, _i32, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _i32]),
     "epgx_download_2d": (_i, [_p, _p, _i64, _p, _i64, _i64, _i64]),
 }
-ABI_VERSION = 9
+ABI_VERSION = 10
 COMM_ID_BYTES = 128
 
 _lock = threading.Lock()
@@ -719,6 +720,20 @@ def signal_reduce(ctx, signal_ptr, signal_ld, row0, row_step, n_rows, grid, redu
     res = out.download(np.complex128, (int(n_rows),) + kept)
     out.free()
     return res
+
+
+def state_dft(ctx, state, vox0, nvox, k, w, pos, phase, out_ptr):
+    """epgx_state_dft: out[v][p] = phase * sum over the rows of w F exp(i k . x_p) for voxels [vox0, vox0 + nvox) of `state`
+    (k [nrow, d] and w [nrow] of the STORED orders, pos [npos, d]) into the device memory at `out_ptr` ([nvox][npos] complex128)"""
+    k = np.ascontiguousarray(k, dtype=np.float64)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    pos = np.ascontiguousarray(pos, dtype=np.float64)
+    if k.ndim != 2 or pos.ndim != 2 or k.shape[1] != pos.shape[1] or w.shape != k.shape[:1]:
+        raise ValueError(f"state_dft: k {k.shape}, w {w.shape}, pos {pos.shape} do not fit together")
+    phase = complex(phase)
+    check(ctx.lib.epgx_state_dft(ctx.handle, state.handle, int(vox0), int(nvox), k.shape[0], k.ctypes.data, w.ctypes.data,
+                                 k.shape[1], pos.ctypes.data, pos.shape[0], phase.real, phase.imag, ctypes.c_void_p(out_ptr)),
+          "epgx_state_dft")
 
 
 def kernel_for(ctx, plan, K, op_begin=0, op_end=None, state_in=None, state_out=None):

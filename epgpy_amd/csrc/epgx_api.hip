@@ -38,6 +38,7 @@
 #include "epgx_deriv_kernels.hip.h"
 #include "epgx_launch.h"
 #include "epgx_chain.h"
+#include "epgx_dft.h"
 #include "epgx_launch_grow.h"
 #include "epgx_launch_tiled.h"
 
@@ -1635,6 +1636,62 @@ extern "C" int epgx_state_info(const epgx_state *st, int64_t *nvox, int32_t *K, 
     if (K) *K = st->K;
     if (data) *data = st->data;
     if (density) *density = st->dens;
+    return EPGX_OK;
+}
+
+// ------------------------------------------------------------------------------ spatial read-out (epgx_dft.hip)
+extern "C" int epgx_state_dft(epgx_ctx *ctx, const epgx_state *st, int64_t vox0, int64_t nvox, int32_t nrow, const double *k,
+                              const double *w, int32_t d, const double *pos, int64_t npos, double phase_re, double phase_im,
+                              void *out) {
+    if (!ctx || !st || !k || !w || !pos || !out) return fail(EPGX_ERR_INVALID, "epgx_state_dft: NULL argument");
+    if (st->ctx != ctx) return fail(EPGX_ERR_INVALID, "epgx_state_dft: the state belongs to another context");
+    if (nrow < 1 || nrow > st->K)
+        return fail(EPGX_ERR_INVALID, "epgx_state_dft: nrow = %d not in [1, K = %d]", nrow, st->K);
+    if (d < 1 || d > 3) return fail(EPGX_ERR_INVALID, "epgx_state_dft: d = %d position columns, expected 1 .. 3", d);
+    if (vox0 < 0 || nvox < 1 || vox0 + nvox > st->nvox)
+        return fail(EPGX_ERR_INVALID, "epgx_state_dft: voxels [%lld, %lld) outside the state (%lld voxels)", (long long)vox0,
+                    (long long)(vox0 + nvox), (long long)st->nvox);
+    if (npos < 1) return fail(EPGX_ERR_INVALID, "epgx_state_dft: npos = %lld < 1", (long long)npos);
+    const int64_t tiles_v = (nvox + DFT_TV - 1) / DFT_TV, tiles_p = (npos + DFT_TP - 1) / DFT_TP;
+    const size_t table_bytes = sizeof(double) * 4 * (size_t)dft_table_voxels(nvox) * (size_t)nrow;
+    if (tiles_v > 65535 || tiles_p > 0x7fffffff || table_bytes > ((size_t)8 << 30))
+        return fail(EPGX_ERR_UNSUPPORTED, "epgx_state_dft: %lld voxels x %d orders x %lld positions in one call: hand over a smaller "
+                    "voxel range (the coefficient table is limited to 8 GiB, the launch to %d voxels)", (long long)nvox, nrow,
+                    (long long)npos, 65535 * DFT_TV);
+    if (int rc = set_device(ctx)) return rc;
+    // k and pos padded to three columns (zero columns add nothing to the phase), w: one upload behind the table
+    std::vector<double> host((size_t)4 * nrow + (size_t)3 * npos, 0.0);
+    double *hk = host.data(), *hw = hk + (size_t)3 * nrow, *hp = hw + nrow;
+    for (int32_t j = 0; j < nrow; ++j) {
+        for (int c = 0; c < d; ++c) hk[3 * j + c] = k[(size_t)j * d + c];
+        hw[j] = w[j];
+    }
+    for (int64_t p = 0; p < npos; ++p)
+        for (int c = 0; c < d; ++c) hp[3 * p + c] = pos[p * d + c];
+    char *block = nullptr;
+    HIP_TRY(dev_alloc(ctx, (void **)&block, table_bytes + sizeof(double) * host.size()));
+    double *d_small = (double *)(block + table_bytes);
+    hipError_t e = hipMemcpyAsync(d_small, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (`host` is pageable and dies with this call)
+    if (e == hipSuccess) {
+        DftArgs a;
+        a.state = st->data;
+        a.K = st->K;
+        a.nrow = nrow;
+        a.vox0 = vox0;
+        a.nvox = nvox;
+        a.k = d_small;
+        a.w = d_small + (size_t)3 * nrow;
+        a.pos = d_small + (size_t)4 * nrow;
+        a.npos = npos;
+        a.table = (double *)block;
+        a.phase_re = phase_re;
+        a.phase_im = phase_im;
+        a.out = (d2 *)out;
+        e = epgx_launch_dft(ctx->stream, a);
+    }
+    dev_free(ctx, block);   // (recycled in stream order, behind the kernels that read it)
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_state_dft: %s", hipGetErrorString(e));
     return EPGX_OK;
 }
 

@@ -19,6 +19,8 @@ import numpy as np
 
 from . import common, operator as _operator, probe as _probe, statematrix, plan as _plan, shift as _shift, collapse as _collapse, _lib
 
+from .utils import dft, imaging  # noqa: F401,E402  (re-exported as the reference does, functions.py:8)
+
 LOGGER = common.LOGGER
 Probe = _probe.Probe
 

@@ -257,3 +257,22 @@ class PD(Operator):
         if self.reset and enc.kspace is not None:   # states <- new equilibrium, coordinates kept
             ks = enc.kspace
             enc.kspace = ks._like([False] * ks.nrow, [i == ks.centre for i in range(ks.nrow)])
+
+
+class System(Operator):
+    """set properties of the system the state matrix lives in (operator.py:348-361): `kvalue` / `tvalue` become attributes
+    of the state matrix, everything else (coords, weights, modulation, ...) goes into `sm.system`, where the imaging probes
+    look for what their constructor was not given.  Host bookkeeping without a device encoding: a sequence that holds one
+    runs operator by operator (`_on_host`)."""
+
+    def __init__(self, name=None, **properties):
+        super().__init__(name=name)
+        self.properties = properties
+
+    def _apply(self, sm):
+        for prop, value in self.properties.items():
+            if prop in ("kvalue", "tvalue"):
+                setattr(sm, prop, value)
+            else:
+                sm.system.set(prop, value)
+        return sm

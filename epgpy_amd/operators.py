@@ -1,7 +1,7 @@
 """operator namespace (mirrors epgpy/operators.py:1-25, hot-path subset)"""
 from .operator import (Operator, MultiOperator, EmptyOperator, Spoiler, Wait, Offset, Reset, PD,
-                       NULL, SPOILER, RESET)
-from .probe import Probe, Adc, ADC
+                       NULL, SPOILER, RESET, System)
+from .probe import Probe, Adc, ADC, DFT, Imaging
 from .opmatrix import MatrixOp
 from .opscalar import ScalarOp
 from .evolution import E, P, R

@@ -93,6 +93,36 @@ def _equilibrium_density(equilibrium):
     return equilibrium[..., neq, 2].real
 
 
+class SystemArrays:
+    """named arrays that describe the system around a state matrix -- positions, weights, modulation (the `system`
+    collection of statematrix.py:78-80, filled by operator.System).  Arrays are kept as they were given."""
+
+    def __init__(self, arrays=None):
+        self._arrays = dict(arrays or {})
+
+    def set(self, name, value):
+        self._arrays[name] = np.array(value)
+
+    def get(self, name, default=None, broadcast=False):
+        """the array `name`, or `default`; `broadcast` is accepted for the reference's signature (nothing is expanded here)"""
+        return self._arrays.get(name, default)
+
+    def __getitem__(self, name):
+        return self._arrays[name]
+
+    def __contains__(self, name):
+        return name in self._arrays
+
+    def __iter__(self):
+        return iter(self._arrays)
+
+    def __len__(self):
+        return len(self._arrays)
+
+    def copy(self):
+        return SystemArrays(self._arrays)
+
+
 class StateMatrix:
     """n-dimensional phase-state matrix stored on the GPU (statematrix.py:9-80)"""
 
@@ -135,6 +165,7 @@ class StateMatrix:
             self._set_equilibrium(_to_grid(general, grid, 2))
         self.kvalue, self.tvalue = kvalue, tvalue
         self.options = options
+        self.system = SystemArrays()
         # k-space coordinate set once an n-D shift has been applied (kspace.py), or handed over with the states
         self._kspace = None if coords is None else self._planned_coords(coords)
 
@@ -157,6 +188,7 @@ class StateMatrix:
         sm.options, sm.kvalue, sm.tvalue = dict(options or {}), kvalue, tvalue
         sm._kspace = None
         sm._eq = sm._eq_host = None
+        sm.system = SystemArrays()
         return sm
 
     def _set_equilibrium(self, eq):
@@ -402,6 +434,7 @@ class StateMatrix:
         new = StateMatrix._wrap(self._ctx, self._state.copy(), self._shape, self._nstate,
                                 {**self.options, **kwargs}, kvalue, tvalue)
         new._kspace = self._kspace
+        new.system = self.system.copy()
         if self._eq is not None and equilibrium is None:
             new._eq, new._eq_host = self._eq.copy(), self._eq_host.copy()
         if equilibrium is not None and not _is_plain_equilibrium(_format_states(equilibrium, check=True)):

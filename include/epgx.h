@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define EPGX_ABI_VERSION 9
+#define EPGX_ABI_VERSION 10
 #define EPGX_MAX_DIMS 8    /* grid dimensions                        */
 #define EPGX_MAX_SPACES 4  /* distinct operator broadcast patterns   */
 #define EPGX_WAVE 64       /* k-states per lane-register (wave64)    */
@@ -376,6 +376,29 @@ int epgx_state_info(const epgx_state *st, int64_t *nvox, int32_t *K, void **data
  * a derivative state (no equilibrium term: DiffOperator.derive1, epgpy/diff.py:103-109). Replaces
  * StateMatrix.__iadd__ in diff.accumulate (epgpy/diff.py:553-563) for operator-by-operator use. */
 int epgx_state_axpy(epgx_state *dst, const epgx_state *src, double alpha, int32_t zero_density);
+
+/* Spatial read-out of a device-resident state matrix: what DFT / Imaging compute on downloaded arrays in the reference
+ * (epgpy/probe.py:168-219 -> epgpy/utils.py:12-115 `imaging` / `_dft`),
+ *   out[v][p] = phase * sum_r  w_r F_r(v) exp(i k_r . x_p),        v = vox0 .. vox0 + nvox - 1,  p = 0 .. npos - 1
+ * r over the 2 nrow - 1 rows of the state matrix.  Row -k is the mirror image of stored order j (comp 1 = conj(F_-k)), carries
+ * the wavenumber -k_j and the same voxel factor, so the sum is taken over the nrow STORED orders (csrc/epgx_dft.hip).
+ *   nrow : stored orders used, nstate + 1 (1 .. K of the state); order 0 is k = 0
+ *   k    : host [nrow][d], wavenumber of stored order j in rad/m (StateMatrix.k: integer coordinate x kvalue), the columns
+ *          that enter the phase
+ *   w    : host [nrow], voxel factor of stored order j: 1 for a point, prod_d sinc(k_d size_d / 2 pi) for a box (over ALL
+ *          wavenumber columns), 0 for an order the caller drops (utils.py:55-57 `kmask`)
+ *   pos  : host [npos][d], d = 1 .. 3
+ *   phase_re / phase_im : exp(i phase), multiplies every output (utils.py:78-79); (1, 0) for none
+ *   out  : DEVICE, [nvox][npos] complex128.  Weights and sums over axes of this record: epgx_signal_reduce with ONE row whose
+ *          grid is (*grid, *positions).
+ * Coordinates that differ between voxel classes (a vectorised shift; a class is a contiguous voxel range): one call per class.
+ * sin / cos are evaluated in full double precision.  Stream-ordered behind the operators that produced the state; the call
+ * uploads k, w and pos (and synchronises for that) before it launches.
+ * Errors (nothing is launched): EPGX_ERR_INVALID for a NULL argument, a state of another context, nrow outside [1, K], d outside
+ * [1, 3], a voxel range outside the state, npos < 1; EPGX_ERR_UNSUPPORTED when the coefficient table of the call (32 bytes per
+ * voxel and order) would exceed 8 GiB or the range 65535 x 256 voxels: hand over voxel slabs. */
+int epgx_state_dft(epgx_ctx *ctx, const epgx_state *st, int64_t vox0, int64_t nvox, int32_t nrow, const double *k,
+                   const double *w, int32_t d, const double *pos, int64_t npos, double phase_re, double phase_im, void *out);
 
 /* ---- run ------------------------------------------------------------------------------ */
 /* Apply operators [op_begin, op_end) of `plan` to voxels [vox0, vox0+nvox) of the plan's grid.
