@@ -144,6 +144,7 @@ SYMBOLS = {
     "epgx_tiled_info": (_i, [_p, _p, _i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i64),
                              ctypes.POINTER(_i32), ctypes.c_char_p, _i64]),
     "epgx_signal_reduce": (_i, [_p, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _i64, _i64]),
+    "epgx_signal_crlb": (_i, [_p, _p, _i64, _i64, _i32, _i32, _i32, _p, _i64, _i64, _p, _d, _i32, _p]),
     "epgx_simulate_f64": (_i, [_p, ctypes.POINTER(PlanDesc), _i32, _p, _p, _p, _p, _i32]),
     "epgx_simulate_sharded_f64": (_i, [ctypes.POINTER(PlanDesc), _i32, _i32, _p, _p, _i32]),
     "epgx_comm_unique_id": (_i, [_p]),
@@ -163,7 +164,7 @@ SYMBOLS = {
     "epgx_run_to_host": (_i, [_p, _p, _i32, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _i32]),
     "epgx_download_2d": (_i, [_p, _p, _i64, _p, _i64, _i64, _i64]),
 }
-ABI_VERSION = 10
+ABI_VERSION = 11
 COMM_ID_BYTES = 128
 
 _lock = threading.Lock()
@@ -720,6 +721,30 @@ def signal_reduce(ctx, signal_ptr, signal_ld, row0, row_step, n_rows, grid, redu
     res = out.download(np.complex128, (int(n_rows),) + kept)
     out.free()
     return res
+
+
+CRLB_SPLIT, CRLB_LOG10 = 1, 2      # enum epgx_crlb_flags
+
+
+def signal_crlb(ctx, signal_ptr, record_stride, row_stride, nrow, nrec, rows, vox0, nvox, weights=None, sigma2=1.0,
+                split=False, log=False):
+    """epgx_signal_crlb: Cramer-Rao bounds of voxels [vox0, vox0 + nvox) from Jacobian records in device memory (column c of
+    record r at signal_ptr + 16 * (r * record_stride + rows[c] * row_stride + voxel)).  Returns float64 [nvox], or with
+    `split` [len(rows), nvox]; only that crosses PCIe"""
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    if rows.ndim != 1 or (w is not None and w.shape != rows.shape):
+        raise ValueError(f"signal_crlb: rows {rows.shape} and weights {None if w is None else w.shape} do not fit together")
+    shape = (len(rows), int(nvox)) if split else (int(nvox),)
+    out = DeviceBuffer(ctx, 8 * max(int(np.prod(shape)), 1), itemsize=8)
+    try:
+        check(ctx.lib.epgx_signal_crlb(ctx.handle, ctypes.c_void_p(signal_ptr) if signal_ptr else None, int(record_stride),
+                                       int(row_stride), int(nrow), int(nrec), len(rows), rows.ctypes.data, int(vox0), int(nvox),
+                                       w.ctypes.data if w is not None else None, float(sigma2),
+                                       (CRLB_SPLIT if split else 0) | (CRLB_LOG10 if log else 0), out.ptr), "epgx_signal_crlb")
+        return out.download(np.float64, shape)
+    finally:
+        out.free()         # (back to the context's pool)
 
 
 def state_dft(ctx, state, vox0, nvox, k, w, pos, phase, out_ptr):

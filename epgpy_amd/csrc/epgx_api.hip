@@ -14,6 +14,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <deque>
 #include <functional>
@@ -39,6 +40,7 @@
 #include "epgx_launch.h"
 #include "epgx_chain.h"
 #include "epgx_dft.h"
+#include "epgx_stats.h"
 #include "epgx_launch_grow.h"
 #include "epgx_launch_tiled.h"
 
@@ -1497,6 +1499,56 @@ extern "C" int epgx_signal_reduce(epgx_ctx *ctx, const void *signal, int64_t sig
     else
         hipLaunchKernelGGL(reduce_thread_kernel, dim3((unsigned)((a.n_out + 255) / 256), (unsigned)n_rows), dim3(256), 0, ctx->stream, a);
     HIP_TRY(hipGetLastError());
+    return EPGX_OK;
+}
+
+// ------------------------------------------------------------------------------ Cramer-Rao bounds (epgx_stats.hip)
+extern "C" int epgx_signal_crlb(epgx_ctx *ctx, const void *signal, int64_t record_stride, int64_t row_stride, int32_t nrow,
+                                int32_t nrec, int32_t nparam, const int32_t *rows, int64_t vox0, int64_t nvox,
+                                const double *weights, double sigma2, int32_t flags, void *out) {
+    if (!ctx || !signal || !rows || !out) return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: NULL argument");
+    if (((uintptr_t)signal & 15) || ((uintptr_t)out & 7))
+        return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: signal must be aligned to 16 bytes, out to 8");
+    if (nparam < 1 || nparam > CRLB_MAX_P)
+        return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: nparam = %d not in [1, %d]", nparam, CRLB_MAX_P);
+    if (nrec < 1 || nrow < 1) return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: nrec = %d, nrow = %d: both must be >= 1", nrec, nrow);
+    if (vox0 < 0 || nvox < 0 || row_stride < 1 || nvox > row_stride - vox0)
+        return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: voxels [%lld, %lld + %lld) outside a row of %lld", (long long)vox0,
+                    (long long)vox0, (long long)nvox, (long long)row_stride);
+    if (record_stride / nrow < row_stride)
+        return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: record_stride = %lld holds fewer than nrow = %d rows of %lld",
+                    (long long)record_stride, nrow, (long long)row_stride);
+    int64_t span, last;      // elements from `signal` to the end of the last record: must be expressible (the kernel's pointer arithmetic)
+    if (__builtin_mul_overflow((int64_t)(nrec - 1), record_stride, &span) || __builtin_mul_overflow((int64_t)nrow, row_stride, &last) ||
+        __builtin_add_overflow(span, last, &span) || span > INT64_MAX / 16)
+        return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: nrec = %d records of record_stride = %lld elements overflow the address range",
+                    nrec, (long long)record_stride);
+    if (flags & ~(EPGX_CRLB_SPLIT | EPGX_CRLB_LOG10)) return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: unknown flags 0x%x", flags);
+    if (!(sigma2 > 0.0) || !std::isfinite(sigma2)) return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: sigma2 = %g is not a positive finite number", sigma2);
+    CrlbArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int c = 0; c < nparam; ++c) {
+        if (rows[c] < 0 || rows[c] >= nrow)
+            return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: rows[%d] = %d not in [0, nrow = %d)", c, rows[c], nrow);
+        if (weights && !std::isfinite(weights[c])) return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: weights[%d] is not finite", c);
+        a.rows[c] = rows[c];
+        a.w[c] = weights ? weights[c] : 1.0;
+    }
+    if (nvox / 64 >= 0x7fffffff) return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: %lld voxels in one call", (long long)nvox);
+    if (nvox == 0) return EPGX_OK;
+    if (int rc = set_device(ctx)) return rc;
+    a.signal = (const d2 *)signal;
+    a.record_stride = record_stride;
+    a.row_stride = row_stride;
+    a.nrec = nrec;
+    a.vox0 = vox0;
+    a.nvox = nvox;
+    a.inv_sigma2 = 1.0 / sigma2;
+    a.flags = flags;
+    crlb_slices(nrec, &a.slices, &a.slice_len);
+    a.out = (double *)out;
+    hipError_t e = epgx_launch_crlb(ctx->stream, nparam, a);
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_signal_crlb: %s", hipGetErrorString(e));
     return EPGX_OK;
 }
 

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define EPGX_ABI_VERSION 10
+#define EPGX_ABI_VERSION 11
 #define EPGX_MAX_DIMS 8    /* grid dimensions                        */
 #define EPGX_MAX_SPACES 4  /* distinct operator broadcast patterns   */
 #define EPGX_WAVE 64       /* k-states per lane-register (wave64)    */
@@ -494,6 +494,31 @@ int epgx_signal_reduce(epgx_ctx *ctx, const void *signal, int64_t signal_ld, int
                        int32_t row_step, int32_t n_rows, int32_t ndim, const int64_t *grid_shape,
                        const uint8_t *reduce_axis, const void *weights, const int64_t *weight_strides,
                        void *out, int64_t vox0, int64_t nvox);
+
+/* Cramer-Rao lower bounds from a Jacobian that stays on the device: what stats.crlb / stats.crlb_split compute on a downloaded
+ * array in the reference (epgpy/stats.py:6-54), per voxel v = vox0 .. vox0 + nvox - 1,
+ *   I(v) = 1 / sigma2 * Re( J(v)^H J(v) ),   lb(v) = I(v)^-1,
+ *   out[v - vox0]             = sum_p W_p lb_pp(v)                  (flags without EPGX_CRLB_SPLIT)
+ *   out[p * nvox + v - vox0]  = W_p lb_pp(v),  p = 0 .. nparam - 1    (EPGX_CRLB_SPLIT)
+ * and log10 of these with EPGX_CRLB_LOG10.  J(v) is [nrec][nparam]: entry (r, c) is the complex128 value
+ *   signal[r * record_stride + rows[c] * row_stride + v]
+ * (strides in elements of 16 bytes) -- the layout of a Jacobian probe's records, [record][probe][row][voxel]: record_stride =
+ * nprobe * nrow * nvox of the grid, row_stride = nvox of the grid, `signal` at row 0 of the probe in record 0.
+ *   nrow    : rows of one probe in a record (bounds rows[c]); record_stride >= nrow * row_stride
+ *   rows    : host [nparam], the row of every column, 0 .. nrow - 1, in any order, any subset; nparam = 1 .. 4
+ *   weights : host [nparam] or NULL (= 1);  sigma2 > 0
+ *   flags   : EPGX_CRLB_SPLIT | EPGX_CRLB_LOG10
+ *   out     : DEVICE, float64 [nvox], with EPGX_CRLB_SPLIT [nparam][nvox]
+ * A voxel whose information matrix is singular -- a Cholesky pivot <= 0 or not finite -- gets NaN in every output (the
+ * reference: cond(I) > 1e30); never an error.  The bits of a voxel's result depend on its own records, nrec and the
+ * arguments, not on nvox, vox0 or other voxels (csrc/epgx_stats.hip).  Stream-ordered; nothing is uploaded or synchronised.
+ * Errors (nothing is launched): EPGX_ERR_INVALID for a NULL or misaligned pointer, nparam outside [1, 4], nrec < 1, nrow < 1,
+ * a row outside [0, nrow), strides whose extent (nrec - 1) * record_stride + nrow * row_stride overflows or that overlap (row_stride < vox0 + nvox, record_stride < nrow * row_stride), vox0 < 0,
+ * nvox < 0, sigma2 that is not a positive finite number, a weight that is not finite, unknown flags.  nvox = 0: nothing to do. */
+enum epgx_crlb_flags { EPGX_CRLB_SPLIT = 1, EPGX_CRLB_LOG10 = 2 };
+int epgx_signal_crlb(epgx_ctx *ctx, const void *signal, int64_t record_stride, int64_t row_stride, int32_t nrow, int32_t nrec,
+                     int32_t nparam, const int32_t *rows, int64_t vox0, int64_t nvox, const double *weights, double sigma2,
+                     int32_t flags, void *out);
 
 /* Convenience for bindings that only have host arrays (what a ctypes/NumPy binding inside
  * the reference would call once per simulate()): builds the plan, runs the whole sequence
