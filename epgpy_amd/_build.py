@@ -30,7 +30,8 @@ UNITS = [("epgx_api.o", "epgx_api.hip", [])] + \
         [(f"epgx_pdfold_v{v}_k{k}.o", "epgx_pdfold.hip", [f"-DEPGX_V={v}", f"-DEPGX_KP={k}"]) for v in (3, 2, 1) for k in (32, 16)] + \
         [(f"epgx_xrun_nc{nc}.o", "epgx_xrun.hip", [f"-DEPGX_NC={nc}"]) for nc in (2, 3, 4)] + \
         [("epgx_tiled.o", "epgx_tiled.hip", []), ("epgx_chain.o", "epgx_chain.hip", []),
-         ("epgx_dft.o", "epgx_dft.hip", []), ("epgx_stats.o", "epgx_stats.hip", [])]
+         ("epgx_dft.o", "epgx_dft.hip", []), ("epgx_stats.o", "epgx_stats.hip", []),
+         ("epgx_merge.o", "epgx_merge.hip", [])]
 ARCH = "gfx950"
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
          # every branch of run_kernel is wave-uniform (scalar compares on record flags); without this

@@ -138,6 +138,8 @@ SYMBOLS = {
     "epgx_state_info": (_i, [_p, ctypes.POINTER(_i64), ctypes.POINTER(_i32), c_void_pp, c_void_pp]),
     "epgx_state_axpy": (_i, [_p, _p, ctypes.c_double, _i32]),
     "epgx_state_dft": (_i, [_p, _p, _i64, _i64, _i32, _p, _p, _i32, _p, _i64, _d, _d, _p]),
+    "epgx_state_row_stats": (_i, [_p, _p, _i32, _p, _p]),
+    "epgx_state_merge": (_i, [_p, _p, _p, _i32, _p, _p]),
     "epgx_run": (_i, [_p, _p, _i32, _i32, _i64, _i64, _p, _p, _i32, _p, _i64, _i64]),
     "epgx_kernel_for": (_i, [_p, _p, _i32, _i32, _i32, _p, _p, ctypes.c_char_p, _i64]),
     "epgx_run_tiled": (_i, [_p, _p, _i64, _i64, _p, _i32, _p, _i64, _i64, _i64]),
@@ -759,6 +761,35 @@ def state_dft(ctx, state, vox0, nvox, k, w, pos, phase, out_ptr):
     check(ctx.lib.epgx_state_dft(ctx.handle, state.handle, int(vox0), int(nvox), k.shape[0], k.ctypes.data, w.ctypes.data,
                                  k.shape[1], pos.ctypes.data, pos.shape[0], phase.real, phase.imag, ctypes.c_void_p(out_ptr)),
           "epgx_state_dft")
+
+
+ERR_UNSUPPORTED = -4                                      # enum epgx_status
+MERGE_MAX_ROWS = 1024                                     # stored orders of an epgx_state_merge destination
+MERGE_COMP_SHIFT = 16                                     # a source entry: order | component << 16 | GS_CONJ
+
+
+def state_row_stats(ctx, state, nrow):
+    """epgx_state_row_stats: (sums [3, nrow], maxabs [nrow]) of the stored orders j < nrow over all voxels of `state` --
+    sum |A_j|, sum |B_j|, sum |Z_j| and the largest modulus; the same bits in every call"""
+    sums, maxabs = np.empty((3, int(nrow)), dtype=np.float64), np.empty(int(nrow), dtype=np.float64)
+    check(ctx.lib.epgx_state_row_stats(ctx.handle, state.handle, int(nrow), sums.ctypes.data, maxabs.ctypes.data),
+          "epgx_state_row_stats")
+    return sums, maxabs
+
+
+def state_merge(ctx, dst, src, nrow_dst, offsets, sources):
+    """epgx_state_merge: dst[v][c][j] = the sources listed for (c, j) of src[v], added in the order listed (offsets int32
+    [3, nrow_dst + 1] in CSR form over the one list `sources`).  More than MERGE_MAX_ROWS stored orders: NotImplementedError"""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+    sources = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+    if offsets.shape != (3, int(nrow_dst) + 1) or int(offsets[-1, -1]) != sources.size:
+        raise ValueError(f"state_merge: offsets {offsets.shape} / {sources.size} sources for nrow_dst={nrow_dst}")
+    keep = sources if sources.size else np.zeros(1, np.int32)
+    rc = ctx.lib.epgx_state_merge(ctx.handle, dst.handle, src.handle, int(nrow_dst), offsets.ctypes.data, keep.ctypes.data)
+    if rc == ERR_UNSUPPORTED:
+        raise NotImplementedError(f"{ctx.lib.epgx_last_error().decode(errors='replace')}: a coarser `kgrid` or a larger `prune` "
+                                  "tolerance keeps the state matrix under the limit")
+    check(rc, "epgx_state_merge")
 
 
 def kernel_for(ctx, plan, K, op_begin=0, op_end=None, state_in=None, state_out=None):

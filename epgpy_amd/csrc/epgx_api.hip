@@ -41,6 +41,7 @@
 #include "epgx_chain.h"
 #include "epgx_dft.h"
 #include "epgx_stats.h"
+#include "epgx_merge.h"
 #include "epgx_launch_grow.h"
 #include "epgx_launch_tiled.h"
 
@@ -1744,6 +1745,89 @@ extern "C" int epgx_state_dft(epgx_ctx *ctx, const epgx_state *st, int64_t vox0,
     }
     dev_free(ctx, block);   // (recycled in stream order, behind the kernels that read it)
     if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_state_dft: %s", hipGetErrorString(e));
+    return EPGX_OK;
+}
+
+// ------------------------------------------------------------------------------ float-wavenumber shift (epgx_merge.hip)
+extern "C" int epgx_state_row_stats(epgx_ctx *ctx, const epgx_state *st, int32_t nrow, double *sums, double *maxabs) {
+    if (!ctx || !st || !sums || !maxabs) return fail(EPGX_ERR_INVALID, "epgx_state_row_stats: NULL argument");
+    if (st->ctx != ctx) return fail(EPGX_ERR_INVALID, "epgx_state_row_stats: the state belongs to another context");
+    if (nrow < 1 || nrow > st->K) return fail(EPGX_ERR_INVALID, "epgx_state_row_stats: nrow = %d not in [1, K = %d]", nrow, st->K);
+    if (st->nvox < 1 || (st->K & 63)) return fail(EPGX_ERR_INVALID, "epgx_state_row_stats: a state of %lld voxels x %d orders", (long long)st->nvox, st->K);
+    if (int rc = set_device(ctx)) return rc;
+    RowStatsArgs a;
+    a.state = st->data;
+    a.K = st->K;
+    a.nvox = st->nvox;
+    a.slab = stats_slab(st->nvox);
+    a.nblocks = (int32_t)stats_blocks(st->nvox);
+    const size_t n_out = (size_t)4 * st->K;
+    double *block = nullptr;
+    HIP_TRY(dev_alloc(ctx, (void **)&block, sizeof(double) * n_out * ((size_t)a.nblocks + 1)));
+    a.partial = block + n_out;
+    a.out = block;
+    std::vector<double> host(n_out);
+    hipError_t e = epgx_launch_row_stats(ctx->stream, a);
+    if (e == hipSuccess) e = hipMemcpyAsync(host.data(), a.out, sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    dev_free(ctx, block);
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_state_row_stats: %s", hipGetErrorString(e));
+    for (int q = 0; q < 3; ++q) memcpy(sums + (size_t)q * nrow, host.data() + (size_t)q * st->K, sizeof(double) * (size_t)nrow);
+    memcpy(maxabs, host.data() + (size_t)3 * st->K, sizeof(double) * (size_t)nrow);
+    return EPGX_OK;
+}
+
+extern "C" int epgx_state_merge(epgx_ctx *ctx, epgx_state *dst, const epgx_state *src, int32_t nrow_dst, const int32_t *offsets,
+                                const int32_t *sources) {
+    if (!ctx || !dst || !src || !offsets || !sources) return fail(EPGX_ERR_INVALID, "epgx_state_merge: NULL argument");
+    if (nrow_dst > MERGE_MAX_ROWS)
+        return fail(EPGX_ERR_UNSUPPORTED, "epgx_state_merge: %d stored orders in the destination, at most %d are supported", nrow_dst,
+                    MERGE_MAX_ROWS);
+    if (dst->ctx != ctx || src->ctx != ctx) return fail(EPGX_ERR_INVALID, "epgx_state_merge: a state belongs to another context");
+    if (dst == src || dst->data == src->data) return fail(EPGX_ERR_INVALID, "epgx_state_merge: dst and src must differ");
+    if (dst->nvox != src->nvox)
+        return fail(EPGX_ERR_INVALID, "epgx_state_merge: nvox mismatch (%lld vs %lld)", (long long)dst->nvox, (long long)src->nvox);
+    if (nrow_dst < 1 || nrow_dst > dst->K)
+        return fail(EPGX_ERR_INVALID, "epgx_state_merge: nrow_dst = %d not in [1, K = %d] of the destination", nrow_dst, dst->K);
+    const size_t n_off = (size_t)3 * ((size_t)nrow_dst + 1);
+    if (offsets[0] != 0) return fail(EPGX_ERR_INVALID, "epgx_state_merge: offsets[0][0] = %d, expected 0", offsets[0]);
+    for (size_t i = 1; i < n_off; ++i) {
+        const bool seam = i % ((size_t)nrow_dst + 1) == 0;      // (the first entry of a component repeats the last of the one before)
+        if (seam ? offsets[i] != offsets[i - 1] : offsets[i] < offsets[i - 1])
+            return fail(EPGX_ERR_INVALID, "epgx_state_merge: offsets[%zu] = %d after %d: the table is not in CSR form", i, offsets[i],
+                        offsets[i - 1]);
+    }
+    const int32_t n_src = offsets[n_off - 1];
+    for (int32_t s = 0; s < n_src; ++s) {
+        const int32_t ent = sources[s], order = ent & MERGE_ORDER_MASK, comp = (ent >> MERGE_COMP_SHIFT) & 0x3fff;
+        if (ent < 0 || comp > 2 || order >= src->K)
+            return fail(EPGX_ERR_INVALID, "epgx_state_merge: sources[%d] = 0x%x: component %d, order %d (the source has %d orders)", s,
+                        ent, comp, order, src->K);
+    }
+    if (int rc = set_device(ctx)) return rc;
+    std::vector<int32_t> host(n_off + (size_t)std::max(n_src, 1));
+    memcpy(host.data(), offsets, sizeof(int32_t) * n_off);
+    if (n_src) memcpy(host.data() + n_off, sources, sizeof(int32_t) * (size_t)n_src);
+    int32_t *d_tab = nullptr;
+    HIP_TRY(dev_alloc(ctx, (void **)&d_tab, sizeof(int32_t) * host.size()));
+    hipError_t e = hipMemcpyAsync(d_tab, host.data(), sizeof(int32_t) * host.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (`host` is pageable and dies with this call)
+    if (e == hipSuccess) {
+        MergeArgs a;
+        a.dst = dst->data;
+        a.src = src->data;
+        a.Kd = dst->K;
+        a.Ks = src->K;
+        a.nrow = nrow_dst;
+        a.nvox = dst->nvox;
+        a.offsets = d_tab;
+        a.sources = d_tab + n_off;
+        e = epgx_launch_merge(ctx->stream, a);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(dst->dens, src->dens, sizeof(double) * (size_t)dst->nvox, hipMemcpyDeviceToDevice, ctx->stream);
+    }
+    dev_free(ctx, d_tab);   // (recycled in stream order, behind the kernel that reads it)
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_state_merge: %s", hipGetErrorString(e));
     return EPGX_OK;
 }
 

@@ -307,7 +307,10 @@ def simulate(sequence, *, adc_time=False, init=None, squeeze=False, probe=None, 
 
     if has_exchange(sequence):
         _check_exchange(sequence, probes, init, out, devices)
-    on_device = all((pb or op)._device_kind() is not None
+    float_shift = has_float_shift(sequence, init)
+    if float_shift:
+        _check_float_shift(sequence, probes, {**(init.options if init is not None else {}), **options})
+    on_device = not float_shift and all((pb or op)._device_kind() is not None
                     for op in sequence if isinstance(op, Probe) for pb in (probes or [op]))
     on_device = on_device and not any(part._on_host() for op in sequence for part in op._parts())   # (user-written operators)
     if init is not None and getattr(init, "_eq", None) is not None:
@@ -345,6 +348,30 @@ def has_exchange(sequence):
     """True if a (flat) sequence holds an exchange operator X"""
     from .exchange import X
     return any(isinstance(part, X) for op in sequence for part in op._parts())
+
+
+def has_float_shift(sequence, init=None):
+    """True if a (flat) sequence holds a shift that takes the shift-merge (shift.py:213-254): a float wavenumber (S with a float
+    k, G, C), or any shift once the start state has float coordinates.  Such a shift needs reductions of the state as it stands
+    (kmerge.py): the sequence runs operator by operator -- device modes, out="device" and ngpu > 1 raise what they raise for
+    probes the kernel cannot record"""
+    floating = init is not None and getattr(getattr(init, "_kspace", None), "points", np.zeros(0, int)).dtype.kind == "f"
+    return any(isinstance(part, _shift.S) and (floating or part._float_k()) for op in sequence for part in op._parts())
+
+
+def _check_float_shift(sequence, probes, options):
+    """what a sequence with a float shift does not carry: NotImplementedError that names the thing"""
+    from .diff import Jacobian, Hessian
+    if not options.get("kgrid") and any(getattr(part, "kgrid", None) is not None for op in sequence for part in op._parts()):
+        # one run, one grid: the coordinate set of a run is ordered by the cells of ONE grid (kmerge.FloatKSpace), which
+        # simulate() takes as the state-matrix option.  A grid that only single operators carry is honoured by op(sm)
+        raise NotImplementedError("simulate() of float shifts takes the grid as its option kgrid= (the state matrix's); a grid "
+                                  "carried by the operators alone (S(k, kgrid=...)) is honoured by op(sm) only")
+    if any(isinstance(pb, (Jacobian, Hessian)) for pb in list(probes) + list(sequence)) or any(
+            getattr(part, "order1", None) or getattr(part, "order2", None) for op in sequence for part in op._parts()):
+        raise NotImplementedError("derivative states (order1 / order2, Jacobian / Hessian) through a float shift (shift-merge)")
+    if has_exchange(sequence):
+        raise NotImplementedError("X (exchange) in a sequence with float shifts (shift-merge)")
 
 
 def _check_exchange(sequence, probes, init, out, devices):

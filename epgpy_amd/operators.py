@@ -6,7 +6,7 @@ from .opmatrix import MatrixOp
 from .opscalar import ScalarOp
 from .evolution import E, P, R
 from .transition import T, Tx, Ty, Phi
-from .shift import S
+from .shift import S, G, C
 from .diffusion import D
 from .diff import Jacobian, Hessian, PartialsPruner
 from .exchange import X

@@ -271,7 +271,7 @@ class Encoder:
         elif what == "spoil":
             self.kspace = self.kspace.after_spoiler()
         elif what == "reset":
-            self.kspace = kspace.KSpace.equilibrium(self.kspace.kdim)
+            self.kspace = type(self.kspace).equilibrium(self.kspace.kdim)      # (float coordinates stay float: statematrix.py:293-297)
 
     def kspace_now(self, kdim=1):
         """coordinate set at this point of the sequence (virtual 1-D orders if no n-D shift yet)"""
@@ -548,6 +548,9 @@ def apply_operators(sm, ops, _plain=False):
                 result = op._apply(op.prepare(sm, inplace=True))
                 sm = sm if result is None else result
         return sm
+    from . import kmerge
+    if kmerge.has_merge(sm._kspace, ops):     # a float shift is a barrier: it needs reductions of the state as it stands
+        return kmerge.apply(sm, ops)
     if not _plain and getattr(sm, "_eq", None) is not None:
         return _apply_with_equilibrium(sm, ops)
     grid = common.broadcast_shapes(sm.shape, *[op.shape for op in ops], append=True)

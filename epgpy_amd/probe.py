@@ -253,9 +253,10 @@ def read_out(sm, positions, *, phase=None, weights=None, modulation=None, voxel_
     """utils.imaging of the state matrix `sm` at `positions`.  On the device when the request is one epgx_state_dft covers:
     `expand`, a "point" or "box" voxel, no or a scalar `phase`, at most three position columns (and no more than the
     wavenumbers have), weights that broadcast to the image; anything else goes through utils.imaging on the downloaded
-    `sm.F` / `sm.k`.  No operator of this library produces a time coordinate, so `modulation` has no effect (as in the
-    reference while kdim < 4).  State matrices live at the library's capacities (up to 1024 orders), all of which the
-    kernel covers."""
+    `sm.F` / `sm.k`.  A state matrix with a time coordinate (operator C: kdim = 4) takes that host path as well, with
+    `acctime=sm.t` and `modulation` (decay rate and frequency of the accumulated time, utils.imaging); while kdim < 4
+    `modulation` has no effect, as in the reference.  State matrices live at the library's capacities (up to 1024 orders),
+    all of which the kernel covers."""
     pos = np.asarray(positions)
     pos = pos if pos.ndim > 1 else pos[..., np.newaxis]
     wts = None if weights is None else np.asarray(weights)
@@ -266,6 +267,9 @@ def read_out(sm, positions, *, phase=None, weights=None, modulation=None, voxel_
                  and (wts is None or _weights_fit(wts, image_shape))
                  and (sm._kspace is None or sm._kspace.nstate == sm.nstate)
                  and sm.nstate + 1 <= sm._state.K)      # (a state matrix truncated at its capacity: the host view pads it)
+    if sm.kdim == 4:
+        return utils.imaging(positions, sm.F, sm.k[..., :3], sm.t, phase=phase, weights=weights, modulation=modulation,
+                             voxel_shape=voxel_shape, voxel_size=voxel_size, expand=expand, reduce=reduce, tol=tol)
     if not on_device:
         return utils.imaging(positions, sm.F, sm.k[..., :3], phase=phase, weights=weights, modulation=modulation,
                              voxel_shape=voxel_shape, voxel_size=voxel_size, expand=expand, reduce=reduce, tol=tol)

@@ -170,10 +170,16 @@ class StateMatrix:
         self._kspace = None if coords is None else self._planned_coords(coords)
 
     def _planned_coords(self, coords):
-        """`coords=` [.., 2 nstate + 1, kdim] as a planner state: integer, symmetric, sorted rows (what `sm.coords` of an
-        earlier run returns; anything else cannot have come from a shift and is rejected), all rows taken as populated"""
-        from . import kspace
-        ks = kspace.KSpace.from_coords(coords)
+        """`coords=` [.., 2 nstate + 1, kdim] as a planner state: symmetric, sorted rows (what `sm.coords` of an
+        earlier run returns; anything else cannot have come from a shift and is rejected), all rows taken as populated.
+        Integer coordinates come from integer shifts, float ones (dtype float) from a shift-merge"""
+        from . import kspace, kmerge
+        if np.all(np.asarray(coords) == np.round(coords)) and np.asarray(coords).dtype.kind != "f":
+            ks = kspace.KSpace.from_coords(coords)
+        else:       # float coordinates: what `sm.coords` returns after a shift-merge (kmerge.py)
+            coords = np.asarray(coords, dtype=np.float64)
+            ks = kmerge.FloatKSpace.from_coords(coords, self.options.get("kgrid"),
+                                                kmerge.ktvalue(self.kvalue, self.tvalue, coords.shape[-1]))
         if ks.nstate != self._nstate:
             raise ValueError(f"coords: {ks.nrow} rows for a state matrix with nstate={self._nstate}")
         if not common.broadcastable(self._shape, ks.lead or (1,), append=True):
@@ -287,8 +293,9 @@ class StateMatrix:
 
     @property
     def coords(self):
-        """integer k-space coordinates after an n-D shift, else None: [1.., 2n+1, kdim], or [*lead, 1.., 2n+1, kdim]
-        when a vectorised shift made them differ along the leading grid axes `lead`"""
+        """k-space coordinates after an n-D shift, else None: [1.., 2n+1, kdim], or [*lead, 1.., 2n+1, kdim]
+        when a vectorised shift made them differ along the leading grid axes `lead`.  Integer after integer shifts, float
+        after a float shift (shift-merge); a fourth column is the accumulated time (operator C)"""
         if self._kspace is None:
             return None
         ks = self._kspace
@@ -316,7 +323,10 @@ class StateMatrix:
 
     @property
     def i0(self):
-        return self._nstate
+        """index of the F0 state; with a time coordinate the mask of the rows whose wavenumber is zero (statematrix.py:136-141)"""
+        if self.kdim < 4:
+            return self._nstate
+        return np.all(np.isclose(self.coords[..., :3], 0), axis=-1)
 
     def _component(self, c):
         half, _ = self._download()
@@ -342,13 +352,36 @@ class StateMatrix:
 
     @property
     def F0(self):
+        if self.kdim == 4:
+            return self._F0_decayed()
         half, _ = self._download()
         return half[:, 0, 0].reshape(self._shape).copy()
 
-    F0t = F0
+    def _F0_decayed(self):
+        """F0 with a time coordinate (statematrix.py:149-155): sum over the rows with k = 0 of F exp(-|t|), on the device.  Row
+        -j carries the weight of row +j, so this is the spatial read-out (epgx_state_dft) at ONE position, the origin, with
+        the voxel factor w_j = i0_j exp(-|t_j|) of stored order j: only [nvox] values cross PCIe"""
+        n = self._nstate
+        w = (self.i0 * np.exp(-np.abs(self.t))).reshape(-1)[n:]
+        if n + 1 > self._state.K:
+            raise NotImplementedError("F0 of a state matrix with a time coordinate that was truncated at its capacity")
+        buf = _lib.DeviceBuffer(self._ctx, 16 * self.size)
+        _lib.state_dft(self._ctx, self._state, 0, self.size, np.zeros((n + 1, 1)), w, np.zeros((1, 1)), 1.0, buf.ptr.value)
+        out = buf.download(np.complex128, (self.size,)).reshape(self._shape)
+        buf.free()
+        return out
+
+    @property
+    def F0t(self):
+        """a separate F0 for every accumulated time (statematrix.py:157-163)"""
+        if self.kdim < 4:
+            return self.F0
+        return self.F * self.i0
 
     @property
     def Z0(self):
+        if self.kdim == 4:      # (statematrix.py:171-175)
+            return self.Z * self.i0
         half, _ = self._download()
         return half[:, 2, 0].reshape(self._shape).copy()
 
@@ -365,9 +398,23 @@ class StateMatrix:
 
     @property
     def t(self):
-        return 0
+        """time-accumulated dephasing: the fourth coordinate x tvalue (statematrix.py:188-193)"""
+        if self.kdim < 4:
+            return 0
+        return self.coords[..., 3] * self.tvalue
 
-    t0 = t
+    @property
+    def t0(self):
+        """the same for the rows with k = 0 (statematrix.py:195-200)"""
+        if self.kdim < 4:
+            return 0
+        return self.coords[..., 3] * self.i0 * self.tvalue
+
+    @property
+    def ktvalue(self):
+        """kvalue per wavenumber column, then tvalue for the time coordinate (statematrix.py:202-211)"""
+        from . import kmerge
+        return kmerge.ktvalue(self.kvalue, self.tvalue, self.kdim)
 
     @property
     def norm(self):

@@ -400,6 +400,36 @@ int epgx_state_axpy(epgx_state *dst, const epgx_state *src, double alpha, int32_
 int epgx_state_dft(epgx_ctx *ctx, const epgx_state *st, int64_t vox0, int64_t nvox, int32_t nrow, const double *k,
                    const double *w, int32_t d, const double *pos, int64_t npos, double phase_re, double phase_im, void *out);
 
+/* The two device primitives of the float-wavenumber shift (epgpy/shift.py:367-449 `shiftmerge`; csrc/epgx_merge.hip).  The
+ * host plans the new row structure from the coordinates alone (epgpy_amd/kmerge.py); what depends on the state -- the weights
+ * of the merged coordinates and the pruning test -- comes from epgx_state_row_stats, the scatter-add of several old rows into
+ * one new row from epgx_state_merge.  Both are stream-ordered behind the operators that produced the state and validate
+ * before anything is launched.
+ *
+ * epgx_state_row_stats: for every stored order j < nrow, over ALL voxels v of the state,
+ *   sums[c * nrow + j] = sum_v |comp_c,j(v)|,  c = 0, 1, 2   (complex moduli of F_j, conj(F_-j), Z_j)
+ *   maxabs[j]          = max_v max_c |comp_c,j(v)|
+ * (row -j of the reference layout holds the conjugates of stored order j, so its moduli are these with c = 0 and 1 swapped).
+ * A modulus is sqrt(re re + im im), every operation rounded on its own.  Deterministic: the association order of every sum
+ * depends on nvox alone (no atomics), two calls on equal states return equal bits.  sums / maxabs are HOST arrays; the call
+ * synchronises the context's stream.  Errors: EPGX_ERR_INVALID for a NULL argument, a state of another context, nrow outside
+ * [1, K]. */
+int epgx_state_row_stats(epgx_ctx *ctx, const epgx_state *st, int32_t nrow, double *sums /*[3][nrow]*/, double *maxabs /*[nrow]*/);
+
+/* epgx_state_merge: the multi-source gather, for every voxel v, component c and order j of dst,
+ *   dst[v][c][j] = sum over s in [offsets[c][j], offsets[c][j + 1]) of  src[v][comp(e_s)][order(e_s)]  or its conjugate,
+ *   e_s = sources[s] = order | comp << 16 | (1 << 30 if conjugated: the flag of EPGX_OP_GS)
+ * added in the order listed, starting from +0 (the bits of NumPy's add.at on zeros); an empty list and every order from
+ * nrow_dst on give exact zero.  offsets is host int32 [3][nrow_dst + 1] in CSR form over ONE list: offsets[0][0] = 0,
+ * non-decreasing, offsets[c + 1][0] = offsets[c][nrow_dst]; sources has offsets[2][nrow_dst] entries.  dst and src are
+ * different states of the same context and number of voxels; their capacities may differ.  dst takes the densities of src.
+ * The call uploads the table (and synchronises for that) before it launches.
+ * Errors (nothing is launched): EPGX_ERR_UNSUPPORTED for nrow_dst > 1024 (checked first); EPGX_ERR_INVALID for a NULL
+ * argument, states of another context, dst == src, different nvox, nrow_dst outside [1, K of dst], a table that is not in
+ * CSR form, a source entry with a component above 2, an order outside the source's capacity or unknown bits. */
+int epgx_state_merge(epgx_ctx *ctx, epgx_state *dst, const epgx_state *src, int32_t nrow_dst, const int32_t *offsets,
+                     const int32_t *sources);
+
 /* ---- run ------------------------------------------------------------------------------ */
 /* Apply operators [op_begin, op_end) of `plan` to voxels [vox0, vox0+nvox) of the plan's grid.
  *   in  : state to start from (its voxel j is grid voxel vox0+j), or NULL = equilibrium
