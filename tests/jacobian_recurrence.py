@@ -131,7 +131,7 @@ def _shift(st, k, keep, nmax):
 
 
 def jacobian_recurrence(ops, variables, *, probe=None, shape=None, max_nstate=None, through_plain=False, init=None,
-                        kvalue=1.0, dtype=np.clongdouble):
+                        kvalue=1.0, dtype=np.clongdouble, return_state=False):
     """[record, *grid, 1 + len(variables)]: column 0 the probed state, column 1 + v its derivative w.r.t. variables[v] (zeros
     for a name no operator declares) at every ADC.
 
@@ -140,7 +140,8 @@ def jacobian_recurrence(ops, variables, *, probe=None, shape=None, max_nstate=No
     probe: "F0" / "Z0" for every ADC (a Jacobian probe's own kind); None: what each ADC tuple says
     through_plain: SPOILER / D act on the derivative states too (exact_partials=True on the device); resets always clear them
     init: start state [*grid-like, 2 n0 + 1, 3] in the StateMatrix layout (rows k = -n0 .. n0), its partials zero
-    max_nstate: shifts truncate F+ / F- above this order; kvalue: rad/m per order, for D"""
+    max_nstate: shifts truncate F+ / F- above this order; kvalue: rad/m per order, for D
+    return_state: also the final state [*grid, 2 n + 1, 3], rows k = -n .. n at the reference's growing n -> (records, state)"""
     plain = [op[:-1] if isinstance(op[-1], dict) else op for op in ops]
     grid = tuple(shape) if shape is not None else grid_of(plain)
     ar = _Arith(grid, dtype)
@@ -238,7 +239,10 @@ def jacobian_recurrence(ops, variables, *, probe=None, shape=None, max_nstate=No
         for v in dst:
             if dst[v].shape != st.shape:
                 dst[v] = np.broadcast_to(dst[v], st.shape).copy()
-    return np.stack(out)
+    records = np.stack(out) if out else np.zeros((0,) + grid + (1 + len(variables),), ar.cplx)
+    if return_state:
+        return records, st[..., nmax - n: nmax + n + 1, :].copy()
+    return records
 
 
 def column_errors(got, want, zero_atol=0.0):
