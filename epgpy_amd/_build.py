@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJDIR = os.path.join(CSRC, "build")
 LIBPATH = os.path.join(CSRC, "libepgx.so")
 # (object name, source, extra flags)
-UNITS = [("epgx_api.o", "epgx_api.hip", [])] + \
+UNITS = [("epgx_api.o", "epgx_api.hip", []), ("epgx_planner.o", "epgx_planner.cpp", [])] + \
         [(f"epgx_split_p{part}.o", "epgx_split.hip", [f"-DEPGX_PART={part}"]) for part in (16, 0, 8, 4, 2)] + \
         [(f"epgx_cgrow_m{m}.o", "epgx_cgrow.hip", [f"-DEPGX_M={m}"]) for m in (16, 8, 4, 2)] + \
         [(f"epgx_packed_v{v}_k{k}.o", "epgx_packed.hip", [f"-DEPGX_V={v}", f"-DEPGX_KP={k}"]) for v in (3, 2, 1) for k in (32, 16)] + \
@@ -40,6 +40,12 @@ FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
          "-mllvm", "-structurizecfg-skip-uniform-regions=1",
          # the first 16 dwords of run_kernel's arguments are preloaded into SGPRs at wave launch
          "-mllvm", "-amdgpu-kernarg-preload-count=16"]
+# epgx_planner.cpp is plain C++ (launch planning, no HIP): the host compiler alone
+HOST_FLAGS = ["-x", "c++", "-O3", "-std=c++17", "-fPIC"]
+
+
+def flags_for(src):
+    return HOST_FLAGS if src.endswith(".cpp") else FLAGS
 
 
 def hipcc():
@@ -101,7 +107,7 @@ def unit_hash(unit):
     for dep in include_closure(src):
         h.update(dep.encode())
         h.update(_dep_bytes(dep, src))
-    h.update(repr((obj, src, extra, FLAGS)).encode())
+    h.update(repr((obj, src, extra, flags_for(src))).encode())
     return h.hexdigest()
 
 
@@ -113,7 +119,7 @@ def source_hash():
         h.update(dep.encode())
         with open(os.path.join(CSRC, dep), "rb") as fh:
             h.update(fh.read())
-    h.update(repr((UNITS, FLAGS)).encode())
+    h.update(repr((UNITS, FLAGS, HOST_FLAGS)).encode())
     return h.hexdigest()
 
 
@@ -151,7 +157,7 @@ def build(force=False, verbose=False, jobs=None):
                         return path
             except OSError:
                 pass
-        cmd = [cc] + FLAGS + extra + ["-c", src, "-o", path]
+        cmd = [cc] + flags_for(src) + extra + ["-c", src, "-o", path]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd, cwd=CSRC)

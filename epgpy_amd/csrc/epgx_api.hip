@@ -38,6 +38,7 @@
 #include "epgx_xrun_kernels.hip.h"
 #include "epgx_deriv_kernels.hip.h"
 #include "epgx_launch.h"
+#include "epgx_planner.h"
 #include "epgx_chain.h"
 #include "epgx_dft.h"
 #include "epgx_stats.h"
@@ -48,15 +49,7 @@
 using namespace epgx;
 
 // ------------------------------------------------------------------------------ errors
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
+// (fail and the thread-local message behind epgx_last_error: epgx_error.h)
 
 #define HIP_TRY(expr)                                                                        \
     do {                                                                                     \
@@ -67,21 +60,8 @@ static int fail(int code, const char *fmt, ...) {
                         __LINE__);                                                           \
     } while (0)
 
-// Measurement knobs of the selection (environment, read ONCE per process): every one defaults to the kernel the library would
-// take anyway; tools/ab_kernels.sh flips them for A/B runs.  EPGX_TRACE is read per call (tests switch it on and off).
+// Measurement knobs of the selection (Knobs, epgx_planner.h), read from the environment ONCE per process, here and nowhere else.
 namespace {
-struct Knobs {
-    bool rows, rows_deriv, rows_deriv2, drun, runs, grow, contig, split, prefetch;
-    int grow_min;
-    bool fold;
-    double grow_share;
-    bool lead_forward;
-    int slab_voxels; // EPGX_SLAB_VOXELS (tests): voxels per slab of the two-leg launch at 2048 orders (0: as many as 8 GiB of scratch hold)
-    bool split_grow; // EPGX_SPLIT_GROW (default 1): K = 2048 in two legs where it pays (one wavefront per voxel up to 512 populated orders)
-    bool xrun;      // EPGX_XRUN (default 1): ranges with exchange (EPGX_OP_X) on xrun_kernel where it covers them; 0: always the split path
-    bool reach;     // EPGX_REACH (default 1): a range of rows_grow_kernel runs at the orders that can still reach a probe (grow_reach); 0: at 16 / 32 / 64
-    int cgrow;      // EPGX_CGROW: 0 off, 1 (default): growing launches at K = 256 .. 1024, at K = 128 when 60 % of the records run below 64 orders; 2: at K = 128 whenever the other capacities would
-};
 int env_int(const char *name, int fallback) {
     const char *v = getenv(name);
     return v ? atoi(v) : fallback;
@@ -96,7 +76,6 @@ const Knobs &knobs() {
                             env_int("EPGX_REACH", 1) != 0,  env_int("EPGX_CGROW", 1)};
     return k;
 }
-bool tracing() { return getenv("EPGX_TRACE") != nullptr; }
 
 }  // namespace
 
@@ -217,71 +196,29 @@ static void dev_free(epgx_ctx *ctx, void *p) {
     }
 }
 
-// one operator range [begin, end) packed into fused records for capacity K, resident on the device
+// one operator range [begin, end) packed into fused records for capacity K (epgx_planner.h), resident on the device
+enum { DEV_RECS, DEV_DRECS, DEV_DRUNS, DEV_DDRUNS, DEV_BDRUNS, DEV_RUNS, DEV_GROW, DEV_COUNT };
 struct PackedRange {
-    int begin = 0, end = 0, K = 0;
-    Rec *d_recs = nullptr;
-    DRec *d_drecs = nullptr;  // derivative plans only
-    int n_rec = 0;
-    Rec *d_runs = nullptr;    // the same records with runs of identical ones folded (rows_kernel<.., RUNS>), or null
-    int n_runs = 0;
-    Rec *d_grow = nullptr;    // K = 64: the run-folded records cut where the populated orders outgrow 16 and 32 (rows_grow_kernel), or null
-    int n_grow = 0, grow1 = 0, grow2 = 0;   // records [0, grow1) run at 16 orders per voxel, [grow1, grow2) at 32, the rest at 64 ...
-    int grow_cap[3] = {16, 32, 64};         // ... or at fewer, where fewer can still reach a probe (grow_reach)
-    Rec *d_druns = nullptr;   // derivative plans, K = 64: the records with a header in front of every run of same-shape
-    DRec *d_ddruns = nullptr; // fused-echo records (drun_kernel), and their DRecs (a header's is all zero); or null
-    DRecB *d_bdruns = nullptr; // ... and, when the runs are of records folded at run time (DRUN_FOLD), E_b's logarithmic partials
-    int n_druns = 0;
-    int drun_code = 0;        // the run shape the headers of d_druns announce (drun_kernel is instantiated per shape)
-    // K = 128 .. 1024 from equilibrium (run_contig_grow_kernel): records [0, cgrow[0]) run while at most 64 orders can hold anything,
-    // [cgrow[0], cgrow[1]) at most 128, [cgrow[1], cgrow[2]) at most 256, [cgrow[2], cgrow[3]) at most 512; cgrow_share = the share
-    // of the records below the capacity
-    int cgrow[6] = {0, 0, 0, 0, 0, 0};   // (cgrow[3]: K = 2048, where the second leg starts; cgrow[4], cgrow[5]: at most 1024, 1536 -- where parts 2 and 3 of run_split_kernel join)
-    double cgrow_share = 0.0;
-    int cgrow_adc3 = 0;       // probe records in front of record cgrow[3] (K = 2048: the first row the second leg writes)
-    int dgrow1 = 0, dgrow2 = 0;   // fused echoes from equilibrium: entries [0, dgrow1) of d_druns run with one order per lane, [dgrow1, dgrow2) with two
-    int drun_inside = 0, drun_headers = 0, drun_ident = 0;   // records inside runs, runs, runs that repeat one record (EPGX_TRACE)
-    bool use_lds = false, has_adc = false, has_pd = false;
-    bool has_gs = false;     // some record is a gather shift (three staged arrays per wavefront instead of two)
-    bool big_shift = false;  // some record shifts by |n| >= 2 (use_lds is also set by gather shifts)
-    bool seq_slots = false;  // the ADC slots of the range are first_slot, first_slot + 1, ...
-    int first_slot = 0;
-    int pf_count = 0;        // 1 + index of the last record that refers to a per-voxel table for the first time
+    RangeLists lists;
+    void *dev[DEV_COUNT] = {};   // the list of that name with its padding records, or null (upload_range)
+    const Rec *recs(int which) const { return (const Rec *)dev[which]; }
 };
+
+static void free_range(epgx_ctx *ctx, PackedRange &pr) {
+    for (void *&p : pr.dev) {
+        dev_free(ctx, p);
+        p = nullptr;
+    }
+}
 
 struct epgx_plan {
     epgx_ctx *ctx = nullptr;
-    std::vector<epgx_op> ops;  // host copy of the primitive stream (validation, packing)
-    std::vector<uint8_t> zero_pattern;  // per op: 1 / 3 = T table with the TX / TY pattern (plan_create), 2 = E table with Im e0 == 0
-    std::vector<std::vector<int32_t>> gather_tables;  // per op: host copy of an EPGX_OP_GS table (validation)
-    std::vector<epgx_dop> dops;  // first-order partials per op (n_vars > 0)
-    std::vector<uint16_t> dpattern; // per op: bits 2v, 2v + 1 = zero pattern of variable v's partial table (1: phi = 0 / real E, 2: real matrix);
-                                    // bit 8 + v: the partial is a generated one (14 per entry: with the partial of the constant term)
+    PlanHost host;            // the host-only part: the primitive stream and what planning reads of it (epgx_planner.h)
     int32_t deriv_flags = 0;
-    int32_t n_vars = 0;
     std::vector<PackedRange> packed;
     double *d_coef = nullptr;
     int64_t n_coef = 0;
-    int64_t n_pool = 0;       // doubles in the device pool: n_coef + the device-generated part; behind it 32 doubles of
-                              // padding that start with the identity relaxation {1, 0, 1, 0} (folded records)
-    bool fold = true;         // fold precession-free relaxations into neighbouring rotations at run time (pack_records)
-    // derivative plans: logarithmic partials (wT, wL per entry, logtab_kernel) of the real relaxation tables that carry a real
-    // partial over the same index space -- what drun_kernel's folded records read.  Behind the pool's padding.
-    struct LogTab {
-        int64_t off = -1;     // doubles from the pool's base
-        int space = -1;
-        uint32_t any = 0;     // 1: some wT != 0, 2: some wL != 0
-    };
-    std::vector<LogTab> logtabs;
-    std::vector<int32_t> log_of;   // [op * EPGX_MAX_VARS + v] -> index into logtabs, or -1
-    // EPGX_OP_T0 operators whose table the host had fused (E_a . T . E_b, epgx_fuse) and whose partial w.r.t. variable v comes
-    // from the relaxations alone (epgx_fuse_partial chain without a rotation partial): the log tables of E_a and E_b
-    // ([(op * EPGX_MAX_VARS + v) * 2 + {0: a, 1: b}], -1: that side has no partial), or empty.  t0_logd[op * MAX_VARS + v]
-    // says whether the variable can take the logarithmic route at all.
-    std::vector<int32_t> t0_log;
-    std::vector<uint8_t> t0_logd;
-    int64_t n_log = 0;             // doubles of log tables behind n_pool + 32
-    int32_t ndim = 0, n_spaces = 0, n_adc = 0;
+    int32_t ndim = 0, n_adc = 0;
     int64_t shape[EPGX_MAX_DIMS];
     int64_t strides[EPGX_MAX_SPACES][EPGX_MAX_DIMS];
     int64_t nvox_total = 0;
@@ -633,7 +570,7 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
     if (!pl) return fail(EPGX_ERR_NOMEM, "epgx_plan_create: host allocation failed");
     pl->ctx = ctx;
     pl->ndim = d->ndim;
-    pl->n_spaces = d->n_spaces;
+    pl->host.n_spaces = d->n_spaces;
     pl->n_adc = d->n_adc;
     pl->n_coef = d->n_coef;
     int64_t nvox = 1;
@@ -761,9 +698,9 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
         const auto hit = chained.find(op.coef_off);
         return op.opcode == EPGX_OP_MAT0 && hit != chained.end() && hit->second == op.space;
     };
-    pl->ops.assign(d->ops, d->ops + d->n_ops);
+    pl->host.ops.assign(d->ops, d->ops + d->n_ops);
     for (int i = 0; i < d->n_ops; ++i) {
-        const epgx_op &op = pl->ops[i];
+        const epgx_op &op = pl->host.ops[i];
         const char *why = nullptr;
         if (op.opcode < 0 || op.opcode >= EPGX_OP__COUNT) why = "unknown opcode";
         int need = why ? 0 : ncoef_expected(op.opcode);
@@ -814,18 +751,18 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
         delete pl;
         return fail(EPGX_ERR_INVALID, "epgx_plan_create: n_vars=%d (at most %d) or dops missing", d->n_vars, EPGX_MAX_VARS);
     }
-    pl->n_vars = d->n_vars;
+    pl->host.n_vars = d->n_vars;
     pl->deriv_flags = d->deriv_flags;
     {
         const int env = knobs().fold ? 1 : 0;   // (EPGX_FOLD=0: measurements)
-        pl->fold = env != 0 && !(d->deriv_flags & EPGX_PLAN_NO_FOLD) && d->n_vars == 0;
+        pl->host.fold = env != 0 && !(d->deriv_flags & EPGX_PLAN_NO_FOLD) && d->n_vars == 0;
     }
     if (d->n_vars > 0) {
-        pl->dops.assign(d->dops, d->dops + d->n_ops);
+        pl->host.dops.assign(d->dops, d->dops + d->n_ops);
         for (int i = 0; i < d->n_ops; ++i) {
-            const epgx_op &op = pl->ops[i];
+            const epgx_op &op = pl->host.ops[i];
             for (int v = 0; v < EPGX_MAX_VARS; ++v) {
-                const int64_t off = pl->dops[i].coef_off[v];
+                const int64_t off = pl->host.dops[i].coef_off[v];
                 if (off < 0) continue;
                 const char *why = nullptr;
                 int nc = 0;
@@ -833,7 +770,7 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
                 else if (op.opcode == EPGX_OP_T || op.opcode == EPGX_OP_MAT || op.opcode == EPGX_OP_MAT0 || op.opcode == EPGX_OP_T0) nc = 10;
                 else if (op.opcode == EPGX_OP_E) nc = 4;
                 else why = "only T / MAT / E operators can carry partial derivatives";
-                const int sp = pl->dops[i].space[v];
+                const int sp = pl->host.dops[i].space[v];
                 if (!why && (sp < -1 || sp >= d->n_spaces)) why = "index space of a partial out of range";
                 if (!why) {
                     const int64_t last = sp < 0 ? 0 : space_extent[sp];
@@ -1068,16 +1005,16 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
         generated_dpattern[fp.dst_off] = (vp == 1 && (dp == 1 || dp == 255)) ? 1 : ((vp == 3 && (dp == 2 || dp == 255)) ? 2 : 0);
     }
     lap("validated");
-    pl->zero_pattern.assign((size_t)d->n_ops, 0);
+    pl->host.zero_pattern.assign((size_t)d->n_ops, 0);
     for (int i = 0; i < d->n_ops; ++i) {
-        const epgx_op &op = pl->ops[i];
+        const epgx_op &op = pl->host.ops[i];
         if (op.opcode != EPGX_OP_T && op.opcode != EPGX_OP_T0 && op.opcode != EPGX_OP_E) continue;
         if (op.opcode == EPGX_OP_E) {
-            pl->zero_pattern[i] = e_is_real(op.coef_off, op.space) ? 2 : 0;
+            pl->host.zero_pattern[i] = e_is_real(op.coef_off, op.space) ? 2 : 0;
             continue;
         }
         if (op.coef_off >= d->n_coef && op.opcode != EPGX_OP_T0 && is_assembled(op.coef_off, op.ncoef, op.space)) {
-            pl->zero_pattern[i] = 0;   // an assembled rotation table: general chains (no host copy to scan)
+            pl->host.zero_pattern[i] = 0;   // an assembled rotation table: general chains (no host copy to scan)
             continue;
         }
         if (op.coef_off >= d->n_coef) {   // generated on the device: pattern known from its sources
@@ -1086,47 +1023,47 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
                 delete pl;
                 return fail(EPGX_ERR_INVALID, "epgx_plan_create: operator %d refers to the generated part of the pool but no entry of `fuse` writes there", i);
             }
-            pl->zero_pattern[i] = g->second;
+            pl->host.zero_pattern[i] = g->second;
             continue;
         }
-        pl->zero_pattern[i] = t_pattern_once(op.coef_off, op.space, op.ncoef);
+        pl->host.zero_pattern[i] = t_pattern_once(op.coef_off, op.space, op.ncoef);
     }
     if (d->n_vars > 0) {
-        pl->dpattern.assign((size_t)d->n_ops, 0);
+        pl->host.dpattern.assign((size_t)d->n_ops, 0);
         for (int i = 0; i < d->n_ops; ++i)
             for (int v = 0; v < d->n_vars; ++v) {
-                const int64_t off = pl->dops[i].coef_off[v];
+                const int64_t off = pl->host.dops[i].coef_off[v];
                 if (off < 0) continue;
-                if (off >= d->n_coef && pl->ops[i].opcode == EPGX_OP_T0) {   // a generated partial (checked above): pattern known from its sources
+                if (off >= d->n_coef && pl->host.ops[i].opcode == EPGX_OP_T0) {   // a generated partial (checked above): pattern known from its sources
                     const auto g = generated_dpattern.find(off);
                     if (g == generated_dpattern.end()) {
                         delete pl;
                         return fail(EPGX_ERR_INVALID, "epgx_plan_create: operator %d, variable %d: the partial refers to the generated part of the pool but no entry of `fuse_partial` writes there", i, v);
                     }
-                    pl->dpattern[i] |= (uint16_t)(((g->second & 3u) << (2 * v)) | (256u << v));
+                    pl->host.dpattern[i] |= (uint16_t)(((g->second & 3u) << (2 * v)) | (256u << v));
                     continue;
                 }
-                pl->dpattern[i] |= (uint16_t)((d_pattern_once(off, pl->dops[i].space[v], pl->ops[i].opcode == EPGX_OP_E) & 3u) << (2 * v));
+                pl->host.dpattern[i] |= (uint16_t)((d_pattern_once(off, pl->host.dops[i].space[v], pl->host.ops[i].opcode == EPGX_OP_E) & 3u) << (2 * v));
             }
     }
     lap("zero scan");
-    pl->gather_tables.resize((size_t)d->n_ops);
+    pl->host.gather_tables.resize((size_t)d->n_ops);
     for (int i = 0; i < d->n_ops; ++i) {
-        const epgx_op &op = pl->ops[i];
+        const epgx_op &op = pl->host.ops[i];
         if (op.opcode != EPGX_OP_GS) continue;
         if (op.space >= 0) {
             delete pl;
             return fail(EPGX_ERR_UNSUPPORTED, "epgx_plan_create: operator %d: gather shifts must be the same for all voxels", i);
         }
         const int32_t *src = (const int32_t *)(d->coef + op.coef_off);
-        pl->gather_tables[i].assign(src, src + 2 * (size_t)op.ncoef);
+        pl->host.gather_tables[i].assign(src, src + 2 * (size_t)op.ncoef);
     }
     int rc = set_device(ctx);
     if (rc) { delete pl; return rc; }
     lap("host done");
     hipError_t e = hipSuccess;
     // pool padded so that the fixed-width scalar loads of the last entry stay in bounds
-    pl->n_pool = n_pool;
+    pl->host.n_pool = n_pool;
     // derivative plans that may fold (drun_kernel): a table of logarithmic partials per (real relaxation table, real partial
     // table over the same index space)
     struct LogJob { int64_t e_off, de_off, entries; };
@@ -1134,40 +1071,40 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
     {
         const int env = knobs().fold ? 1 : 0;
         if (d->n_vars > 0 && env != 0 && !(d->deriv_flags & EPGX_PLAN_NO_FOLD)) {
-            pl->log_of.assign((size_t)d->n_ops * EPGX_MAX_VARS, -1);
+            pl->host.log_of.assign((size_t)d->n_ops * EPGX_MAX_VARS, -1);
             std::map<std::pair<int64_t, int64_t>, int32_t> seen;
             for (int i = 0; i < d->n_ops; ++i) {
-                const epgx_op &op = pl->ops[i];
-                if (op.opcode != EPGX_OP_E || op.ncoef != 4 || pl->zero_pattern[i] != 2) continue;
+                const epgx_op &op = pl->host.ops[i];
+                if (op.opcode != EPGX_OP_E || op.ncoef != 4 || pl->host.zero_pattern[i] != 2) continue;
                 for (int v = 0; v < d->n_vars; ++v) {
-                    const int64_t doff = pl->dops[i].coef_off[v];
-                    if (doff < 0 || ((pl->dpattern[i] >> (2 * v)) & 3u) != 1u || pl->dops[i].space[v] != op.space) continue;
+                    const int64_t doff = pl->host.dops[i].coef_off[v];
+                    if (doff < 0 || ((pl->host.dpattern[i] >> (2 * v)) & 3u) != 1u || pl->host.dops[i].space[v] != op.space) continue;
                     const auto key = std::make_pair((int64_t)op.coef_off, doff);
                     auto it = seen.find(key);
                     if (it == seen.end()) {
-                        epgx_plan::LogTab lt;
-                        lt.off = n_pool + 32 + pl->n_log;
+                        LogTab lt;
+                        lt.off = n_pool + 32 + pl->host.n_log;
                         lt.space = op.space;
                         const int64_t entries = (op.space < 0 ? 0 : space_extent[op.space]) + 1;
-                        pl->n_log += 2 * entries;
+                        pl->host.n_log += 2 * entries;
                         log_jobs.push_back({op.coef_off, doff, entries});
-                        it = seen.emplace(key, (int32_t)pl->logtabs.size()).first;
-                        pl->logtabs.push_back(lt);
+                        it = seen.emplace(key, (int32_t)pl->host.logtabs.size()).first;
+                        pl->host.logtabs.push_back(lt);
                     }
-                    pl->log_of[(size_t)i * EPGX_MAX_VARS + v] = it->second;
+                    pl->host.log_of[(size_t)i * EPGX_MAX_VARS + v] = it->second;
                 }
             }
             // fused echoes: walk the epgx_fuse_partial chain behind every generated partial of an EPGX_OP_T0 operator
             if (d->n_fuse_partial > 0) {
                 std::map<int64_t, int> recipe_of;
                 for (int k = 0; k < d->n_fuse_partial; ++k) recipe_of[d->fuse_partial[k].dst_off] = k;
-                pl->t0_log.assign((size_t)d->n_ops * EPGX_MAX_VARS * 2, -1);
-                pl->t0_logd.assign((size_t)d->n_ops * EPGX_MAX_VARS, 0);
+                pl->host.t0_log.assign((size_t)d->n_ops * EPGX_MAX_VARS * 2, -1);
+                pl->host.t0_logd.assign((size_t)d->n_ops * EPGX_MAX_VARS, 0);
                 std::map<std::pair<int64_t, int>, std::pair<int32_t, int32_t>> walked;   // (partial offset) -> (a, b), -2: not logarithmic
                 for (int i = 0; i < d->n_ops; ++i) {
-                    if (pl->ops[i].opcode != EPGX_OP_T0) continue;
+                    if (pl->host.ops[i].opcode != EPGX_OP_T0) continue;
                     for (int v = 0; v < d->n_vars; ++v) {
-                        const int64_t doff = pl->dops[i].coef_off[v];
+                        const int64_t doff = pl->host.dops[i].coef_off[v];
                         if (doff < d->n_coef) continue;   // (no partial, or not a generated one)
                         const auto wkey = std::make_pair(doff, 0);
                         auto w = walked.find(wkey);
@@ -1185,14 +1122,14 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
                                     const auto key = std::make_pair((int64_t)fp.e_off, (int64_t)fp.de_off);
                                     auto it = seen.find(key);
                                     if (it == seen.end()) {
-                                        epgx_plan::LogTab lt;
-                                        lt.off = n_pool + 32 + pl->n_log;
+                                        LogTab lt;
+                                        lt.off = n_pool + 32 + pl->host.n_log;
                                         lt.space = fp.e_space;
                                         const int64_t entries = (fp.e_space < 0 ? 0 : space_extent[fp.e_space]) + 1;
-                                        pl->n_log += 2 * entries;
+                                        pl->host.n_log += 2 * entries;
                                         log_jobs.push_back({fp.e_off, fp.de_off, entries});
-                                        it = seen.emplace(key, (int32_t)pl->logtabs.size()).first;
-                                        pl->logtabs.push_back(lt);
+                                        it = seen.emplace(key, (int32_t)pl->host.logtabs.size()).first;
+                                        pl->host.logtabs.push_back(lt);
                                     }
                                     side[which] = it->second;
                                 }
@@ -1204,17 +1141,17 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
                             w = walked.emplace(wkey, ok ? std::make_pair(side[0], side[1]) : std::make_pair(-2, -2)).first;
                         }
                         if (w->second.first == -2) continue;
-                        pl->t0_log[((size_t)i * EPGX_MAX_VARS + v) * 2] = w->second.first;
-                        pl->t0_log[((size_t)i * EPGX_MAX_VARS + v) * 2 + 1] = w->second.second;
-                        pl->t0_logd[(size_t)i * EPGX_MAX_VARS + v] = 1;
+                        pl->host.t0_log[((size_t)i * EPGX_MAX_VARS + v) * 2] = w->second.first;
+                        pl->host.t0_log[((size_t)i * EPGX_MAX_VARS + v) * 2 + 1] = w->second.second;
+                        pl->host.t0_logd[(size_t)i * EPGX_MAX_VARS + v] = 1;
                     }
                 }
             }
         }
     }
-    e = dev_alloc(ctx, (void **)&pl->d_coef, sizeof(double) * (size_t)(n_pool + 32 + pl->n_log + (pl->n_log ? 32 : 0)));
-    if (e == hipSuccess && pl->n_log)
-        e = hipMemsetAsync(pl->d_coef + n_pool + 32 + pl->n_log, 0, sizeof(double) * 32, ctx->stream);
+    e = dev_alloc(ctx, (void **)&pl->d_coef, sizeof(double) * (size_t)(n_pool + 32 + pl->host.n_log + (pl->host.n_log ? 32 : 0)));
+    if (e == hipSuccess && pl->host.n_log)
+        e = hipMemsetAsync(pl->d_coef + n_pool + 32 + pl->host.n_log, 0, sizeof(double) * 32, ctx->stream);
     if (e == hipSuccess)   // (the generated part is written entry by entry: only the padding needs zeros)
         e = hipMemsetAsync(pl->d_coef + n_pool, 0, sizeof(double) * 32, ctx->stream);
     static const double identity_relaxation[4] = {1.0, 0.0, 1.0, 0.0};   // e, Im e, e2, r: what a missing E_a / E_b of a folded record reads
@@ -1358,7 +1295,7 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
             la.pool = pl->d_coef;
             la.e_off = log_jobs[j].e_off;
             la.de_off = log_jobs[j].de_off;
-            la.dst_off = pl->logtabs[j].off;
+            la.dst_off = pl->host.logtabs[j].off;
             la.n_entries = log_jobs[j].entries;
             la.flags = d_logflags;
             la.slot = (int32_t)j;
@@ -1371,19 +1308,19 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (d_logflags) dev_free(ctx, d_logflags);
     for (size_t j = 0; j < log_jobs.size(); ++j) {
-        pl->logtabs[j].any = logflags[j] & 3u;
-        if (logflags[j] & 4u) pl->logtabs[j].off = -1;   // not of the logarithmic form: records that need it do not fold
+        pl->host.logtabs[j].any = logflags[j] & 3u;
+        if (logflags[j] & 4u) pl->host.logtabs[j].off = -1;   // not of the logarithmic form: records that need it do not fold
         if (trace && (j < 8 || (logflags[j] & 4u)))
             fprintf(stderr, "[epgx] plan_create log table %zu: value table at %lld, partial at %lld, %lld entries: wT %s, wL %s%s\n", j,
                     (long long)log_jobs[j].e_off, (long long)log_jobs[j].de_off, (long long)log_jobs[j].entries,
                     (logflags[j] & 1u) ? "nonzero" : "zero", (logflags[j] & 2u) ? "nonzero" : "zero",
                     (logflags[j] & 4u) ? " -- NOT of the logarithmic form" : "");
     }
-    if (trace && !pl->t0_logd.empty()) {
+    if (trace && !pl->host.t0_logd.empty()) {
         int routed = 0, generated = 0;
         for (int i = 0; i < d->n_ops; ++i)
             for (int v = 0; v < d->n_vars; ++v)
-                if (pl->ops[i].opcode == EPGX_OP_T0 && pl->dops[i].coef_off[v] >= 0) (pl->t0_logd[(size_t)i * EPGX_MAX_VARS + v] ? routed : generated)++;
+                if (pl->host.ops[i].opcode == EPGX_OP_T0 && pl->host.dops[i].coef_off[v] >= 0) (pl->host.t0_logd[(size_t)i * EPGX_MAX_VARS + v] ? routed : generated)++;
         fprintf(stderr, "[epgx] plan_create fused-echo partials: %d relaxation-only (logarithmic route), %d with a rotation partial\n", routed, generated);
     }
     lap("uploaded");
@@ -1399,15 +1336,7 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
 extern "C" int epgx_plan_destroy(epgx_plan *pl) {
     if (!pl) return EPGX_OK;
     (void)hipSetDevice(pl->ctx->device);
-    for (auto &pr : pl->packed) {
-        dev_free(pl->ctx, pr.d_recs);
-        dev_free(pl->ctx, pr.d_drecs);
-        dev_free(pl->ctx, pr.d_runs);
-        dev_free(pl->ctx, pr.d_grow);
-        dev_free(pl->ctx, pr.d_druns);
-        dev_free(pl->ctx, pr.d_ddruns);
-        dev_free(pl->ctx, pr.d_bdruns);
-    }
+    for (auto &pr : pl->packed) free_range(pl->ctx, pr);
     dev_free(pl->ctx, pl->d_coef);
     dev_free(pl->ctx, pl->d_vidx);
     dev_free(pl->ctx, pl->d_ops);
@@ -1417,14 +1346,14 @@ extern "C" int epgx_plan_destroy(epgx_plan *pl) {
 
 // make sure the plan's cached table-index array covers [vox0, vox0+nvox)
 static int ensure_vidx(epgx_plan *pl, int64_t vox0, int64_t nvox) {
-    if (pl->n_spaces == 0) return EPGX_OK;
+    if (pl->host.n_spaces == 0) return EPGX_OK;
     if (pl->d_vidx && pl->vidx_vox0 == vox0 && pl->vidx_nvox == nvox) return EPGX_OK;
     epgx_ctx *ctx = pl->ctx;
     if (!pl->d_vidx || pl->vidx_cap < nvox) {
         dev_free(ctx, pl->d_vidx);
         pl->d_vidx = nullptr;
         // the 4-space kernel variant reads four rows: always allocate (and zero) that many
-        const int rows = pl->n_spaces > 2 ? 4 : pl->n_spaces;
+        const int rows = pl->host.n_spaces > 2 ? 4 : pl->host.n_spaces;
         HIP_TRY(dev_alloc(ctx, (void **)&pl->d_vidx, sizeof(int32_t) * (size_t)nvox * rows));
         HIP_TRY(hipMemsetAsync(pl->d_vidx, 0, sizeof(int32_t) * (size_t)nvox * rows, ctx->stream));
         pl->vidx_cap = nvox;
@@ -1435,7 +1364,7 @@ static int ensure_vidx(epgx_plan *pl, int64_t vox0, int64_t nvox) {
     ia.ld = nvox;
     ia.vox0 = vox0;
     ia.nvox = nvox;
-    ia.n_spaces = pl->n_spaces;
+    ia.n_spaces = pl->host.n_spaces;
     ia.ndim = pl->ndim;
     for (int i = 0; i < EPGX_MAX_DIMS; ++i) ia.shape[i] = pl->shape[i];
     memcpy(ia.strides, pl->strides, sizeof(ia.strides));
@@ -1832,1100 +1761,55 @@ extern "C" int epgx_state_merge(epgx_ctx *ctx, epgx_state *dst, const epgx_state
 }
 
 // ------------------------------------------------------------------------------ run
-// Pack primitives [begin, end) into fused records  [misc] -> [T] -> [E] -> [S] -> [ADC].
-// "S E" is rewritten "E S" first: E multiplies every order by the same coefficients and S only
-// moves values, so the two commute bit for bit (the wrap value conj(B_1) * e0 equals
-// conj(B_1 * conj(e0)) exactly); nothing else is reordered.
-// which table of logarithmic partials (epgx_plan::logtabs) the relaxation stage of a record has for every variable
-struct ELog {
-    int32_t tab[EPGX_MAX_VARS];   // -1: the stage has no partial w.r.t. this variable
-    bool blocked;                 // some partial of the stage has no log table: the record cannot fold
-    int32_t t_op;                 // primitive index of the record's rotation stage, or -1
-};
-
-static void pack_records(const std::vector<epgx_op> &all, const std::vector<uint8_t> &zero_pattern,
-                         const std::vector<epgx_dop> &dops, const std::vector<uint16_t> &dpattern, int begin, int end,
-                         int K, bool fold, uint32_t identity_off, std::vector<Rec> &out,
-                         std::vector<DRec> &dout, bool &use_lds, bool &has_adc, const std::vector<int32_t> *log_of = nullptr,
-                         std::vector<ELog> *elog = nullptr) {
-    std::vector<epgx_op> ops;
-    for (int i = begin; i < end; ++i)
-        if (all[i].opcode != EPGX_OP_NOP) {
-            ops.push_back(all[i]);
-            // travels with the operator through the reordering: zero pattern in the low byte, the
-            // primitive's index (for its partial derivatives) above it
-            ops.back().reserved = (int32_t)zero_pattern[i] | (i << 8);
-        }
-    const bool deriv = !dops.empty();
-    for (bool swapped = true; swapped;) {
-        swapped = false;
-        for (size_t i = 0; i + 1 < ops.size(); ++i)
-            if (ops[i].opcode == EPGX_OP_S && ops[i + 1].opcode == EPGX_OP_E) {
-                std::swap(ops[i], ops[i + 1]);
-                swapped = true;
-            }
+// the lists of one range on the device: build_range (epgx_planner.cpp) on a cache miss, uploaded once, kept with the plan
+// every list of `pr.lists` that holds something, with its padding records (all zero) behind it: the kernels fetch up to three
+// records past the end (rows_kernel may run the first as a no-op), rows_deriv_kernel as many DRecs; two past the folded lists
+static hipError_t upload_range(epgx_ctx *ctx, PackedRange &pr) {
+    const RangeLists &l = pr.lists;
+    const struct { const void *host; size_t elem, count, pad; } table[DEV_COUNT] = {
+        {l.recs.data(), sizeof(Rec), l.recs.size(), 3},      {l.drecs.data(), sizeof(DRec), l.drecs.size(), 3},
+        {l.druns.data(), sizeof(Rec), l.druns.size(), 3},    {l.ddruns.data(), sizeof(DRec), l.ddruns.size(), 3},
+        {l.bdruns.data(), sizeof(DRecB), l.bdruns.size(), 3}, {l.runs.data(), sizeof(Rec), l.runs.size(), 2},
+        {l.grow.data(), sizeof(Rec), l.grow.size(), 2}};
+    std::vector<char> staged[DEV_COUNT];
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < DEV_COUNT && e == hipSuccess; ++i) {
+        if (!table[i].count) continue;
+        staged[i].assign((table[i].count + table[i].pad) * table[i].elem, 0);
+        memcpy(staged[i].data(), table[i].host, table[i].count * table[i].elem);
+        e = dev_alloc(ctx, &pr.dev[i], staged[i].size());
+        if (e == hipSuccess) e = hipMemcpyAsync(pr.dev[i], staged[i].data(), staged[i].size(), hipMemcpyHostToDevice, ctx->stream);
     }
-    auto table_ix = [](const epgx_op &op) -> uint32_t {
-        if (op.space < 0) return 0u;  // same entry for every voxel
-        return (uint32_t)(op.ncoef * 8) | ((uint32_t)op.space << 24);  // entry bytes | index space
-    };
-    out.clear();
-    dout.clear();
-    use_lds = has_adc = false;
-    Rec cur;
-    DRec dcur;
-    ELog lcur;
-    memset(&cur, 0, sizeof(cur));
-    memset(&dcur, 0, sizeof(dcur));
-    auto no_logs = [&]() {
-        for (int v = 0; v < EPGX_MAX_VARS; ++v) lcur.tab[v] = -1;
-        lcur.blocked = false;
-        lcur.t_op = -1;
-    };
-    no_logs();
-    if (elog) elog->clear();
-    int stage = 0;  // 1 misc, 2 leading S(+1), 3 T/MAT, 4 E, 5 S, 6 ADC
-    auto flush = [&]() {   // (the leaf numbers are assigned at the end, after the fold pass)
-        if (stage) {
-            out.push_back(cur);
-            if (deriv) dout.push_back(dcur);
-            if (deriv && elog) elog->push_back(lcur);
-        }
-        memset(&cur, 0, sizeof(cur));
-        memset(&dcur, 0, sizeof(dcur));
-        no_logs();
-        stage = 0;
-    };
-    auto partials = [&](const epgx_op &op, bool t_stage) {
-        if (!deriv) return;
-        const epgx_dop &dp = dops[(size_t)(op.reserved >> 8)];
-        const uint32_t pattern = dpattern[(size_t)(op.reserved >> 8)];
-        for (int v = 0; v < EPGX_MAX_VARS; ++v) {
-            if (dp.coef_off[v] < 0) continue;
-            const uint32_t pat = (pattern >> (2 * v)) & 3u;
-            if (pat == 1) dcur.present |= (t_stage ? 256u : 4096u) << v;
-            if (pat == 2 && t_stage) dcur.present |= 65536u << v;
-            const bool with_const = t_stage && (pattern & (256u << v));   // generated partial of a T0 table: 14 per entry
-            const uint32_t bytes = t_stage ? (with_const ? 112u : 80u) : 32u;
-            const uint32_t ix = dp.space[v] < 0 ? 0u : (bytes | ((uint32_t)dp.space[v] << 24));
-            if (t_stage) {
-                dcur.t_off[v] = (uint32_t)(dp.coef_off[v] * 8);
-                dcur.t_ix[v] = ix;
-                dcur.present |= 1u << v;
-                if (with_const) {   // the partial of the constant term sits where a relaxation partial would: slots 10..12 of the
-                    dcur.e_off[v] = dcur.t_off[v] + 80u;   // partial line; such a record has no relaxation stage (below)
-                    dcur.e_ix[v] = ix;
-                    dcur.present |= 16u << v;
-                }
-            } else {
-                dcur.e_off[v] = (uint32_t)(dp.coef_off[v] * 8);
-                dcur.e_ix[v] = ix;
-                dcur.present |= 16u << v;
-                const int32_t tab = (log_of && !log_of->empty()) ? (*log_of)[(size_t)(op.reserved >> 8) * EPGX_MAX_VARS + v] : -1;
-                lcur.tab[v] = tab;
-                if (tab < 0) lcur.blocked = true;
-            }
-        }
-    };
-    auto is_matrix = [](const epgx_op &op) {
-        return op.opcode == EPGX_OP_T || op.opcode == EPGX_OP_T0 || op.opcode == EPGX_OP_MAT || op.opcode == EPGX_OP_MAT0;
-    };
-    for (size_t oi = 0; oi < ops.size(); ++oi) {
-        const epgx_op &op = ops[oi];
-        int st;
-        switch (op.opcode) {
-        case EPGX_OP_T: case EPGX_OP_T0: case EPGX_OP_MAT: case EPGX_OP_MAT0: st = 3; break;
-        case EPGX_OP_E: st = 4; break;
-        case EPGX_OP_S:
-            // "S T ..." : a shift by +1 (no truncation) directly in front of a rotation opens the
-            // record of that rotation instead of being a record of its own -- every record costs
-            // a dependent scalar fetch that the wave has to sit out
-            // (only when the shift could not close the current record anyway, and when the rotation
-            // is not followed by an E: those shapes have straight-line bodies)
-            // (also behind a lone rotation when the NEXT rotation is followed by a shift of its own -- "T | S T S ..." : the
-            // excitation of a train.  The shift saves no record either way, and the first repetition of the train then has the
-            // shape of the others, so that the run-length folding takes all of them: EPGX_LEAD_FORWARD=0, measurements)
-            st = ((stage == 0 || stage >= 5 ||
-                   (stage == 3 && knobs().lead_forward && oi + 2 < ops.size() && ops[oi + 2].opcode == EPGX_OP_S && ops[oi + 2].ia == 1)) &&
-                  op.ia == 1 && op.ib >= K - 1 && oi + 1 < ops.size() && is_matrix(ops[oi + 1]) &&
-                  !(oi + 2 < ops.size() && ops[oi + 2].opcode == EPGX_OP_E))
-                     ? 2
-                     : 5;
-            break;
-        case EPGX_OP_ADC: st = 6; break;
-        default: st = 1; break;
-        }
-        if (st <= stage || st == 1) flush();
-        if (deriv && st == 4 && (cur.flags & F_T0) && (dcur.present & 0x70u)) flush();   // (the relaxation-partial slots are taken)
-        switch (op.opcode) {
-        case EPGX_OP_T: case EPGX_OP_T0: case EPGX_OP_MAT: case EPGX_OP_MAT0:
-            cur.flags |= (op.opcode == EPGX_OP_T)    ? F_T
-                         : (op.opcode == EPGX_OP_T0) ? (F_T | F_T0)
-                         : (op.opcode == EPGX_OP_MAT) ? F_MAT
-                                                      : (F_MAT | F_MAT0);
-            if ((op.opcode == EPGX_OP_T || op.opcode == EPGX_OP_T0) && (op.reserved & 0xff) == 1) cur.flags |= F_TX;
-            if ((op.opcode == EPGX_OP_T || op.opcode == EPGX_OP_T0) && (op.reserved & 0xff) == 3) cur.flags |= F_TY;
-            partials(op, true);
-            lcur.t_op = op.reserved >> 8;
-            cur.t_off = (uint32_t)(op.coef_off * 8);
-            cur.t_ix = table_ix(op);
-            break;
-        case EPGX_OP_E:
-            cur.flags |= F_E | ((op.reserved & 0xff) == 2 ? F_ER : 0u);
-            partials(op, false);
-            cur.e_off = (uint32_t)(op.coef_off * 8);
-            cur.e_ix = table_ix(op);
-            break;
-        case EPGX_OP_S:
-            if (st == 2) {
-                cur.flags |= F_S0;
-                break;
-            }
-            cur.flags |= F_S;
-            cur.shift = op.ia;
-            if (op.ib < K - 1) {
-                cur.flags |= F_TRUNC;
-                cur.kmax = op.ib;
-            }
-            if (std::abs(op.ia) > 1) use_lds = true;
-            break;
-        case EPGX_OP_ADC:
-            cur.flags |= F_ADC | (op.ib ? F_ADC_Z : 0u);
-            cur.slot = op.ia;
-            has_adc = true;
-            break;
-        case EPGX_OP_D: case EPGX_OP_GS:
-            cur.flags |= (op.opcode == EPGX_OP_D) ? F_D : F_GS;
-            cur.t_off = (uint32_t)(op.coef_off * 8);
-            cur.t_ix = table_ix(op);
-            if (op.opcode == EPGX_OP_GS) use_lds = true;
-            st = 7;  // nothing else may join this record
-            break;
-        case EPGX_OP_SPOIL: cur.flags |= F_SPOIL; break;
-        case EPGX_OP_RESET: cur.flags |= F_RESET; break;
-        case EPGX_OP_PD:
-            cur.flags |= F_PD | (op.ia ? F_PD_RESET : 0u);
-            cur.e_off = (uint32_t)(op.coef_off * 8);
-            cur.e_ix = table_ix(op);
-            st = 4;  // the E slot of this record is taken
-            break;
-        default: break;
-        }
-        stage = st;
-    }
-    flush();
-
-    // ---- run-time fold (F_FOLD, fold_T in epgx_kernels.hip.h).  A rotation next to precession-free relaxations whose
-    // tables do not share its index space -- T over a B1 axis, E over (T1, T2): the product table would be the whole grid
-    // PER PULSE, so the host's E.T.E fusion (epgx_fuse) does not apply -- becomes ONE stage  E_a . T . E_b  whose
-    // coefficients every wavefront computes for its voxels when it meets the record: 3 instructions per record instead of
-    // 6 per order and relaxation.  E_a = the relaxation stage of the record itself; E_b = the relaxation that closes the
-    // PREVIOUS record (it commutes with the integer shift and the truncation behind it: E scales every order alike, and
-    // the recovery only touches Z_0, which a shift does not move).  An ADC behind E_b pins it; so does a reset or density
-    // stage in front of the rotation.  A SPOILER there is folded as well (F_FOLD_SPOIL: zero F columns).  The decisions only look at neighbours inside one ADC-to-ADC
-    // span, so the per-timestep launches (ranges cut at the probes) and the state-resident launch of the whole
-    // sequence fold alike -- the same chains in the same order in every kernel (same bits; the one exception is the sum /
-    // difference form of rotations about x in the 64-order state-resident kernels: last bits, include/epgx.h epgx_run).
-    // (The decision is per PLAN, never per launch capacity: the same plan must run the same chains at every K.  A host
-    // that runs a plan with 16 orders per voxel sets EPGX_PLAN_NO_FOLD: with one order per lane a relaxation stage is 6
-    // instructions per record, less than the fold's extra loads cost -- the 1000-TR MRF train with max_nstate = 10 takes
-    // 28.2 ms unfolded and 35.6 ms folded at K = 16; K = 32: 43.8 / 33.2 ms.)
-    if (fold && !deriv) {
-        const uint32_t misc = F_SPOIL | F_RESET | F_PD | F_PD_RESET;
-        for (size_t j = 0; j < out.size(); ++j) {
-            Rec &c = out[j];
-            if (!(c.flags & F_T) || (c.flags & (F_MAT | F_T0 | F_FOLD | F_D | F_GS | F_PD))) continue;
-            if ((c.flags & F_S) && c.shift != 1) continue;             // the shift word is about to carry E_b's table
-            if ((c.flags & F_E) && !(c.flags & F_ER)) continue;        // precession behind the rotation: not a real diagonal
-            const bool has_a = (c.flags & F_E) != 0;
-            // a spoiler right in front of the rotation (and no reset / density stage with it) joins the fold: F <- 0 means
-            // that T only sees Z, i.e. the F columns of E_b count as zero; E_b itself commutes with the spoiler
-            const bool spoil = (c.flags & F_SPOIL) && !(c.flags & (misc & ~(uint32_t)F_SPOIL));
-            Rec *p = j > 0 ? &out[j - 1] : nullptr;
-            const bool has_b = p && (p->flags & F_E) && (p->flags & F_ER) && !(c.flags & (misc & ~(uint32_t)F_SPOIL)) &&
-                               !(p->flags & (F_ADC | F_ADC_Z | F_PD | F_PD_RESET | F_D | F_GS | F_FOLD));
-            if (!has_a && !has_b && !spoil) continue;
-            const uint32_t a_off = has_a ? c.e_off : identity_off, a_ix = has_a ? c.e_ix : 0u;
-            c.flags = (c.flags & ~(uint32_t)(F_E | F_ER)) | F_FOLD | F_T0;
-            if (spoil) c.flags = (c.flags & ~(uint32_t)F_SPOIL) | F_FOLD_SPOIL;
-            c.e_off = a_off;
-            c.e_ix = a_ix;
-            c.shift = (int32_t)(has_b ? p->e_off : identity_off);
-            if (has_b) {
-                if (p->e_ix & 0xffffffu) c.flags |= F_FOLD_BVOX | (((p->e_ix >> 24) & 3u) << 21);
-                p->flags &= ~(uint32_t)(F_E | F_ER);
-                p->e_off = p->e_ix = 0;
-                // what is left of the previous record: nothing, or a lone S(+1) that can lead this record
-                const uint32_t rest = p->flags & 0xffffffu;
-                const bool lone_shift = (rest & ~(uint32_t)F_TRUNC) == F_S && p->shift == 1 && !(c.flags & F_S0) &&
-                                        (!(rest & F_TRUNC) || !(c.flags & F_S));   // (one kmax per record: the trailing shift's)
-                if (lone_shift) {
-                    c.flags |= F_S0 | (rest & F_TRUNC);
-                    if (rest & F_TRUNC) c.kmax = p->kmax;
-                    p->flags = 0;
-                }
-            }
-        }
-        out.erase(std::remove_if(out.begin(), out.end(), [](const Rec &r) { return (r.flags & 0xffffffu) == 0; }), out.end());
-    }
-    for (Rec &r : out)   // K < 64 always runs rows_kernel, whose leaves truncate themselves (see record_leaf)
-        r.flags = (r.flags & 0xffffffu) | ((K < 64 ? record_leaf<true>(r.flags, r.shift) : record_leaf<false>(r.flags, r.shift)) << 24);
-}
-
-// The run-folded record list of a launch that starts from EQUILIBRIUM (one populated order), cut where the populated orders
-// outgrow 16 and 32 (rows_grow_kernel: the reference grows its state matrix the same way, functions.py:135 / shift.py:86).
-// `top` = the highest order that can hold anything: every S(+-1) of a record adds one (resets and truncations are ignored:
-// `top` only ever over-estimates, which is safe).  Repeat-count records and header runs are cut at the boundaries.
-// work[p] = the record executions of range p.
-static void grow_split(const std::vector<Rec> &runs, std::vector<Rec> &out, int &n1, int &n2, double work[3]) {
-    auto shifts_of = [](const Rec &r) { return ((r.flags & F_S0) ? 1 : 0) + ((r.flags & F_S) ? 1 : 0); };
-    static const int cap[3] = {15, 31, 1 << 30};
-    int top = 0, phase = 0;
-    n1 = n2 = -1;
-    work[0] = work[1] = work[2] = 0.0;
-    auto next_phase = [&]() {
-        if (phase == 0) n1 = (int)out.size();
-        else n2 = (int)out.size();
-        ++phase;
-    };
-    for (size_t i = 0; i < runs.size();) {
-        const Rec &r = runs[i];
-        const uint32_t head = r.flags >> 24;
-        const int count = (int)((uint32_t)r.kmax >> 16);
-        if (head == LEAF_PAIR || head == LEAF_SINGLE) {
-            const int per = head == LEAF_PAIR ? 2 : 1;   // records per repetition
-            int d = 0;
-            for (int j = 0; j < per; ++j) d += shifts_of(runs[i + 1 + (size_t)j]);
-            int done = 0;
-            while (done < count) {
-                int m = d > 0 ? (cap[phase] - top) / d : count - done;
-                m = std::min(m, count - done);
-                if (m <= 0) {
-                    next_phase();
-                    continue;
-                }
-                Rec h = r;
-                h.kmax = m << 16;
-                out.push_back(h);
-                for (int j = 0; j < per * m; ++j) out.push_back(runs[i + 1 + (size_t)(per * done + j)]);
-                work[phase] += (double)per * m;
-                top += m * d;
-                done += m;
-            }
-            i += 1 + (size_t)per * (size_t)count;
-            continue;
-        }
-        const int d = shifts_of(r), rep = std::max(count, 1);
-        int done = 0;
-        while (done < rep) {
-            int m = d > 0 ? (cap[phase] - top) / d : rep - done;
-            m = std::min(m, rep - done);
-            if (m <= 0) {
-                next_phase();
-                continue;
-            }
-            Rec c = r;
-            c.kmax = (r.kmax & 0xffff) | (m << 16);
-            if (r.flags & F_ADC) c.slot = r.slot + done;   // (a repeat count implies consecutive ADC rows)
-            out.push_back(c);
-            work[phase] += m;
-            top += m * d;
-            done += m;
-        }
-        ++i;
-    }
-    if (n1 < 0) n1 = (int)out.size();
-    if (n2 < 0) n2 = (int)out.size();
-    n1 = std::min(n1, n2);
-}
-
-// The orders per voxel the three ranges [0, n1), [n1, n2), [n2, end) of a cut list NEED (rows_grow_kernel writes no state: its
-// only outputs are the order-0 probes).  A coefficient of order k reaches order 0 through k shifts and through nothing else, so
-// at a record execution with `rem` shifts left up to the last probe of the list (its own included: a record shifts before it
-// probes) the orders above `rem` are dead, and the orders above `top` (grow_split) are empty: the execution needs
-// 1 + min(top, rem) orders, a range the maximum over its executions.  Like `top`, `rem` only ever over-estimates (resets,
-// spoilers and truncations are ignored).  Records behind the last probe need nothing; a list without a probe keeps 16 / 32 / 64.
-// cap[p] = the smallest of 16 / 32 / 64 that holds the need of range p, never more than the range has today.
-static void grow_reach(const std::vector<Rec> &list, int n1, int n2, int cap[3]) {
-    auto shifts_of = [](const Rec &r) { return ((r.flags & F_S0) ? 1 : 0) + ((r.flags & F_S) ? 1 : 0); };
-    struct Exec { int range, d, rep, top0; bool adc; };   // a record of the list: `rep` executions of `d` shifts each from top0 on
-    std::vector<Exec> ex;
-    int top = 0;
-    for (size_t i = 0, members = 0; i < list.size(); ++i) {
-        const Rec &r = list[i];
-        const uint32_t head = r.flags >> 24;
-        const int count = (int)((uint32_t)r.kmax >> 16);
-        if (!members && (head == LEAF_PAIR || head == LEAF_SINGLE)) {   // (a header's low flag bits are a shape code, not flags)
-            members = (size_t)(head == LEAF_PAIR ? 2 : 1) * (size_t)count;
-            continue;
-        }
-        const int rep = members ? 1 : std::max(count, 1);
-        if (members) --members;
-        ex.push_back({(int)i < n1 ? 0 : ((int)i < n2 ? 1 : 2), shifts_of(r), rep, top, (r.flags & F_ADC) != 0});
-        top += rep * ex.back().d;
-    }
-    static const int today[3] = {16, 32, 64};
-    int need[3] = {0, 0, 0};
-    bool probed = false;
-    long rem = 0;   // shifts behind the record at hand up to the last probe
-    for (size_t q = ex.size(); q-- > 0;) {
-        const Exec &x = ex[q];
-        if (!probed && !x.adc) continue;
-        probed = true;
-        for (int e = x.rep - 1; e >= 0; --e) {
-            rem += x.d;
-            const long t = (long)x.top0 + (long)x.d * (e + 1);
-            need[x.range] = (int)std::max<long>(need[x.range], 1 + std::min(t, rem));
-        }
-    }
-    for (int p = 0; p < 3; ++p) cap[p] = !probed ? today[p] : std::min(today[p], need[p] <= 16 ? 16 : (need[p] <= 32 ? 32 : 64));
+    // `staged` is local: nothing may still be reading it when this returns
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? es : e;
 }
 
 static int get_packed(epgx_plan *pl, int begin, int end, int K, const PackedRange **out) {
     for (const auto &pr : pl->packed)
-        if (pr.begin == begin && pr.end == end && pr.K == K) {
+        if (pr.lists.begin == begin && pr.lists.end == end && pr.lists.K == K) {
             *out = &pr;
             return EPGX_OK;
         }
-    std::vector<Rec> recs;
-    std::vector<DRec> drecs;
     PackedRange pr;
-    pr.begin = begin;
-    pr.end = end;
-    pr.K = K;
-    std::vector<ELog> elog;
-    pack_records(pl->ops, pl->zero_pattern, pl->dops, pl->dpattern, begin, end, K, pl->fold, (uint32_t)(pl->n_pool * 8), recs, drecs,
-                 pr.use_lds, pr.has_adc, &pl->log_of, &elog);
-    pr.n_rec = (int)recs.size();
-    for (const Rec &r : recs) pr.big_shift = pr.big_shift || ((r.flags & F_S) && !(r.flags & F_FOLD) && std::abs(r.shift) > 1);
-    for (const Rec &r : recs) pr.has_gs = pr.has_gs || (r.flags & F_GS);
-    pr.seq_slots = true;
-    int expect = -1;
-    for (const Rec &r : recs) pr.has_pd = pr.has_pd || (r.flags & F_PD);
-    for (const Rec &r : recs)
-        if (r.flags & F_ADC) {
-            if (expect < 0) pr.first_slot = r.slot;
-            else if (r.slot != expect) pr.seq_slots = false;
-            expect = r.slot + 1;
-        }
-    {
-        std::vector<std::pair<uint32_t, uint32_t>> seen;
-        auto fresh = [&](uint32_t off, uint32_t ix) {
-            if ((ix & 0xffffffu) == 0) return false;   // same entry for every voxel: hot in the caches
-            for (auto &q : seen)
-                if (q.first == off && q.second == ix) return false;
-            if (seen.size() < 4096) seen.emplace_back(off, ix);
-            return true;
-        };
-        for (int i = 0; i < pr.n_rec; ++i) {
-            const Rec &r = recs[(size_t)i];
-            bool any = false;
-            if (r.flags & (F_T | F_MAT | F_D | F_GS)) any |= fresh(r.t_off, r.t_ix);
-            if (r.flags & (F_E | F_PD)) any |= fresh(r.e_off, r.e_ix);
-            if (any) pr.pf_count = i + 1;
-        }
-    }
-    // Folded copy of the records for rows_kernel<.., RUNS>:
-    //  * a run of identical records (an MSE train: same shape, same table entries, consecutive ADC rows) becomes one
-    //    record with a repeat count in the upper half of the kmax word (rows_run);
-    //  * a run of >= 4 record PAIRS [T, E, S(+1)?, ADC] [E, S(+1)] of constant shapes but arbitrary tables (the repetitions of an
-    //    SSFP / MRF train that cannot be fused) gets a header record in front (leaf byte LEAF_PAIR, shape code, number
-    //    of pairs): rows_pair_run.
-    // Kept when it saves a quarter of the records or pair runs cover half of them.
-    std::vector<Rec> runs;
-    if (K <= 64 && drecs.empty() && pr.n_rec) {
-        auto leaf_of = [&](const Rec &r) {   // with the truncation handled inside the leaf (K = 64 records carry LEAF_NONE for it)
-            const uint32_t l = r.flags >> 24;
-            return (l == LEAF_NONE && (r.flags & F_TRUNC)) ? record_leaf<true>(r.flags & 0xffffffu, r.shift) : l;
-        };
-        auto pair_code = [&](const Rec &a, const Rec &b) -> int {   // -1: not a pair this kernel loops over
-            int code = -1;
-            for (int c = 0; c < 16 && code < 0; ++c)
-                if (leaf_of(a) == leaf_id((c & 1) ? 2 : 1, (c & 2) ? 2 : 1, (c & 8) != 0, true, false) &&
-                    leaf_of(b) == leaf_id(0, (c & 4) ? 2 : 1, true, false, false))
-                    code = c;
-            return code;
-        };
-        // (same stages AND same table geometry -- entry size and index space: the kernel hoists the per-lane entry offsets)
-        auto same_shape = [](const Rec &x, const Rec &y) {
-            return x.flags == y.flags && x.shift == y.shift && x.kmax == y.kmax && x.t_ix == y.t_ix && x.e_ix == y.e_ix;
-        };
-        // run of folded records of one shape (rows_single_run): stages and table geometry equal, table offsets free
-        auto single_code = [&](const Rec &a) -> int {
-            if (!(a.flags & F_FOLD)) return -1;
-            for (int c = 0; c < 16; ++c)
-                if (leaf_of(a) == leaf_id((c & 1) ? 4 : 3, 0, (c & 4) != 0, (c & 8) != 0, (c & 2) != 0)) return c;
-            return -1;
-        };
-        auto same_fold_shape = [](const Rec &x, const Rec &y) {
-            return x.flags == y.flags && (x.kmax & 0xffff) == (y.kmax & 0xffff) && x.t_ix == y.t_ix && x.e_ix == y.e_ix;
-        };
-        auto identical = [](const Rec &x, const Rec &y) {
-            return x.flags == y.flags && x.shift == y.shift && x.kmax == y.kmax && x.t_off == y.t_off && x.e_off == y.e_off &&
-                   x.t_ix == y.t_ix && x.e_ix == y.e_ix;
-        };
-        size_t in_pairs = 0;
-        bool back_is_plain = false;   // runs.back() is an ordinary record (not part of a pair run): a repeat may fold into it
-        for (int i = 0; i < pr.n_rec;) {
-            const int scode = single_code(recs[(size_t)i]);
-            if (scode >= 0 && !(i + 1 < pr.n_rec && identical(recs[(size_t)i], recs[(size_t)i + 1]))) {
-                int n = 1;   // (a train of IDENTICAL records is folded into a repeat count instead, below)
-                while (i + n < pr.n_rec && n < 0x7fff && same_fold_shape(recs[(size_t)i], recs[(size_t)i + n]) &&
-                       !(i + n + 1 < pr.n_rec && identical(recs[(size_t)i + n], recs[(size_t)i + n + 1])))
-                    ++n;
-                if (n >= 4) {
-                    Rec head;
-                    memset(&head, 0, sizeof(head));
-                    head.flags = (LEAF_SINGLE << 24) | (uint32_t)scode;
-                    head.kmax = n << 16;
-                    runs.push_back(head);
-                    for (int j = 0; j < n; ++j) {
-                        runs.push_back(recs[(size_t)i + j]);
-                        runs.back().kmax = (runs.back().kmax & 0xffff) | (1 << 16);
-                    }
-                    in_pairs += (size_t)n;
-                    i += n;
-                    back_is_plain = false;
-                    continue;
-                }
-            }
-            int code = i + 1 < pr.n_rec ? pair_code(recs[(size_t)i], recs[(size_t)i + 1]) : -1;
-            int npairs = 0;
-            if (code >= 0) {
-                npairs = 1;
-                while (i + 2 * npairs + 1 < pr.n_rec && npairs < 0x7fff && same_shape(recs[(size_t)i], recs[(size_t)i + 2 * npairs]) &&
-                       same_shape(recs[(size_t)i + 1], recs[(size_t)i + 2 * npairs + 1]))
-                    ++npairs;
-            }
-            if (npairs >= 4) {
-                Rec head;
-                memset(&head, 0, sizeof(head));
-                head.flags = (LEAF_PAIR << 24) | (uint32_t)code;
-                head.kmax = npairs << 16;
-                runs.push_back(head);
-                for (int j = 0; j < 2 * npairs; ++j) {
-                    runs.push_back(recs[(size_t)i + j]);
-                    runs.back().kmax = (runs.back().kmax & 0xffff) | (1 << 16);
-                }
-                in_pairs += 2 * (size_t)npairs;
-                i += 2 * npairs;
-                back_is_plain = false;
-                continue;
-            }
-            const Rec &r = recs[(size_t)i];
-            bool same = false;
-            if (back_is_plain && (r.flags >> 24) != LEAF_NONE) {
-                const Rec &q = runs.back();
-                const int rep = (int)((uint32_t)q.kmax >> 16);
-                same = q.flags == r.flags && q.shift == r.shift && (q.kmax & 0xffff) == r.kmax && q.t_off == r.t_off &&
-                       q.e_off == r.e_off && q.t_ix == r.t_ix && q.e_ix == r.e_ix && rep < 0x7fff &&
-                       (!(r.flags & F_ADC) || r.slot == q.slot + rep);
-            }
-            if (same) runs.back().kmax += 1 << 16;
-            else {
-                runs.push_back(r);
-                runs.back().kmax = (r.kmax & 0xffff) | (1 << 16);
-                back_is_plain = true;
-            }
-            ++i;
-        }
-        if (runs.size() * 4 > (size_t)pr.n_rec * 3 && in_pairs * 2 < (size_t)pr.n_rec) runs.clear();
-    }
-    // K = 64: the same list cut into phases of 16 / 32 / 64 orders per voxel for launches from equilibrium (rows_grow_kernel); kept
-    // when at least a tenth of the record executions run below 64 orders (a 20-echo train: 15 of 20; a 1000-TR train: 30 of 1000)
-    std::vector<Rec> grow;
-    if (K == 64 && !runs.empty()) {
-        double work[3];
-        grow_split(runs, grow, pr.grow1, pr.grow2, work);
-        if (knobs().grow_min >= 2) pr.grow1 = 0;   // (EPGX_GROW_MIN=2, measurements: first phase at 2 orders per lane)
-        if (knobs().reach) grow_reach(grow, pr.grow1, pr.grow2, pr.grow_cap);   // (EPGX_REACH=0, measurements: 16 / 32 / 64)
-        // the share of record executions that run below 64 orders: the first two ranges, and the last where it runs short
-        const double all = work[0] + work[1] + work[2];
-        const double early = all > 0 ? (work[0] + work[1] + (pr.grow_cap[2] < 64 ? work[2] : 0.0)) / all : 0.0;
-        if (early < knobs().grow_share) grow.clear();   // (EPGX_GROW_SHARE, measurements)
-        if (tracing())
-            for (size_t i = 0; i < grow.size(); ++i)
-                fprintf(stderr, "[epgx] grow list %zu: leaf %u flags %06x x %u (orders <= %d)%s\n", i, grow[i].flags >> 24, grow[i].flags & 0xffffffu,
-                        (uint32_t)grow[i].kmax >> 16, grow[i].kmax & 0xffff, (int)i == pr.grow1 || (int)i == pr.grow2 ? "   <- next phase" : "");
-    }
-    // K = 128 .. 2048: where the populated orders of a launch from equilibrium outgrow 64, 128 .. 1536 (run_contig_grow_kernel; the
-    // two legs at 2048 orders).  `top` = the highest order that can hold anything, as in grow_split: every shift of a record adds one
-    if (K >= 128 && drecs.empty() && pr.n_rec && !pr.use_lds) {
-        int top = 0, phase = 0;
-        double below = 0;
-        static const int cap[6] = {63, 127, 255, 511, 1023, 1535};
-        for (int &g : pr.cgrow) g = pr.n_rec;
-        for (int i = 0; i < pr.n_rec; ++i) {
-            const Rec &r = recs[(size_t)i];
-            top += ((r.flags & F_S0) ? 1 : 0) + ((r.flags & F_S) ? 1 : 0);
-            while (phase < 6 && top > cap[phase]) pr.cgrow[phase++] = i;
-            if (phase < 5 && 64 << phase < K) below += 1;
-        }
-        for (int i = 0; i < pr.cgrow[3] && i < pr.n_rec; ++i) pr.cgrow_adc3 += (recs[(size_t)i].flags & F_ADC) ? 1 : 0;
-        for (int q = 0; q < 6; ++q)
-            if (cap[q] + 1 >= K) pr.cgrow[q] = pr.n_rec;     // (no phase at or above the capacity)
-        for (int q = 1; q < 6; ++q) pr.cgrow[q] = std::max(pr.cgrow[q], pr.cgrow[q - 1]);
-        pr.cgrow_share = below / pr.n_rec;
-    }
-    // Derivative plans at 64 orders: runs of >= 4 records of one shape get a header (leaf byte LEAF_DRUN, shape code, count) and
-    // run on rotating order slots (drun_kernel, epgx_drun_kernels.hip.h); kept when the runs cover at least half of the
-    // records.  Two families of shapes:
-    //   * fused echoes  [S(+1)?  E.T.E + generated partials  S(+1)?  ADC]  (the host fused the tables: epgx_fuse_partial);
-    //   * repetitions FOLDED AT RUN TIME (DRUN_FOLD)  [S(+1)?  E_a . T . E_b  S(+1)?  ADC]  -- a rotation over one index space
-    //     between real relaxations over another (MRF / SSFP trains over a (T1, T2, B1) grid).  The fold happens HERE, for this
-    //     array only (every other kernel keeps walking the unfolded records of d_recs): E_a = the relaxation stage of the
-    //     rotation's own record, E_b = the record in front of it when that is nothing but a real relaxation and a shift by
-    //     one.  The rotation's partial is folded like the rotation (a . dT . b per coefficient); a relaxation's partial
-    //     enters through its table of logarithmic partials (epgx_plan::logtabs) -- every relaxation partial of both stages
-    //     needs one, else the record stays unfolded.  Records the runs leave over are emitted UNFOLDED (their originals).
-    std::vector<Rec> druns;
-    std::vector<DRec> ddruns;
-    std::vector<DRecB> bdruns;
-    if ((K == 64 || K == 32 || K == 16) && !drecs.empty() && pr.n_rec) {   // (16 / 32 orders: folded repetitions only, packed_dfold_kernel)
-        const int nv = pl->n_vars;
-        struct Item { Rec r; DRec d; DRecB b; int lo, hi; bool folded, logd, moved; };
-        std::vector<Item> fl;
-        fl.reserve((size_t)pr.n_rec);
-        const uint32_t identity_off = (uint32_t)(pl->n_pool * 8), zeros_off = (uint32_t)((pl->n_pool + 8) * 8);
-        // (plan_create fills log_of for derivative plans that may fold: EPGX_FOLD, EPGX_PLAN_NO_FOLD)
-        const bool dfold = !pl->log_of.empty() && elog.size() == recs.size();
-        for (int j = 0; j < pr.n_rec; ++j) {
-            Item it;
-            memset(&it, 0, sizeof(it));
-            it.r = recs[(size_t)j];
-            it.d = drecs[(size_t)j];
-            it.lo = it.hi = j;
-            const Rec &c = recs[(size_t)j];
-            const uint32_t cf = c.flags & 0xffffffu;
-            // (a spoiler in front of the rotation joins the fold at 16 / 32 orders -- where spoiled trains live: F_FOLD_SPOIL, the F
-            // columns of E_b count as zero for the STATE; packed_dfold_kernel knows what that means for the derivative states)
-            const uint32_t no_spoil = K == 64 ? (uint32_t)F_SPOIL : 0u;
-            bool can = dfold && (cf & F_T) && (cf & F_ADC) &&
-                       !(cf & (F_MAT | F_MAT0 | F_T0 | F_FOLD | F_D | F_GS | F_PD | F_PD_RESET | no_spoil | F_RESET | F_ADC_Z)) &&
-                       !((cf & F_S) && c.shift != 1) && !((cf & F_E) && !(cf & F_ER));
-            const bool has_a = (cf & F_E) != 0;
-            if (can && has_a && elog[(size_t)j].blocked) can = false;
-            // (three derivative states at 64 orders: the kernel carries one partial line of the rotation, epgx_drun_kernels.hip.h)
-            if (can && K == 64 && nv == 3 && !EPGX_DF3_SPLIT && __builtin_popcount(drecs[(size_t)j].present & 7u) > 1) can = false;
-            bool has_b = false;
-            if (can && j > 0 && !fl.empty() && !fl.back().folded && fl.back().lo == j - 1) {
-                const Rec &q = recs[(size_t)j - 1];
-                const uint32_t rest = q.flags & 0xffffffu;
-                has_b = (rest & F_E) && (rest & F_ER) && !(rest & ~(uint32_t)(F_E | F_ER | F_S | F_TRUNC)) &&
-                        (!(rest & F_S) || q.shift == 1) && !elog[(size_t)j - 1].blocked &&
-                        !((cf & F_S0) && (rest & F_S)) && (!(rest & F_TRUNC) || !(cf & F_S));
-            }
-            if (!can || (!has_a && !has_b)) {
-                // a fused echo (EPGX_OP_T0 from the host's fusion) whose partials w.r.t. some variables come from its relaxations
-                // alone: those variables take the logarithmic route (weights of E_a / E_b instead of a generated partial table)
-                const int t_op = dfold && K == 64 && (cf & F_T0) ? elog[(size_t)j].t_op : -1;
-                if (t_op >= 0 && !pl->t0_logd.empty()) {
-                    DRec nd = it.d;
-                    DRecB nb;
-                    memset(&nb, 0, sizeof(nb));
-                    bool any = false, ok = true;
-                    for (int v = 0; v < EPGX_MAX_VARS; ++v) nb.off[v] = zeros_off;
-                    for (int v = 0; v < nv && ok; ++v) {
-                        if (!pl->t0_logd[(size_t)t_op * EPGX_MAX_VARS + v] || !(nd.present & (1u << v))) continue;
-                        const int32_t ta = pl->t0_log[((size_t)t_op * EPGX_MAX_VARS + v) * 2], tb = pl->t0_log[((size_t)t_op * EPGX_MAX_VARS + v) * 2 + 1];
-                        if ((ta >= 0 && pl->logtabs[(size_t)ta].off < 0) || (tb >= 0 && pl->logtabs[(size_t)tb].off < 0)) continue;   // not of the logarithmic form
-                        nd.present &= ~(((1u | 16u | 256u | 65536u) << v));
-                        nd.t_off[v] = nd.t_ix[v] = 0;
-                        nd.e_off[v] = zeros_off;
-                        nd.e_ix[v] = 0;
-                        if (ta >= 0) {
-                            const auto &lt = pl->logtabs[(size_t)ta];
-                            nd.e_off[v] = (uint32_t)(lt.off * 8);
-                            nd.e_ix[v] = lt.space < 0 ? 0u : (16u | ((uint32_t)lt.space << 24));
-                            nb.logs |= ((lt.any & 1u) ? (1u << v) : 0u) | ((lt.any & 2u) ? (16u << v) : 0u);
-                        }
-                        if (tb >= 0) {
-                            const auto &lt = pl->logtabs[(size_t)tb];
-                            nb.off[v] = (uint32_t)(lt.off * 8);
-                            nb.ix[v] = lt.space < 0 ? 0u : (16u | ((uint32_t)lt.space << 24));
-                            nb.logs |= ((lt.any & 1u) ? (256u << v) : 0u) | ((lt.any & 2u) ? (4096u << v) : 0u);
-                        }
-                        any = true;
-                    }
-                    // (three derivative states: one partial line of the rotation at most)
-                    if (any && !(nv == 3 && __builtin_popcount(nd.present & 7u) > 1)) {
-                        it.d = nd;
-                        it.b = nb;
-                        it.logd = true;
-                    }
-                }
-                fl.push_back(it);
-                continue;
-            }
-            Rec f = c;
-            f.flags = (cf & ~(uint32_t)(F_E | F_ER | F_SPOIL)) | F_FOLD | F_T0 | ((cf & F_SPOIL) ? (uint32_t)F_FOLD_SPOIL : 0u) | (LEAF_NONE << 24);
-            f.e_off = has_a ? c.e_off : identity_off;
-            f.e_ix = has_a ? c.e_ix : 0u;
-            f.shift = (int32_t)identity_off;
-            DRec fd;
-            memset(&fd, 0, sizeof(fd));
-            DRecB fb;
-            memset(&fb, 0, sizeof(fb));
-            const DRec &dc = drecs[(size_t)j];
-            for (int v = 0; v < EPGX_MAX_VARS; ++v) {
-                fd.e_off[v] = fb.off[v] = zeros_off;
-                if (v < nv && (dc.present & (1u << v))) {   // the rotation's partial: folded like the rotation, constant term included
-                    fd.t_off[v] = dc.t_off[v];
-                    fd.t_ix[v] = dc.t_ix[v];
-                    fd.present |= (dc.present & ((1u << v) | (256u << v) | (65536u << v))) | (16u << v);
-                }
-                const int32_t ta = has_a ? elog[(size_t)j].tab[v] : -1;
-                if (ta >= 0) {
-                    const auto &lt = pl->logtabs[(size_t)ta];
-                    fd.e_off[v] = (uint32_t)(lt.off * 8);
-                    fd.e_ix[v] = lt.space < 0 ? 0u : (16u | ((uint32_t)lt.space << 24));
-                    fb.logs |= ((lt.any & 1u) ? (1u << v) : 0u) | ((lt.any & 2u) ? (16u << v) : 0u);
-                }
-            }
-            if (has_b) {
-                const Rec &q = recs[(size_t)j - 1];
-                const uint32_t rest = q.flags & 0xffffffu;
-                f.shift = (int32_t)q.e_off;
-                if (q.e_ix & 0xffffffu) f.flags |= F_FOLD_BVOX | (((q.e_ix >> 24) & 3u) << 21);
-                if (rest & F_S) {
-                    f.flags |= F_S0 | (rest & F_TRUNC);
-                    if (rest & F_TRUNC) f.kmax = q.kmax;
-                }
-                for (int v = 0; v < nv; ++v) {
-                    const int32_t tb = elog[(size_t)j - 1].tab[v];
-                    if (tb < 0) continue;
-                    const auto &lt = pl->logtabs[(size_t)tb];
-                    fb.off[v] = (uint32_t)(lt.off * 8);
-                    fb.ix[v] = lt.space < 0 ? 0u : (16u | ((uint32_t)lt.space << 24));
-                    fb.logs |= ((lt.any & 1u) ? (256u << v) : 0u) | ((lt.any & 2u) ? (4096u << v) : 0u);
-                }
-                fl.pop_back();
-                it.lo = j - 1;
-            }
-            it.r = f;
-            it.d = fd;
-            it.b = fb;
-            it.folded = true;
-            fl.push_back(it);
-        }
-        auto shape_of = [&](const Item &x) {
-            if (x.folded) return dfold_shape(x.r.flags & 0xffffffu, x.d.present, nv, K != 64);
-            if (K != 64) return -1;
-            const int code = drun_shape(x.r.flags & 0xffffffu, x.r.shift, x.d.present, nv);
-            return (code >= 0 && x.logd) ? (code | (int)DRUN_LOGD) : code;
-        };
-        // A trailing S(+1) that closes the record in front of a train (the excitation pulse: [T S] [T0 S ADC] [S0 T0 S ADC] ...) is
-        // the LEADING shift of the train's first record just as well -- same stages in the same order.  Moved, the first echo
-        // has the shape of the others and joins their run (20 echoes: 20 records in the run instead of 16 + 4 flag-tested ones).
-        if (K == 64)
-            for (size_t j = 1; j + 1 < fl.size(); ++j) {
-                Item &q = fl[j - 1], &c = fl[j];
-                const Item &n = fl[j + 1];
-                const uint32_t qf = q.r.flags & 0xffffffu, cf = c.r.flags & 0xffffffu, nf2 = n.r.flags & 0xffffffu;
-                if (q.folded || c.folded != n.folded || q.lo != q.hi || c.lo != c.hi) continue;
-                if (!(qf & F_S) || q.r.shift != 1 || (qf & (F_TRUNC | F_ADC | F_ADC_Z | F_FOLD))) continue;    // (nothing behind that shift)
-                if ((cf & F_S0) || !(nf2 & F_S0) || (cf | F_S0) != nf2 || c.logd != n.logd || shape_of(n) < 0) continue;
-                q.r.flags = ((qf & ~(uint32_t)F_S)) | (LEAF_NONE << 24);
-                q.r.shift = 0;
-                c.r.flags = (cf | F_S0) | (LEAF_NONE << 24);
-                q.moved = c.moved = true;             // (emitted from the item itself from now on: see below)
-            }
-        const int nf = (int)fl.size();
-        auto same_shape = [&](int x, int y) {
-            const Item &X = fl[(size_t)x], &Y = fl[(size_t)y];
-            const Rec &a = X.r, &b = Y.r;
-            const DRec &da = X.d, &db = Y.d;
-            if (X.folded != Y.folded || X.logd != Y.logd) return false;
-            if (((a.flags ^ b.flags) & 0xffffffu) || a.kmax != b.kmax || a.t_ix != b.t_ix || a.e_ix != b.e_ix || da.present != db.present)
-                return false;                                       // (the leaf byte of a record inside a run is never read)
-            if (!X.folded && a.shift != b.shift) return false;      // (a folded record keeps E_b's table offset there)
-            if ((X.folded || X.logd) && X.b.logs != Y.b.logs) return false;
-            for (int v = 0; v < nv; ++v) {
-                if (da.t_ix[v] != db.t_ix[v] || da.e_ix[v] != db.e_ix[v]) return false;
-                if ((X.folded || X.logd) && X.b.ix[v] != Y.b.ix[v]) return false;
-            }
-            return true;
-        };
-        auto same_tables = [&](int x, int y) {
-            const Item &X = fl[(size_t)x], &Y = fl[(size_t)y];
-            const Rec &a = X.r, &b = Y.r;
-            const DRec &da = X.d, &db = Y.d;
-            if (a.t_off != b.t_off || a.e_off != b.e_off) return false;
-            for (int v = 0; v < nv; ++v)
-                if (da.t_off[v] != db.t_off[v] || da.e_off[v] != db.e_off[v] || X.b.off[v] != Y.b.off[v]) return false;
-            return true;
-        };
-        // maximal runs of >= 4 same-shape records; the kernel handles ONE shape per launch: the one that covers most records
-        struct Found { int first, n, code; };
-        std::vector<Found> found;
-        std::map<int, size_t> covered;
-        for (int i = 0; i < nf;) {
-            const int code = shape_of(fl[(size_t)i]);
-            int n = 1;
-            if (code >= 0)
-                while (i + n < nf && n < 0x7fff && same_shape(i, i + n)) ++n;
-            if (code >= 0 && n >= 4 && K != 64) {
-                // 16 / 32 orders: a train that repeats ONE record (an echo train: same tables in every record) stays with the
-                // straight-line leaves of packed_deriv_kernel, which beat the folded loop there (20-echo MSE, 1024 x 1024, three
-                // variables: 6.4 / 2.9 ms at 32 / 16 orders against 6.9 / 3.2 folded); new tables per repetition (MRF) fold
-                bool ident = true;
-                for (int j = 1; j < n && ident; ++j) ident = same_tables(i, i + j);
-                if (ident) {
-                    i += n;
-                    continue;
-                }
-            }
-            if (code >= 0 && n >= 4) {
-                // the loops of drun_kernel are unrolled four times (the slot bases come round after four records) and finish a
-                // run of any length (up to three more records, then the registers are put back in order); the loop at
-                // 16 / 32 orders takes a record at a time anyway
-                const int take = n;
-                found.push_back({i, take, code});
-                covered[code] += (size_t)take * (size_t)(fl[(size_t)i].folded ? 2 : 1);   // (weights: original records covered)
-            }
-            i += n;
-        }
-        size_t in_runs = 0;
-        for (const auto &c : covered)
-            if (c.second > in_runs) {
-                in_runs = c.second;
-                pr.drun_code = c.first;
-            }
-        DRec dzero;
-        memset(&dzero, 0, sizeof(dzero));
-        DRecB bzero;
-        memset(&bzero, 0, sizeof(bzero));
-        size_t next = 0;
-        for (int i = 0; i < nf;) {
-            while (next < found.size() && (found[next].first < i || found[next].code != pr.drun_code)) ++next;
-            if (next < found.size() && found[next].first == i) {
-                const int n = found[next].n;
-                bool ident = !fl[(size_t)i].folded;
-                for (int j = 1; j < n && ident; ++j) ident = same_tables(i, i + j);
-                Rec head;
-                memset(&head, 0, sizeof(head));
-                head.flags = (LEAF_DRUN << 24) | (uint32_t)pr.drun_code | (ident ? (uint32_t)DRUN_IDENT : 0u);
-                head.kmax = n << 16;
-                pr.drun_inside += n;
-                pr.drun_headers += 1;
-                pr.drun_ident += ident ? 1 : 0;
-                druns.push_back(head);
-                ddruns.push_back(dzero);
-                bdruns.push_back(bzero);
-                for (int j = 0; j < n; ++j) {
-                    druns.push_back(fl[(size_t)i + j].r);
-                    ddruns.push_back(fl[(size_t)i + j].d);
-                    bdruns.push_back(fl[(size_t)i + j].b);
-                }
-                i += n;
-                continue;
-            }
-            if (fl[(size_t)i].moved) {           // a record whose shift moved (above): the item's own record, unfolded
-                druns.push_back(fl[(size_t)i].r);
-                ddruns.push_back(drecs[(size_t)fl[(size_t)i].lo]);
-                bdruns.push_back(bzero);
-                ++i;
-                continue;
-            }
-            for (int j = fl[(size_t)i].lo; j <= fl[(size_t)i].hi; ++j) {   // outside the runs: the records as they were packed
-                druns.push_back(recs[(size_t)j]);
-                ddruns.push_back(drecs[(size_t)j]);
-                bdruns.push_back(bzero);
-            }
-            ++i;
-        }
-        if (in_runs * 2 < (size_t)pr.n_rec) {
-            druns.clear();
-            ddruns.clear();
-            bdruns.clear();
-        }
-        // Fused echoes with logarithmic partials at 64 orders, from equilibrium: the run list cut where the populated orders
-        // outgrow 16 and 32 (cf. grow_split) -- drun_kernel walks the first ranges with one and two orders per lane.  Cutting a
-        // run ends its owed E_a update there and starts the next part afresh: the same sums in another association (rounding).
-        if (K == 64 && !druns.empty() && (pr.drun_code & (int)DRUN_LOGD) && !(pr.drun_code & (int)DRUN_FOLD)) {
-            auto shifts_of = [](const Rec &r) { return ((r.flags & F_S0) ? 1 : 0) + ((r.flags & F_S) ? 1 : 0); };
-            static const int cap[3] = {15, 31, 1 << 30};
-            std::vector<Rec> r2;
-            std::vector<DRec> d2v;
-            std::vector<DRecB> b2;
-            int top = 0, phase = 0, n1 = -1, n2 = -1;
-            double work[3] = {0, 0, 0};
-            auto next_phase = [&]() {
-                if (phase == 0) n1 = (int)r2.size();
-                else n2 = (int)r2.size();
-                ++phase;
-            };
-            for (size_t i = 0; i < druns.size();) {
-                const Rec &r = druns[i];
-                if ((r.flags >> 24) == LEAF_DRUN) {
-                    const int count = (int)((uint32_t)r.kmax >> 16);
-                    const int d = shifts_of(druns[i + 1]);
-                    int done = 0;
-                    while (done < count) {
-                        int m = d > 0 ? (cap[phase] - top) / d : count - done;
-                        m = std::min(m, count - done);
-                        if (m <= 0) {
-                            next_phase();
-                            continue;
-                        }
-                        Rec h = r;
-                        h.kmax = m << 16;
-                        r2.push_back(h);
-                        d2v.push_back(ddruns[i]);
-                        b2.push_back(bdruns[i]);
-                        for (int j = 0; j < m; ++j) {
-                            r2.push_back(druns[i + 1 + (size_t)(done + j)]);
-                            d2v.push_back(ddruns[i + 1 + (size_t)(done + j)]);
-                            b2.push_back(bdruns[i + 1 + (size_t)(done + j)]);
-                        }
-                        work[phase] += m;
-                        top += m * d;
-                        done += m;
-                    }
-                    i += 1 + (size_t)count;
-                    continue;
-                }
-                const int d = shifts_of(r);
-                while (top + d > cap[phase]) next_phase();
-                r2.push_back(r);
-                d2v.push_back(ddruns[i]);
-                b2.push_back(bdruns[i]);
-                work[phase] += 1;
-                top += d;
-                ++i;
-            }
-            if (n1 < 0) n1 = (int)r2.size();
-            if (n2 < 0) n2 = (int)r2.size();
-            const double all = work[0] + work[1] + work[2];
-            if (all > 0 && (work[0] + work[1]) / all >= 0.1) {
-                druns.swap(r2);
-                ddruns.swap(d2v);
-                bdruns.swap(b2);
-                pr.dgrow1 = std::min(n1, n2);
-                pr.dgrow2 = n2;
-                if (knobs().grow_min >= 2) pr.dgrow1 = 0;
-            }
-        }
-    }
-    if (pr.n_rec) {
-        Rec pad;  // the kernels fetch up to three records past the end (rows_kernel may run the first as a no-op)
-        memset(&pad, 0, sizeof(pad));
-        recs.push_back(pad);
-        recs.push_back(pad);
-        recs.push_back(pad);
-        epgx_ctx *ctx = pl->ctx;
-        hipError_t e = dev_alloc(ctx, (void **)&pr.d_recs, sizeof(Rec) * recs.size());
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(pr.d_recs, recs.data(), sizeof(Rec) * recs.size(), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && !drecs.empty()) {
-            DRec dpad;   // rows_deriv_kernel fetches up to three entries past the end, like the records
-            memset(&dpad, 0, sizeof(dpad));
-            drecs.push_back(dpad);
-            drecs.push_back(dpad);
-            drecs.push_back(dpad);
-            e = dev_alloc(ctx, (void **)&pr.d_drecs, sizeof(DRec) * drecs.size());
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(pr.d_drecs, drecs.data(), sizeof(DRec) * drecs.size(), hipMemcpyHostToDevice,
-                                   ctx->stream);
-        }
-        if (e == hipSuccess && !druns.empty()) {
-            pr.n_druns = (int)druns.size();
-            DRec dpad;
-            memset(&dpad, 0, sizeof(dpad));
-            DRecB bpad;
-            memset(&bpad, 0, sizeof(bpad));
-            for (int k = 0; k < 3; ++k) {
-                druns.push_back(pad);
-                ddruns.push_back(dpad);
-                bdruns.push_back(bpad);
-            }
-            e = dev_alloc(ctx, (void **)&pr.d_druns, sizeof(Rec) * druns.size());
-            if (e == hipSuccess) e = dev_alloc(ctx, (void **)&pr.d_ddruns, sizeof(DRec) * ddruns.size());
-            if (e == hipSuccess) e = dev_alloc(ctx, (void **)&pr.d_bdruns, sizeof(DRecB) * bdruns.size());
-            if (e == hipSuccess) e = hipMemcpyAsync(pr.d_druns, druns.data(), sizeof(Rec) * druns.size(), hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(pr.d_ddruns, ddruns.data(), sizeof(DRec) * ddruns.size(), hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(pr.d_bdruns, bdruns.data(), sizeof(DRecB) * bdruns.size(), hipMemcpyHostToDevice, ctx->stream);
-        }
-        if (e == hipSuccess && !runs.empty()) {
-            pr.n_runs = (int)runs.size();
-            runs.push_back(pad);
-            runs.push_back(pad);
-            e = dev_alloc(ctx, (void **)&pr.d_runs, sizeof(Rec) * runs.size());
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(pr.d_runs, runs.data(), sizeof(Rec) * runs.size(), hipMemcpyHostToDevice, ctx->stream);
-        }
-        if (e == hipSuccess && !grow.empty()) {
-            pr.n_grow = (int)grow.size();
-            grow.push_back(pad);
-            grow.push_back(pad);
-            e = dev_alloc(ctx, (void **)&pr.d_grow, sizeof(Rec) * grow.size());
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(pr.d_grow, grow.data(), sizeof(Rec) * grow.size(), hipMemcpyHostToDevice, ctx->stream);
-        }
-        {   // `recs` / `drecs` / `runs` are locals: nothing may still be reading them when this returns
-            const hipError_t es = hipStreamSynchronize(ctx->stream);
-            if (e == hipSuccess) e = es;
-        }
+    pr.lists = build_range(pl->host, begin, end, K, knobs());
+    if (pr.lists.n_rec) {
+        const hipError_t e = upload_range(pl->ctx, pr);
         if (e != hipSuccess) {
-            dev_free(ctx, pr.d_recs);
-            dev_free(ctx, pr.d_drecs);
-            dev_free(ctx, pr.d_runs);
-            dev_free(ctx, pr.d_grow);
-            dev_free(ctx, pr.d_druns);
-            dev_free(ctx, pr.d_ddruns);
-            dev_free(ctx, pr.d_bdruns);
+            free_range(pl->ctx, pr);
             return fail(EPGX_ERR_HIP, "epgx_run: uploading records failed: %s", hipGetErrorString(e));
         }
     }
     if (pl->packed.size() >= 4096) {  // bound the cache (streams of thousands of distinct ranges)
-        for (auto &old : pl->packed) {
-            dev_free(pl->ctx, old.d_recs);
-            dev_free(pl->ctx, old.d_drecs);
-            dev_free(pl->ctx, old.d_runs);
-            dev_free(pl->ctx, old.d_grow);
-            dev_free(pl->ctx, old.d_druns);
-            dev_free(pl->ctx, old.d_ddruns);
-            dev_free(pl->ctx, old.d_bdruns);
-        }
+        for (auto &old : pl->packed) free_range(pl->ctx, old);
         pl->packed.clear();
     }
-    pl->packed.push_back(pr);
+    pl->packed.push_back(std::move(pr));
     *out = &pl->packed.back();
     return EPGX_OK;
 }
 
-// ------------------------------------------------------------------------------ kernel selection
-namespace {
-enum Family {
-    FAM_RUN,           // run_kernel<M, NSP, HAS_IN>: one wavefront per voxel, K / 64 orders per lane (any operator; state in / out)
-    FAM_RUN_CONTIG,    // run_contig_kernel: K = 128 .. 1024 without a state output, K / 64 consecutive orders per lane
-    FAM_RUN_CONTIG_GROW, // run_contig_grow_kernel<M, NSP>: the same from equilibrium in phases of 1, 2, 4 .. orders per lane while the state matrix grows
-    FAM_RUN_SPLIT,     // run_split_kernel<4, ..>: K = 2048 from equilibrium, four wavefronts per voxel (behind a run_kernel<8, ..> leg where that pays)
-    FAM_ROWS,          // rows_kernel<NSP, R, RUNS>: four voxels per wavefront, R = K / 16 orders per lane, state-resident
-    FAM_ROWS_GROW,     // rows_grow_kernel<NSP>: the same walked in phases of R = 1, 2, 4 while the state matrix grows (K = 64)
-    FAM_DERIV,         // deriv_kernel<M, NSP, V>: one wavefront per voxel, 1 + V states
-    FAM_PACKED_DERIV,  // packed_deriv_kernel<NSP, V, KP>: 16 / 32 orders, four / two voxels per wavefront, 1 + V states
-    FAM_ROWS_DERIV,    // rows_deriv_kernel<NSP, 4, V>: the rows layout with one or two derivative states
-    FAM_DRUN,          // drun_kernel<NSP, V, SHAPE, V0>: rotating order slots, runs of fused / folded records, 1 + V states
-    FAM_PACKED_DFOLD   // packed_dfold_kernel: 16 / 32 orders, repetitions folded at run time, 1 + V states
-};
-struct Choice {
-    Family family = FAM_RUN;
-    bool runs = false;      // rows kernels: the run-length folded record list
-    bool split_grow = false; // K = 2048: two legs -- run_kernel<8, ..> up to 512 populated orders, then run_split_kernel from its state
-    bool split3 = false;    // drun_kernel: three derivative states of folded runs in two launches (V0 = 2, then V = 2)
-    char name[128] = "";
-    const char *why = "";
-};
-}  // namespace
 
-// THE place where a launch gets its kernel: operators [op_begin, op_end) of a plan at capacity K, with / without a state input
-// and output.  Everything the decision depends on is an argument or a field of the plan / its packed range -- no state of the
-// context, no launch size -- so epgx_kernel_for can answer without launching (tests pin the kernel of every BASELINE config).
-static int choose_kernel(const epgx_plan *pl, const PackedRange *pr, int op_begin, int op_end, int K, bool has_in, bool has_out, Choice *c) {
-    const Knobs &kn = knobs();
-    const bool packed16 = K == 16 || K == 32, wide = K == 2048 && !has_in && !has_out;
-    bool has_general = false, has_nd = false;   // general 3x3 matrices; diffusion / gather shifts
-    for (int i = op_begin; i < op_end; ++i) {
-        const int oc = pl->ops[i].opcode;
-        has_general = has_general || oc == EPGX_OP_MAT || oc == EPGX_OP_MAT0;
-        has_nd = has_nd || oc == EPGX_OP_D || oc == EPGX_OP_GS;
-    }
-    // (the rows kernels and packed_deriv_kernel address the pool through a buffer resource of 2 GiB)
-    const bool pool_in_reach = (pl->n_pool + 64 + pl->n_log) * (int64_t)sizeof(double) <= 0x7fffffff;
-    if (packed16 && !pool_in_reach)
-        return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: K = 16 / 32 need a coefficient pool below 2 GiB (use K = 64)");
-    if (wide && (pr->use_lds || pl->n_vars > 0))
-        return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: K = 2048 handles rotations, relaxation, shifts by +-1 and probes only (no derivative states)");
-    if (packed16 && pr->big_shift) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: K = 16 / 32 handle shifts by +-1 (and, at K = 16, gather shifts) only");
-    if (packed16 && pl->n_vars > 0 && has_in) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: K = 16 / 32 derivative plans start from equilibrium");
-    if (packed16 && pl->n_vars > 0 && pr->use_lds) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: K = 16 / 32 derivative plans handle shifts by +-1 only");
-    const int nsp = pl->n_spaces <= 2 ? pl->n_spaces : 4, V = pl->n_vars;
-    const bool plain_ops = !has_general && !has_nd && !pr->use_lds;   // rotations, relaxation, shifts by +-1, probes, SPOILER / RESET / PD
-    if (V > 0) {
-        if (has_out) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: derivative plans run state-resident (out = NULL)");
-        if (K > 1024) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: derivative plans support K <= 1024, got %d", K);
-        if (K == 1024 && V > 1)
-            return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: at K = 1024 a launch carries ONE derivative state (plan has %d variables: one plan per variable)", V);
-        const bool resident64 = K == 64 && !has_in && plain_ops && pool_in_reach;
-        if (packed16 && kn.drun && pr->d_druns && pr->d_bdruns && !has_in && !pr->use_lds && pool_in_reach) {
-            c->family = FAM_PACKED_DFOLD;
-            c->why = "16 / 32 orders, mostly runs of repetitions folded at run time";
-            snprintf(c->name, sizeof(c->name), "packed_dfold_kernel<%d, %d>", V, K);
-        } else if (kn.drun && pr->d_druns && resident64) {
-            c->family = FAM_DRUN;
-            c->split3 = V == 3 && (pr->drun_code & (int)DRUN_FOLD) && EPGX_DF3_SPLIT;
-            c->why = (pr->drun_code & (int)DRUN_FOLD)   ? "64 orders, mostly runs of repetitions folded at run time: rotating order slots"
-                     : (pr->drun_code & (int)DRUN_LOGD) ? "64 orders, mostly runs of fused echoes with logarithmic relaxation partials: rotating order slots"
-                                                        : "64 orders, mostly runs of fused echoes: rotating order slots";
-            // (runs with logarithmic partials exist for four index spaces only; the others for one and four: epgx_launch_drun)
-            const int knsp = ((pr->drun_code & 384) || pl->n_spaces > 1) ? 4 : 1;
-            if (c->split3) snprintf(c->name, sizeof(c->name), "drun_kernel<%d, 1, %d, 2> + drun_kernel<%d, 2, %d, 0>", knsp, pr->drun_code, knsp, pr->drun_code);
-            else snprintf(c->name, sizeof(c->name), "drun_kernel<%d, %d, %d, 0>", knsp, V, pr->drun_code);
-        } else if (kn.rows_deriv && (V == 1 || (V == 2 && kn.rows_deriv2)) && resident64) {
-            c->family = FAM_ROWS_DERIV;
-            c->why = "64 orders from equilibrium, one or two derivative states: four voxels per wavefront";
-            snprintf(c->name, sizeof(c->name), "rows_deriv_kernel<%d, 4, %d>", nsp, V);
-        } else if (packed16) {
-            c->family = FAM_PACKED_DERIV;
-            c->why = "16 / 32 orders with derivative states";
-            snprintf(c->name, sizeof(c->name), "packed_deriv_kernel<%d, %d, %d>", nsp, V, K);
-        } else {
-            c->family = FAM_DERIV;
-            c->why = "derivative states, one wavefront per voxel";
-            const bool contig_orders = kn.contig && K >= 128 && !pr->use_lds && !has_nd && !(V == 3 && (K == 256 || K == 512));
-            snprintf(c->name, sizeof(c->name), "deriv_kernel<%d, %d, %d%s>", K / 64, nsp, V, contig_orders ? ", true" : "");
-        }
-        return EPGX_OK;
-    }
-    // K = 256 .. 1024 (EPGX_CGROW=2: from 128) from equilibrium with a good share of the records while the state matrix is short: phases of 1, 2, 4 .. orders per lane
-    // (at K = 128 the four-voxels-per-wavefront kernel with 8 orders per lane is the alternative: the phases win while the train mostly
-    // runs below 64 orders -- 40 echoes 1.08 against 1.17 ms, 63 echoes 1.82 against 1.78; EPGX_CGROW=2: always)
-    const bool cgrow = kn.contig && kn.cgrow && K >= 128 && K <= 1024 && !has_in && !has_out && !pr->use_lds && !has_nd &&
-                       pr->cgrow_share >= ((K == 128 && kn.cgrow < 2) ? std::max(kn.grow_share, 0.6) : kn.grow_share);
-    if (cgrow) {
-        c->family = FAM_RUN_CONTIG_GROW;
-        c->why = "from equilibrium, a good share of the records while the state matrix is short: K / 64 consecutive orders per lane reached in phases of 1, 2, 4 ..";
-        snprintf(c->name, sizeof(c->name), "run_contig_grow_kernel<%d, %d>", K / 64, nsp);
-        return EPGX_OK;
-    }
-    // four voxels per wavefront, K / 16 orders per lane: always at 16 / 32 orders; at 64 / 128 state-resident launches of plain operators
-    const bool rows = packed16 || (kn.rows && (K == 64 || K == 128) && !has_in && !has_out && plain_ops && pool_in_reach);
-    if (rows) {
-        c->runs = kn.runs && pr->d_runs && K <= 64;
-        if (c->runs && K == 64 && kn.grow && pr->d_grow) {
-            c->family = FAM_ROWS_GROW;
-            c->why = "64 orders from equilibrium, a good share of the records while the state matrix is short: phases of 1 / 2 / 4 orders per lane";
-            snprintf(c->name, sizeof(c->name), "rows_grow_kernel<%d>", nsp);
-        } else {
-            c->family = FAM_ROWS;
-            c->why = "state-resident, four voxels per wavefront";
-            snprintf(c->name, sizeof(c->name), "rows_kernel<%d, %d, %s>", nsp, K / 16, (c->runs && K <= 64) ? "true" : "false");
-        }
-        return EPGX_OK;
-    }
-    // one wavefront per voxel (four at K = 2048).  Launches without a state output at
-    // K >= 128 are free to choose the order layout: a lane then holds K / 64 consecutive orders and a shift by one costs 8 DPP
-    // moves instead of 16 K / 64 moves and selects (epgx_split.hip; the same bits).  Not with shifts by |n| >= 2, gather shifts or diffusion.
-    const bool free_layout = !has_out && !pr->use_lds && !has_nd;
-    if (K == 2048) {
-        c->family = FAM_RUN_SPLIT;
-        c->split_grow = kn.split_grow && pr->cgrow_share >= kn.grow_share && pr->cgrow[3] > 0;
-        c->why = c->split_grow ? "2048 orders from equilibrium: one wavefront per voxel while at most 512 orders hold anything, then up to four (the state crosses HBM once)"
-                               : "2048 orders from equilibrium: four wavefronts per voxel";
-        if (c->split_grow) snprintf(c->name, sizeof(c->name), "run_kernel<8, %d, false> + run_split_kernel<4, %d, true>", nsp, nsp);
-        else snprintf(c->name, sizeof(c->name), "run_split_kernel<4, %d, false>", nsp);
-    } else if (kn.contig && K >= 128 && K <= 1024 && free_layout) {
-        c->family = FAM_RUN_CONTIG;
-        c->why = "no state output: K / 64 consecutive orders per lane";
-        snprintf(c->name, sizeof(c->name), "run_contig_kernel<%d, %d, %s>", K / 64, nsp, has_in ? "true" : "false");
-    } else {
-        c->family = FAM_RUN;
-        c->why = "one wavefront per voxel, state through HBM or operators the other kernels do not take";
-        snprintf(c->name, sizeof(c->name), "run_kernel<%d, %d, %s>", K / 64, nsp, has_in ? "true" : "false");
-    }
-    return EPGX_OK;
-}
 
 static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin, int32_t op_end, int64_t vox0, int64_t nvox,
                        const epgx_state *in, epgx_state *out, int32_t K, void *signal, int64_t signal_ld, int64_t signal_col0,
@@ -2976,7 +1860,7 @@ static int launch_exchange(epgx_ctx *ctx, const epgx_plan *pl, const epgx_op &op
 static int run_exchange_split(epgx_ctx *ctx, epgx_plan *pl, int32_t op_begin, int32_t op_end, int64_t vox0, int64_t nvox,
                               const epgx_state *in, epgx_state *out, int32_t K, void *signal, int64_t signal_ld, int64_t signal_col0,
                               char *name_out, int64_t name_bytes) {
-    if (pl->n_vars > 0) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: exchange (EPGX_OP_X) in a plan with derivative states");
+    if (pl->host.n_vars > 0) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: exchange (EPGX_OP_X) in a plan with derivative states");
     if (!supported_K(K))
         return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: ranges with an exchange (EPGX_OP_X) keep the state in HBM: K = 64 .. 1024, not %d", K);
     if (vox0 % pl->x_span || nvox % pl->x_span)
@@ -2987,8 +1871,8 @@ static int run_exchange_split(epgx_ctx *ctx, epgx_plan *pl, int32_t op_begin, in
     bool fused = knobs().xrun && NC >= 2 && NC <= 4 && K <= 256 && NC * M <= 8;
     bool has_adc = false;
     for (int i = op_begin; i < op_end && fused; ++i) {
-        fused = pl->ops[i].opcode != EPGX_OP_D && pl->ops[i].opcode != EPGX_OP_GS;
-        has_adc = has_adc || pl->ops[i].opcode == EPGX_OP_ADC;
+        fused = pl->host.ops[i].opcode != EPGX_OP_D && pl->host.ops[i].opcode != EPGX_OP_GS;
+        has_adc = has_adc || pl->host.ops[i].opcode == EPGX_OP_ADC;
     }
     if (name_out) {
         if (fused) snprintf(name_out, (size_t)name_bytes, "xrun_kernel<%d, %d, %s>", NC, M, in ? "true" : "false");
@@ -3003,8 +1887,8 @@ static int run_exchange_split(epgx_ctx *ctx, epgx_plan *pl, int32_t op_begin, in
         {
             std::lock_guard<std::mutex> plan_guard(pl->cache_lock);
             if (!pl->d_ops) {
-                HIP_TRY(dev_alloc(ctx, (void **)&pl->d_ops, sizeof(epgx_op) * pl->ops.size()));
-                HIP_TRY(hipMemcpyAsync(pl->d_ops, pl->ops.data(), sizeof(epgx_op) * pl->ops.size(), hipMemcpyHostToDevice, ctx->stream));
+                HIP_TRY(dev_alloc(ctx, (void **)&pl->d_ops, sizeof(epgx_op) * pl->host.ops.size()));
+                HIP_TRY(hipMemcpyAsync(pl->d_ops, pl->host.ops.data(), sizeof(epgx_op) * pl->host.ops.size(), hipMemcpyHostToDevice, ctx->stream));
             }
         }
         XRunArgs a;
@@ -3022,7 +1906,7 @@ static int run_exchange_split(epgx_ctx *ctx, epgx_plan *pl, int32_t op_begin, in
         a.vox0 = vox0;
         a.stride = pl->x_span / NC;
         a.ndim = pl->ndim;
-        a.n_spaces = pl->n_spaces;
+        a.n_spaces = pl->host.n_spaces;
         memcpy(a.shape, pl->shape, sizeof(a.shape));
         memcpy(a.strides, pl->strides, sizeof(a.strides));
         const int64_t ngroups = nvox / NC;
@@ -3047,7 +1931,7 @@ static int run_exchange_split(epgx_ctx *ctx, epgx_plan *pl, int32_t op_begin, in
     const epgx_state *src = in;   // the state the next piece starts from (NULL: equilibrium)
     int begin = op_begin;
     for (int i = op_begin; i <= op_end && !rc; ++i) {
-        if (i < op_end && pl->ops[i].opcode != EPGX_OP_X) continue;
+        if (i < op_end && pl->host.ops[i].opcode != EPGX_OP_X) continue;
         if (i > begin) {
             rc = run_or_name(ctx, pl, begin, i, vox0, nvox, src, work, K, signal, signal_ld, signal_col0, nullptr, 0);
             src = work;
@@ -3063,7 +1947,7 @@ static int run_exchange_split(epgx_ctx *ctx, epgx_plan *pl, int32_t op_begin, in
             }
             src = work;
         }
-        if (!rc) rc = launch_exchange(ctx, pl, pl->ops[i], vox0, work);
+        if (!rc) rc = launch_exchange(ctx, pl, pl->host.ops[i], vox0, work);
         begin = i + 1;
     }
     if (!rc && out && src != out) rc = epgx_state_copy(out, src);   // (a range of X-free NOPs only: cannot happen, kept for safety)
@@ -3080,7 +1964,7 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
     epgx_plan *pl = const_cast<epgx_plan *>(plan_c);
     if (!ctx || !pl) return fail(EPGX_ERR_INVALID, "epgx_run: NULL argument");
     if (pl->ctx != ctx) return fail(EPGX_ERR_INVALID, "epgx_run: plan belongs to another context");
-    const int n_ops = (int)pl->ops.size();
+    const int n_ops = (int)pl->host.ops.size();
     if (op_begin < 0 || op_end > n_ops || op_begin > op_end)
         return fail(EPGX_ERR_INVALID, "epgx_run: operator range [%d,%d) outside [0,%d)", op_begin, op_end, n_ops);
     if (nvox > (int64_t)4 * 0x7fffffff) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: more than 2^33 voxels in one launch");
@@ -3115,7 +1999,7 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
     }
 
     for (int i = op_begin; i < op_end; ++i) {
-        const epgx_op &op = pl->ops[i];
+        const epgx_op &op = pl->host.ops[i];
         if (op.opcode == EPGX_OP_S && std::abs(op.ia) >= K)
             return fail(EPGX_ERR_INVALID, "epgx_run: operator %d shifts by %d, capacity K=%d", i, op.ia, K);
         if (packed16 && (op.opcode == EPGX_OP_MAT || op.opcode == EPGX_OP_MAT0))
@@ -3129,13 +2013,13 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
             if (2 * op.ncoef != 3 * K)
                 return fail(EPGX_ERR_INVALID, "epgx_run: operator %d: gather table has %d entries, need 3*K=%d", i,
                             2 * op.ncoef, 3 * K);
-            for (int32_t v : pl->gather_tables[i])
+            for (int32_t v : pl->host.gather_tables[i])
                 if (v != -1 && ((v & ~(1 << 30)) < 0 || (v & ~(1 << 30)) >= K))
                     return fail(EPGX_ERR_INVALID, "epgx_run: operator %d: gather index %d outside [0,%d)", i, v, K);
         }
     }
     for (int i = op_begin; i < op_end; ++i)
-        if (pl->ops[i].opcode == EPGX_OP_X)
+        if (pl->host.ops[i].opcode == EPGX_OP_X)
             return run_exchange_split(ctx, pl, op_begin, op_end, vox0, nvox, in, out, K, signal, signal_ld, signal_col0, name_out,
                                       name_bytes);
     if (int rc = set_device(ctx)) return rc;
@@ -3144,13 +2028,13 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
     std::lock_guard<std::mutex> plan_guard(pl->cache_lock);
     const PackedRange *pr = nullptr;
     if (int rc = get_packed(pl, op_begin, op_end, K, &pr)) return rc;
-    if (pr->has_adc && !name_out) {
+    if (pr->lists.has_adc && !name_out) {
         if (!signal) return fail(EPGX_ERR_INVALID, "epgx_run: range contains an ADC but signal is NULL");
         if (signal_col0 < 0 || signal_col0 + nvox > signal_ld)
             return fail(EPGX_ERR_INVALID, "epgx_run: signal columns [%lld,%lld) exceed signal_ld=%lld",
                         (long long)signal_col0, (long long)(signal_col0 + nvox), (long long)signal_ld);
     }
-    if (pr->n_rec == 0) {  // nothing but NOPs: only a state copy may be needed
+    if (pr->lists.n_rec == 0) {  // nothing but NOPs: only a state copy may be needed
         if (name_out) {
             snprintf(name_out, (size_t)name_bytes, "none");
             return EPGX_OK;
@@ -3158,8 +2042,9 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
         if (out && in && out != in) return epgx_state_copy(out, in);
         return EPGX_OK;
     }
+    const RangeLists &rl = pr->lists;
     Choice c;
-    if (int rc = choose_kernel(pl, pr, op_begin, op_end, K, in != nullptr, out != nullptr, &c)) return rc;
+    if (int rc = choose_kernel(pl->host, rl, op_begin, op_end, K, in != nullptr, out != nullptr, knobs(), &c)) return rc;
     if (name_out) {   // epgx_kernel_for: the decision, no launch
         snprintf(name_out, (size_t)name_bytes, "%s", c.name);
         return EPGX_OK;
@@ -3168,69 +2053,63 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
     if (int rc = ensure_vidx(pl, vox0, nvox)) return rc;
 
     hipError_t e = hipSuccess;
-    if (pl->n_vars > 0) {
+    if (pl->host.n_vars > 0) {
         DerivArgs da;
         memset(&da, 0, sizeof(da));
         da.nvox = nvox;
         da.in = in ? in->data : nullptr;
         da.dens_in = in ? in->dens : nullptr;
-        da.recs = pr->d_recs;
-        da.drecs = pr->d_drecs;
+        da.recs = pr->recs(DEV_RECS);
+        da.drecs = (const DRec *)pr->dev[DEV_DRECS];
         da.coef = pl->d_coef;
         da.signal = signal ? (d2 *)signal + signal_col0 : nullptr;
         da.signal_ld = signal_ld;
         da.t.vidx = pl->d_vidx;
         da.t.vidx_ld = pl->vidx_nvox;
         da.t.vox0 = vox0;
-        da.t.n_rec = pr->n_rec;
+        da.t.n_rec = rl.n_rec;
         da.t.dense_spaces = pl->dense_spaces;
-        da.t.use_lds = pr->use_lds ? ((pr->has_gs && K < 1024) ? 3 : 2) : 0;      // (gather shifts at 1024 orders stage Z behind F: gather_shift)
+        da.t.use_lds = c.lds_mode;
         da.through_plain = (pl->deriv_flags & EPGX_DERIV_THROUGH_PLAIN_OPS) ? 1 : 0;
-        {   // deriv_kernel at K >= 128: consecutive orders per lane unless the range shifts by |n| >= 2, gathers or diffuses (EPGX_CONTIG=0: never)
-            bool nd = false;
-            for (int i = op_begin; i < op_end; ++i) nd = nd || pl->ops[i].opcode == EPGX_OP_D || pl->ops[i].opcode == EPGX_OP_GS;
-            // (not with three derivative states at 256 / 512 orders: 282 VGPRs / 585 spill instructions there against 249 / 9 lane-strided,
-            // measured 111 against 75 ms and 313 against 174 ms)
-            da.contig = (knobs().contig && K >= 128 && !pr->use_lds && !nd && !(pl->n_vars == 3 && (K == 256 || K == 512))) ? 1 : 0;
-        }
+        da.contig = c.contig ? 1 : 0;
         if (c.family == FAM_DRUN && knobs().grow) {   // (0, 0: four orders per lane throughout; EPGX_GROW=0, measurements)
-            da.grow1 = pr->dgrow1;
-            da.grow2 = pr->dgrow2;
+            da.grow1 = rl.dgrow1;
+            da.grow2 = rl.dgrow2;
         }
         if (c.family == FAM_PACKED_DFOLD || c.family == FAM_DRUN) {   // the records with run headers (and E_b's logarithmic partials)
-            da.recs = pr->d_druns;
-            da.drecs = pr->d_ddruns;
-            da.drecs_b = pr->d_bdruns;
-            da.t.n_rec = pr->n_druns;
+            da.recs = pr->recs(DEV_DRUNS);
+            da.drecs = (const DRec *)pr->dev[DEV_DDRUNS];
+            da.drecs_b = (const DRecB *)pr->dev[DEV_BDRUNS];
+            da.t.n_rec = rl.n_druns;
             // (these kernels exist for 1 and 4 index spaces: a space the plan does not have counts as dense -- no index row is read for it)
-            da.t.dense_spaces |= 0xfu & ~((1u << pl->n_spaces) - 1u);
+            da.t.dense_spaces |= 0xfu & ~((1u << pl->host.n_spaces) - 1u);
             if (tracing())
                 fprintf(stderr, "[epgx] run: %d records with headers (%d unfolded); %d runs (%d of one repeated record) hold %d records; [0, %d) "
                                 "with one order per lane, [%d, %d) with two\n",
-                        pr->n_druns, pr->n_rec, pr->drun_headers, pr->drun_ident, pr->drun_inside, da.grow1, da.grow1, da.grow2);
+                        rl.n_druns, rl.n_rec, rl.drun_headers, rl.drun_ident, rl.drun_inside, da.grow1, da.grow1, da.grow2);
         }
         switch (c.family) {
-        case FAM_PACKED_DFOLD: e = epgx_launch_packed_dfold(ctx->stream, da, K, pl->n_vars); break;
+        case FAM_PACKED_DFOLD: e = epgx_launch_packed_dfold(ctx->stream, da, K, pl->host.n_vars); break;
         case FAM_DRUN:
             if (c.split3) {
                 // three derivative states of folded runs: the last variable alone (rows shifted by two), then the first two over it
                 DerivArgs last = da;
                 last.signal = da.signal ? da.signal + 2 * da.signal_ld : nullptr;
-                e = epgx_launch_drun(ctx->stream, last, K, pl->n_spaces, 1, pr->drun_code | (int)DRUN_LAST);
-                if (e == hipSuccess) e = epgx_launch_drun(ctx->stream, da, K, pl->n_spaces, 2, pr->drun_code);
+                e = epgx_launch_drun(ctx->stream, last, K, pl->host.n_spaces, 1, rl.drun_code | (int)DRUN_LAST);
+                if (e == hipSuccess) e = epgx_launch_drun(ctx->stream, da, K, pl->host.n_spaces, 2, rl.drun_code);
             } else
-                e = epgx_launch_drun(ctx->stream, da, K, pl->n_spaces, pl->n_vars, pr->drun_code);
+                e = epgx_launch_drun(ctx->stream, da, K, pl->host.n_spaces, pl->host.n_vars, rl.drun_code);
             break;
         case FAM_ROWS_DERIV:
-            if (pl->n_vars == 2) {
-                switch (pl->n_spaces) {
+            if (pl->host.n_vars == 2) {
+                switch (pl->host.n_spaces) {
                 case 0: e = epgx_launch_rows_deriv_v2_nsp0(ctx->stream, da, K); break;
                 case 1: e = epgx_launch_rows_deriv_v2_nsp1(ctx->stream, da, K); break;
                 case 2: e = epgx_launch_rows_deriv_v2_nsp2(ctx->stream, da, K); break;
                 default: e = epgx_launch_rows_deriv_v2_nsp4(ctx->stream, da, K); break;
                 }
             } else {
-                switch (pl->n_spaces) {
+                switch (pl->host.n_spaces) {
                 case 0: e = epgx_launch_rows_deriv_nsp0(ctx->stream, da, K); break;
                 case 1: e = epgx_launch_rows_deriv_nsp1(ctx->stream, da, K); break;
                 case 2: e = epgx_launch_rows_deriv_nsp2(ctx->stream, da, K); break;
@@ -3238,16 +2117,16 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
                 }
             }
             break;
-        case FAM_PACKED_DERIV: e = epgx_launch_packed_deriv(ctx->stream, da, K, pl->n_spaces, pl->n_vars); break;
-        default: e = epgx_launch_deriv(ctx->stream, da, K, pl->n_spaces, pl->n_vars); break;
+        case FAM_PACKED_DERIV: e = epgx_launch_packed_deriv(ctx->stream, da, K, pl->host.n_spaces, pl->host.n_vars); break;
+        default: e = epgx_launch_deriv(ctx->stream, da, K, pl->host.n_spaces, pl->host.n_vars); break;
         }
         if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_run: launch failed: %s", hipGetErrorString(e));
         return EPGX_OK;
     }
     RunArgs a;
     memset(&a, 0, sizeof(a));
-    a.recs = pr->d_recs;
-    a.t.n_rec = pr->n_rec;
+    a.recs = pr->recs(DEV_RECS);
+    a.t.n_rec = rl.n_rec;
     a.coef = pl->d_coef;
     a.t.vidx = pl->d_vidx;
     a.t.vidx_ld = pl->vidx_nvox;
@@ -3258,54 +2137,54 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
     a.t.dens_out = out ? out->dens : nullptr;
     a.signal = signal ? (d2 *)signal + signal_col0 : nullptr;
     a.signal_ld = signal_ld;
-    a.t.use_lds = pr->use_lds ? ((pr->has_gs && K < 1024) ? 3 : 2) : 0;      // (gather shifts at 1024 orders stage Z behind F: gather_shift)
-    a.t.seq_slots = pr->seq_slots ? 1 : 0;
-    a.t.first_slot = pr->first_slot;
+    a.t.use_lds = c.lds_mode;
+    a.t.seq_slots = rl.seq_slots ? 1 : 0;
+    a.t.first_slot = rl.first_slot;
     a.t.vox0 = vox0;
     a.t.dense_spaces = pl->dense_spaces;
-    a.t.write_dens = (pr->has_pd || out != in) ? 1 : 0;
+    a.t.write_dens = (rl.has_pd || out != in) ? 1 : 0;
     // long record lists over per-voxel tables: prefetch (EPGX_PREFETCH=0 disables, for measurements)
-    a.t.prefetch = (knobs().prefetch && !in && pr->n_rec >= 4) ? pr->pf_count : 0;
+    a.t.prefetch = (knobs().prefetch && !in && rl.n_rec >= 4) ? rl.pf_count : 0;
     // a wave of rows_kernel takes ONE voxel group (rounds 1 and 2 gave it four on big grids; with today's kernels one is faster on
     // every workload measured: MRF C3 44.5 / 45.8 ms, MRF with max_nstate = 10 at 16 orders 27.0 / 28.5 ms, spoiled gradient echo
     // 14.5 / 14.7 ms); a wave of rows_grow_kernel two (C2-L 0.672 -> 0.634 ms per launch; four: the same).  EPGX_GPW=n overrides
     a.groups_per_wave = c.family == FAM_ROWS_GROW ? 2 : 1;
     if (c.runs) {   // run-length folded records (get_packed)
-        a.recs = pr->d_runs;
-        a.t.n_rec = pr->n_runs;
+        a.recs = pr->recs(DEV_RUNS);
+        a.t.n_rec = rl.n_runs;
     }
     switch (c.family) {
     case FAM_ROWS_GROW:
-        a.recs = pr->d_grow;
-        a.t.n_rec = pr->n_grow;
+        a.recs = pr->recs(DEV_GROW);
+        a.t.n_rec = rl.n_grow;
         if (tracing())
-            fprintf(stderr, "[epgx] run: %d records: [0, %d) at %d orders per voxel, [%d, %d) at %d, the rest at %d\n", pr->n_grow, pr->grow1,
-                    pr->grow_cap[0], pr->grow1, pr->grow2, pr->grow_cap[1], pr->grow_cap[2]);
-        switch (pl->n_spaces) {
-        case 0: e = epgx_launch_rows_grow_nsp0(ctx->stream, a, pr->grow1, pr->grow2, pr->grow_cap); break;
-        case 1: e = epgx_launch_rows_grow_nsp1(ctx->stream, a, pr->grow1, pr->grow2, pr->grow_cap); break;
-        case 2: e = epgx_launch_rows_grow_nsp2(ctx->stream, a, pr->grow1, pr->grow2, pr->grow_cap); break;
-        default: e = epgx_launch_rows_grow_nsp4(ctx->stream, a, pr->grow1, pr->grow2, pr->grow_cap); break;
+            fprintf(stderr, "[epgx] run: %d records: [0, %d) at %d orders per voxel, [%d, %d) at %d, the rest at %d\n", rl.n_grow, rl.grow1,
+                    rl.grow_cap[0], rl.grow1, rl.grow2, rl.grow_cap[1], rl.grow_cap[2]);
+        switch (pl->host.n_spaces) {
+        case 0: e = epgx_launch_rows_grow_nsp0(ctx->stream, a, rl.grow1, rl.grow2, rl.grow_cap); break;
+        case 1: e = epgx_launch_rows_grow_nsp1(ctx->stream, a, rl.grow1, rl.grow2, rl.grow_cap); break;
+        case 2: e = epgx_launch_rows_grow_nsp2(ctx->stream, a, rl.grow1, rl.grow2, rl.grow_cap); break;
+        default: e = epgx_launch_rows_grow_nsp4(ctx->stream, a, rl.grow1, rl.grow2, rl.grow_cap); break;
         }
         break;
     case FAM_ROWS:
         switch (K / 16) {
-        case 1: e = epgx_launch_rows_r1(ctx->stream, a, pl->n_spaces, c.runs); break;
-        case 2: e = epgx_launch_rows_r2(ctx->stream, a, pl->n_spaces, c.runs); break;
-        case 4: e = epgx_launch_rows_r4(ctx->stream, a, pl->n_spaces, c.runs); break;
-        default: e = epgx_launch_rows_r8(ctx->stream, a, pl->n_spaces, c.runs); break;
+        case 1: e = epgx_launch_rows_r1(ctx->stream, a, pl->host.n_spaces, c.runs); break;
+        case 2: e = epgx_launch_rows_r2(ctx->stream, a, pl->host.n_spaces, c.runs); break;
+        case 4: e = epgx_launch_rows_r4(ctx->stream, a, pl->host.n_spaces, c.runs); break;
+        default: e = epgx_launch_rows_r8(ctx->stream, a, pl->host.n_spaces, c.runs); break;
         }
         break;
     case FAM_RUN_SPLIT:
         if (!c.split_grow) {
-            e = epgx_launch_run_split2048(ctx->stream, a, pl->n_spaces, nullptr, nullptr, 0, 0, 0, 0);
+            e = epgx_launch_run_split2048(ctx->stream, a, pl->host.n_spaces, nullptr, nullptr, 0, 0, 0, 0);
             break;
         }
         {
             // two legs per slab of voxels: records [0, j1) on one wavefront per voxel at 512 orders (run_kernel<8, ..>: the growing kernel
             // cannot hand its state on -- epgx_cgrow.hip), its state [3][512] + density through a scratch buffer (24 KiB per voxel: slabs
             // of at most 8 GiB), then the records [j1, n_rec) on four wavefronts per voxel
-            const int j1 = pr->cgrow[3], j2 = pr->cgrow[4], j3 = pr->cgrow[5];
+            const int j1 = rl.cgrow[3], j2 = rl.cgrow[4], j3 = rl.cgrow[5];
             const int64_t per_voxel = (int64_t)3 * 512 * sizeof(d2) + sizeof(double);
             int64_t slab = std::min<int64_t>((nvox + 3) & ~(int64_t)3, std::max<int64_t>(4, (((int64_t)8 << 30) / per_voxel) & ~(int64_t)3));
             if (knobs().slab_voxels > 0) slab = std::min<int64_t>(slab, (knobs().slab_voxels + 3) & ~3);
@@ -3316,7 +2195,7 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
             double *dn = (double *)((char *)scratch + slab * 3 * 512 * sizeof(d2));
             if (tracing())
                 fprintf(stderr, "[epgx] run: %d records: [0, %d) on one wavefront per voxel, the rest on four (parts 2 and 3 join at %d and %d); slabs of "
-                                "%lld voxels\n", pr->n_rec, j1, j2, j3, (long long)slab);
+                                "%lld voxels\n", rl.n_rec, j1, j2, j3, (long long)slab);
             for (int64_t c0 = 0; c0 < nvox && e == hipSuccess; c0 += slab) {
                 RunArgs s = a;
                 s.nvox = std::min(slab, nvox - c0);
@@ -3330,30 +2209,30 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
                 leg.out = st;
                 leg.t.dens_out = dn;
                 leg.t.write_dens = 1;
-                e = epgx_launch_run_m8(ctx->stream, leg, pl->n_spaces);
-                if (e == hipSuccess && j1 < pr->n_rec)
-                    e = epgx_launch_run_split2048(ctx->stream, s, pl->n_spaces, st, dn, j1, j2, j3, pr->first_slot + pr->cgrow_adc3);
+                e = epgx_launch_run_m8(ctx->stream, leg, pl->host.n_spaces);
+                if (e == hipSuccess && j1 < rl.n_rec)
+                    e = epgx_launch_run_split2048(ctx->stream, s, pl->host.n_spaces, st, dn, j1, j2, j3, rl.first_slot + rl.cgrow_adc3);
             }
             dev_free(ctx, scratch);
         }
         break;
-    case FAM_RUN_CONTIG: e = epgx_launch_run_contig(ctx->stream, a, K, pl->n_spaces); break;
+    case FAM_RUN_CONTIG: e = epgx_launch_run_contig(ctx->stream, a, K, pl->host.n_spaces); break;
     case FAM_RUN_CONTIG_GROW:
         if (tracing())
             fprintf(stderr, "[epgx] run: %d records: [0, %d) at 64 orders per voxel, [%d, %d) at 128, [%d, %d) at 256, [%d, %d) at 512, the rest at %d\n",
-                    pr->n_rec, pr->cgrow[0], pr->cgrow[0], pr->cgrow[1], pr->cgrow[1], pr->cgrow[2], pr->cgrow[2], pr->cgrow[3], K);
+                    rl.n_rec, rl.cgrow[0], rl.cgrow[0], rl.cgrow[1], rl.cgrow[1], rl.cgrow[2], rl.cgrow[2], rl.cgrow[3], K);
         {
-            const int g4[4] = {pr->cgrow[0], pr->cgrow[1], pr->cgrow[2], pr->cgrow[3]};
-            e = epgx_launch_run_contig_grow(ctx->stream, a, K, pl->n_spaces, g4);
+            const int g4[4] = {rl.cgrow[0], rl.cgrow[1], rl.cgrow[2], rl.cgrow[3]};
+            e = epgx_launch_run_contig_grow(ctx->stream, a, K, pl->host.n_spaces, g4);
         }
         break;
     default:
         switch (K / 64) {
-        case 1: e = epgx_launch_run_m1(ctx->stream, a, pl->n_spaces); break;
-        case 2: e = epgx_launch_run_m2(ctx->stream, a, pl->n_spaces); break;
-        case 4: e = epgx_launch_run_m4(ctx->stream, a, pl->n_spaces); break;
-        case 8: e = epgx_launch_run_m8(ctx->stream, a, pl->n_spaces); break;
-        default: e = epgx_launch_run_m16(ctx->stream, a, pl->n_spaces); break;
+        case 1: e = epgx_launch_run_m1(ctx->stream, a, pl->host.n_spaces); break;
+        case 2: e = epgx_launch_run_m2(ctx->stream, a, pl->host.n_spaces); break;
+        case 4: e = epgx_launch_run_m4(ctx->stream, a, pl->host.n_spaces); break;
+        case 8: e = epgx_launch_run_m8(ctx->stream, a, pl->host.n_spaces); break;
+        default: e = epgx_launch_run_m16(ctx->stream, a, pl->host.n_spaces); break;
         }
         break;
     }
@@ -3375,28 +2254,7 @@ extern "C" int epgx_kernel_for(epgx_ctx *ctx, const epgx_plan *plan, int32_t op_
 }
 
 // ------------------------------------------------------------------------------ tiled runs: state matrices of any length
-// (epgx_tiled.hip).  The plan's records are packed as for any capacity, with every truncation explicit (no capacity drops
-// orders here), then
-//   * a shift by 2 .. H orders becomes |n| records of S(+-1) (the same moves, the truncation and the probe on the last);
-//   * a shift by more than H becomes a step of its own (tiled_shift_kernel): the stages in front of it stay a record, the
-//     probe behind it becomes one;
-// and the list is cut into blocks whose shifts add up to at most H.  `top` = the highest order that can hold anything, as in
-// get_packed plus truncations and resets; a launch covers the tiles up to the top after its block, and at least the tiles the
-// launch before the previous one wrote into the same buffer (so no tile of the output buffer keeps a stale value).
-struct TiledStep {
-    int rec0 = 0, rec1 = 0;    // block: records [rec0, rec1); a shift step has none
-    int shift = 0;             // shift step: n, |n| > H
-    int kmax = INT32_MAX;      // shift step: truncation above kmax
-    int tiles = 0;             // tiles the launch covers
-    int top = 0;               // highest order that can hold anything after the step
-};
-struct TiledSchedule {
-    std::vector<Rec> recs;
-    std::vector<TiledStep> steps;
-    int peak = 0, n_shift = 0;
-    int64_t tile_launches = 0;
-    bool has_adc = false;
-};
+// (epgx_tiled.hip; the schedule -- blocks and shift steps -- comes from tiled_schedule, epgx_planner.cpp)
 
 static void tiled_knobs(int &M, int &H) {   // EPGX_TILED_M=16: 16 orders per lane, halo 64 (measurements)
     static const int m = env_int("EPGX_TILED_M", 8);
@@ -3404,131 +2262,14 @@ static void tiled_knobs(int &M, int &H) {   // EPGX_TILED_M=16: 16 orders per la
     H = M == 16 ? 64 : 32;
 }
 
-static Rec with_leaf(Rec r) {
-    r.flags &= 0xffffffu;
-    r.flags |= record_leaf<false>(r.flags, r.shift) << 24;
-    return r;
-}
-
-static int tiled_schedule(const epgx_plan *pl, int Kbuf, int top0, int M, int H, TiledSchedule &ts) {
-    std::vector<Rec> packed;
-    std::vector<DRec> drecs;
-    std::vector<ELog> elog;
-    bool use_lds = false;
-    const int n_ops = (int)pl->ops.size();
-    pack_records(pl->ops, pl->zero_pattern, pl->dops, pl->dpattern, 0, n_ops, 1 << 30, pl->fold, (uint32_t)(pl->n_pool * 8), packed, drecs,
-                 use_lds, ts.has_adc, &pl->log_of, &elog);
-    const int W = 64 * M - 2 * H;
-    struct Item { Rec r; int big; };    // big: 0, or the shift of a step of its own
-    std::vector<Item> items;
-    const uint32_t probe = F_ADC | F_ADC_Z;
-    for (const Rec &r : packed) {
-        const int n = ((r.flags & F_S) && !(r.flags & F_FOLD)) ? r.shift : 1;
-        if (!(r.flags & F_S) || std::abs(n) <= 1) {
-            items.push_back({r, 0});
-            continue;
-        }
-        Rec head = r;
-        head.flags &= ~(F_TRUNC | probe);
-        if (std::abs(n) > H) {
-            head.flags &= ~F_S;
-            head.shift = 0;
-            if (head.flags & 0xffffffu) items.push_back({with_leaf(head), 0});
-            Rec step;
-            memset(&step, 0, sizeof(step));
-            step.flags = r.flags & F_TRUNC;
-            step.kmax = r.kmax;
-            items.push_back({step, n});
-        } else {
-            head.shift = n > 0 ? 1 : -1;
-            items.push_back({with_leaf(head), 0});
-            for (int j = 1; j < std::abs(n); ++j) {
-                Rec one;
-                memset(&one, 0, sizeof(one));
-                one.flags = F_S | (j + 1 == std::abs(n) ? (r.flags & F_TRUNC) : 0u);
-                one.shift = n > 0 ? 1 : -1;
-                one.kmax = r.kmax;
-                items.push_back({with_leaf(one), 0});
-            }
-            if (!(r.flags & probe)) continue;
-            Rec &last = items.back().r;
-            last.flags |= r.flags & probe;
-            last.slot = r.slot;
-            last = with_leaf(last);
-            continue;
-        }
-        if (r.flags & probe) {
-            Rec adc;
-            memset(&adc, 0, sizeof(adc));
-            adc.flags = r.flags & probe;
-            adc.slot = r.slot;
-            items.push_back({with_leaf(adc), 0});
-        }
-    }
-    ts.recs.clear();
-    ts.steps.clear();
-    ts.peak = top0;
-    ts.n_shift = 0;
-    ts.tile_launches = 0;
-    int top = top0, units = 0;
-    int cov[2] = {top0 / W + 1, 0};   // tiles the latest step wrote into buffer 0 / 1 (the start state is in buffer 0)
-    TiledStep cur;
-    auto close = [&](TiledStep st) {
-        const int buf = (int)(ts.steps.size() + 1) & 1;      // the buffer this step writes
-        st.top = top;
-        st.tiles = std::max(top / W + 1, cov[buf]);
-        cov[buf] = st.tiles;
-        ts.tile_launches += st.tiles;
-        ts.steps.push_back(st);
-    };
-    for (const Item &it : items) {
-        const Rec &r = it.r;
-        if (it.big) {
-            if (cur.rec1 > cur.rec0) close(cur);
-            TiledStep st;
-            st.shift = it.big;
-            top += std::abs(it.big);
-            if (r.flags & F_TRUNC) {
-                st.kmax = r.kmax;
-                top = std::min(top, r.kmax);
-            }
-            ts.peak = std::max(ts.peak, top);
-            close(st);
-            ++ts.n_shift;
-            cur = TiledStep();
-            cur.rec0 = cur.rec1 = (int)ts.recs.size();
-            units = 0;
-            continue;
-        }
-        const int u = ((r.flags & F_S0) ? 1 : 0) + ((r.flags & F_S) ? 1 : 0);
-        if (units + u > H && cur.rec1 > cur.rec0) {
-            close(cur);
-            cur = TiledStep();
-            cur.rec0 = cur.rec1 = (int)ts.recs.size();
-            units = 0;
-        }
-        units += u;
-        if (r.flags & (F_RESET | F_PD_RESET)) top = 0;
-        if (r.flags & F_S0) top += 1;
-        if (r.flags & F_S) top += 1;
-        if (r.flags & F_TRUNC) top = std::min(top, r.kmax);
-        ts.peak = std::max(ts.peak, top);
-        ts.recs.push_back(r);
-        cur.rec1 = (int)ts.recs.size();
-    }
-    if (cur.rec1 > cur.rec0) close(cur);
-    if (ts.peak >= Kbuf)
-        return fail(EPGX_ERR_INVALID, "epgx_run_tiled: the plan populates orders up to %d, Kbuf=%d", ts.peak, Kbuf);
-    return EPGX_OK;
-}
 
 static int tiled_check(epgx_ctx *ctx, const epgx_plan *pl, int32_t Kbuf, const char *who) {
     if (!ctx || !pl) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
     if (pl->ctx != ctx) return fail(EPGX_ERR_INVALID, "%s: plan belongs to another context", who);
     if (Kbuf < 64 || Kbuf % 64 != 0 || Kbuf > (1 << 24)) return fail(EPGX_ERR_INVALID, "%s: Kbuf=%d is not a multiple of 64 in [64, 2^24]", who, Kbuf);
-    if (pl->n_vars > 0) return fail(EPGX_ERR_UNSUPPORTED, "%s: plans with derivative states run at K <= 1024 (epgx_run)", who);
-    for (size_t i = 0; i < pl->ops.size(); ++i) {
-        const int oc = pl->ops[i].opcode;
+    if (pl->host.n_vars > 0) return fail(EPGX_ERR_UNSUPPORTED, "%s: plans with derivative states run at K <= 1024 (epgx_run)", who);
+    for (size_t i = 0; i < pl->host.ops.size(); ++i) {
+        const int oc = pl->host.ops[i].opcode;
         if (oc == EPGX_OP_X || oc == EPGX_OP_GS || oc == EPGX_OP_D)
             return fail(EPGX_ERR_UNSUPPORTED, "%s: operator %zu: exchange, gather shifts and diffusion run at K <= 1024 (epgx_run)", who, i);
     }
@@ -3542,7 +2283,7 @@ extern "C" int epgx_tiled_info(epgx_ctx *ctx, const epgx_plan *plan, int32_t Kbu
     int M, H;
     tiled_knobs(M, H);
     TiledSchedule ts;
-    if (int rc = tiled_schedule(plan, Kbuf, top0, M, H, ts)) return rc;
+    if (int rc = tiled_schedule(plan->host, Kbuf, top0, M, H, knobs(), ts)) return rc;
     const int nb = (int)ts.steps.size() - ts.n_shift;
     if (blocks) *blocks = nb;
     if (shifts) *shifts = ts.n_shift;
@@ -3574,7 +2315,7 @@ extern "C" int epgx_run_tiled(epgx_ctx *ctx, const epgx_plan *plan_c, int64_t vo
     int M, H;
     tiled_knobs(M, H);
     TiledSchedule ts;
-    if (int rc = tiled_schedule(pl, Kbuf, in ? in->K - 1 : 0, M, H, ts)) return rc;
+    if (int rc = tiled_schedule(pl->host, Kbuf, in ? in->K - 1 : 0, M, H, knobs(), ts)) return rc;
     if (ts.has_adc) {
         if (!signal) return fail(EPGX_ERR_INVALID, "epgx_run_tiled: the plan contains an ADC but signal is NULL");
         if (signal_col0 < 0 || signal_col0 + nvox > signal_ld)
@@ -3647,7 +2388,7 @@ extern "C" int epgx_run_tiled(epgx_ctx *ctx, const epgx_plan *plan_c, int64_t vo
             a.t.vidx_ld = pl->vidx_nvox;
             a.t.vox0 = vox0 + c0;
             a.t.dense_spaces = pl->dense_spaces;
-            e = epgx_launch_tiled(ctx->stream, a, M, H, pl->n_spaces);
+            e = epgx_launch_tiled(ctx->stream, a, M, H, pl->host.n_spaces);
         }
     }
     dev_free(ctx, mem);
@@ -4235,7 +2976,7 @@ extern "C" int epgx_run_to_host(epgx_ctx *ctx, const epgx_plan *plan, int32_t K,
     if (int rc = ensure_copy_stream(ctx, n_slabs)) return rc;
     const bool pinned = n_adc > 0 && host_is_pinned((const char *)signal_host + rec * (size_t)host_col0,
                                                     rec * ((size_t)(n_adc - 1) * (size_t)host_ld + (size_t)nvox));
-    const int n_ops = (int)plan->ops.size();
+    const int n_ops = (int)plan->host.ops.size();
     int rc = EPGX_OK;
     // complex64 destination: every slab is narrowed (behind its kernel, on the same stream) into scratch [n_adc][dev_ld] float2
     // of the context's block cache; the copies then move 8 bytes per record

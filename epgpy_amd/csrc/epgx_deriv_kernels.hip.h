@@ -16,32 +16,7 @@
 
 namespace epgx {
 
-constexpr int MAX_VARS = 3;
-
-struct DRec {                 // 64 bytes = two s_load_dwordx8
-    uint32_t t_off[MAX_VARS]; // byte offset of d(T stage)/dv, 10 doubles per entry
-    uint32_t t_ix[MAX_VARS];
-    uint32_t present;         // bit v: T partial for variable v; bit 4 + v: E partial; bit 16 + v: the T partial is a REAL matrix;
-                              // bit 8 + v: the T partial has the phi = 0 zero pattern (Im m00 = Im m01 =
-                              // Re m02 = Re m20 = 0 for every entry); bit 12 + v: the E partial is real
-    uint32_t pad0;
-    uint32_t e_off[MAX_VARS]; // byte offset of d(E stage)/dv, 4 doubles per entry
-    uint32_t e_ix[MAX_VARS];
-    uint32_t pad1[2];
-};
-static_assert(sizeof(DRec) == 64, "DRec must be two s_load_dwordx8");
-
-// records folded at run time in derivative plans (drun_kernel, DRUN_FOLD): E_a . T . E_b as ONE stage.  DRec then holds, per
-// variable, the rotation's partial (t_off / t_ix, folded like the rotation) and E_a's table of logarithmic partials (e_off /
-// e_ix: two doubles per entry, logtab_kernel); this parallel record holds E_b's.  One s_load_dwordx8.
-struct DRecB {
-    uint32_t off[MAX_VARS];   // byte offset of E_b's (wT, wL) table for variable v; tables that do not exist point at zeros
-    uint32_t ix[MAX_VARS];
-    uint32_t logs;            // bit v: E_a's wT != 0 somewhere; 4 + v: E_a's wL; 8 + v: E_b's wT; 12 + v: E_b's wL
-    uint32_t pad;
-};
-static_assert(sizeof(DRecB) == 32, "DRecB must be one s_load_dwordx8");
-
+// (DRec, DRecB and the shape codes of runs, drun_shape / dfold_shape: epgx_records.h)
 struct DerivArgs {
     const d2 *in;             // [nvox][3][K] initial state, or null (equilibrium); derivative states start at 0
     const double *dens_in;    // [nvox] or null (1.0)
@@ -59,58 +34,6 @@ struct DerivArgs {
     int32_t grow1, grow2;     // drun_kernel, fused echoes from equilibrium: records [0, grow1) run with one order per lane, [grow1,
                               // grow2) with two, the rest with four -- while the state matrix is that short (0, 0: four throughout)
 };
-
-// ---- runs of same-shape records in derivative plans (drun_kernel, epgx_drun_kernels.hip.h): what the host (get_packed) and the
-// kernel have to agree on
-constexpr uint32_t LEAF_DRUN = 252u;   // header of a run of same-shape records in a derivative plan (drun_kernel only)
-// shape code of a run (low bits of the header's flags word)
-enum : uint32_t {
-    DRUN_KIND = 3u,        // bits 0..1: rotation chains -- 0 general (T), 1 phi = 0 pattern (TX), 2 real matrix (TY)
-    DRUN_PK = 3u << 2,     // bits 2..3: chains of the partial accumulation -- 0 general symmetric 3x3, 1 TX pattern, 2 real
-    DRUN_HS0 = 1u << 4,    // leading S(+1)
-    DRUN_HS = 1u << 5,     // trailing S(+1)
-    DRUN_IDENT = 1u << 6,  // every record of the run refers to the same table entries (an echo train): lines loaded once
-    DRUN_FOLD = 1u << 7,   // records folded at run time: E_a . T . E_b with logarithmic relaxation partials (part of the shape code)
-    DRUN_LAST = 1u << 9,   // launcher flag (not part of a header's code): the one-state kernel propagates the plan's THIRD variable
-    DRUN_LOGD = 1u << 8,   // fused-echo records (table from the host's fusion) whose relaxation-only partials take the logarithmic
-                           // route instead of their generated partial tables (part of the shape code)
-};
-
-// shape code of a record that can be part of a run (flags without the leaf byte), or -1.  `present`: DRec.present, n_vars: V.
-// Shared by the host (get_packed) and nothing else: kept next to the kernel that has to agree with it.
-__host__ __device__ inline int drun_shape(uint32_t f, int shift, uint32_t present, int n_vars) {
-    const uint32_t need = F_T | F_T0 | F_ADC;
-    const uint32_t other = F_MAT | F_E | F_ADC_Z | F_SPOIL | F_RESET | F_PD | F_PD_RESET | F_D | F_GS | F_MAT0 | F_FOLD | F_FOLD_SPOIL;
-    if ((f & need) != need || (f & other)) return -1;
-    if ((f & F_S) && shift != 1) return -1;
-    const int kind = (f & F_TX) ? 1 : ((f & F_TY) ? 2 : 0);
-    // the accumulation runs the rotation's own pattern: every present partial must have it (the partial of a rotation about x
-    // or y w.r.t. the flip angle or a relaxation time has; w.r.t. the phase it has not: the flag-tested body takes those)
-    for (int v = 0; v < n_vars; ++v) {
-        if (!(present & (1u << v))) continue;
-        const int pat = (present & (256u << v)) ? 1 : ((present & (65536u << v)) ? 2 : 0);
-        if (kind != 0 && pat != kind) return -1;
-    }
-    return kind | (kind << 2) | ((f & F_S0) ? 16 : 0) | ((f & F_S) ? 32 : 0);
-}
-
-#ifndef EPGX_DF3_SPLIT
-#define EPGX_DF3_SPLIT 1      // three derivative states of a run folded at run time: two launches (epgx_run: the last variable, then the
-#endif                        // first two); the host then folds whatever the number of rotation partials (get_packed)
-// the same for a record folded at run time (the host's fold pass in get_packed builds them)
-// `spoiled`: a spoiler folded into the record (F_FOLD_SPOIL) is allowed -- the loop at 16 / 32 orders handles it, drun_kernel not
-__host__ __device__ inline int dfold_shape(uint32_t f, uint32_t present, int n_vars, bool spoiled = false) {
-    const uint32_t need = F_T | F_T0 | F_FOLD | F_ADC;
-    const uint32_t other = F_MAT | F_E | F_ADC_Z | F_SPOIL | F_RESET | F_PD | F_PD_RESET | F_D | F_GS | F_MAT0 | (spoiled ? 0u : (uint32_t)F_FOLD_SPOIL);
-    if ((f & need) != need || (f & other)) return -1;
-    const int kind = (f & F_TX) ? 1 : ((f & F_TY) ? 2 : 0);
-    for (int v = 0; v < n_vars; ++v) {
-        if (!(present & (1u << v))) continue;
-        const int pat = (present & (256u << v)) ? 1 : ((present & (65536u << v)) ? 2 : 0);
-        if (kind != 0 && pat != kind) return -1;
-    }
-    return kind | (kind << 2) | ((f & F_S0) ? 16 : 0) | ((f & F_S) ? 32 : 0) | (int)DRUN_FOLD;
-}
 
 __device__ __forceinline__ DRec load_drec(const EPGX_CONSTANT u32x8 *drecs, int i) {
     const u32x8 a = drecs[2 * i], b = drecs[2 * i + 1];

@@ -328,7 +328,7 @@ __device__ __forceinline__ void drun_loop(State<4> &s, State<4> (&d)[V], int cou
 
 // ------------------------------------------------------------------------------------------------ runs folded at run time
 // A repetition of an MRF / SSFP train over a (T1, T2, B1) grid -- [T(a_n B1)  E(TE)  ADC  E(TR_n - TE)  S(+1)] -- cannot be
-// fused on the host (the product table would be the whole grid per pulse).  The host's fold pass (get_packed) turns it
+// fused on the host (the product table would be the whole grid per pulse).  The host's fold pass (build_range, epgx_planner.cpp) turns it
 // into ONE stage  M = E_a . T . E_b  per repetition whose line every wavefront computes for its voxels (fold_value: the
 // plain kernels' run-time fold), and the derivative states follow through
 //     dS_v  <-  M_lin (dS_v + wb_v o (S - eq))  +  (E_a . dT/dv . E_b) S  +  wa_v o (S' - eq)
@@ -595,7 +595,7 @@ __device__ __forceinline__ void dfold_loop(State<R> &s, State<R> (&d)[V], int co
 // (SHAPE = the header's code without DRUN_IDENT; the accumulation runs the rotation's pattern: drun_shape): with all twelve
 // shapes in one kernel the register allocator spilled inside every loop (4 480 spill instructions at three derivative
 // states), and a spilled double costs this VALU-bound loop a memory round trip.  The host emits headers for the dominant
-// shape of a launch only (get_packed).
+// shape of a launch only (build_range).
 #ifndef EPGX_DRUN_WAVES
 #define EPGX_DRUN_WAVES(V) ((V) == 1 ? 3 : 2)     // waves per SIMD the kernel is compiled for
 #endif
@@ -653,7 +653,7 @@ __device__ __forceinline__ void drun_walk(State<R> &s, State<R> (&d)[V], int i0,
 
 // one pass of a wavefront over the records for its four voxels: the state and the V derivative states of variables V0 ..
 // V0 + V - 1 of the plan, signal rows behind `sig_base`.  A train of fused echoes from equilibrium grows its state matrix by two
-// orders per echo: the host cuts the run list where the populated orders outgrow 16 and 32 (a.grow1, a.grow2; get_packed), and
+// orders per echo: the host cuts the run list where the populated orders outgrow 16 and 32 (a.grow1, a.grow2; build_range), and
 // the wave walks those ranges with one and two orders per lane before it settles at four -- every state re-laid out between the
 // phases (rows_widen), the same loops at every R (cf. rows_grow_kernel; the reference grows its state matrix the same way).
 template <int NSP, int V, int SHAPE, int V0>

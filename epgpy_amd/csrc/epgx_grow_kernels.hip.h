@@ -5,7 +5,7 @@
 // matrix is resized as it grows, `max_nstate` only caps it) -- at echo n of a spin-echo train 2 n + 1 of the 64 orders exist.
 // rows_kernel<., 4, .> computes all 64 from the first record on: over a 20-echo train 80 order slots per lane where 43 hold
 // anything.  Here the host cuts the (run-length folded) record list where the populated orders outgrow 16 and 32
-// (grow_split, epgx_api.hip), and a wave walks
+// (grow_split, epgx_planner.cpp), and a wave walks
 //      records [0, n1)  with r0 orders per lane   (1: the rows code at R = 1, 16 orders),
 //      records [n1, n2) with r1                   (1 or 2: 32 orders),
 //      the rest         with r2                   (1, 2 or 4: 64 orders),
@@ -16,7 +16,7 @@
 // those of rows_kernel<., 4, .> bit for bit.
 //
 // A range runs BELOW 16 / 32 / 64 orders where the populated orders no longer fit but the orders that can still reach a probe
-// do (grow_reach, epgx_api.hip).  This kernel writes no state: its outputs are the order-0 probes, and a coefficient of order k
+// do (grow_reach, epgx_planner.cpp).  This kernel writes no state: its outputs are the order-0 probes, and a coefficient of order k
 // gets to order 0 through k shifts and through nothing else.  With `rem` shifts left before the last probe the orders above
 // `rem` are dead; the host gives a range C orders only if, at every record of it, min(highest populated order, rem) <= C - 1.
 // Narrowing drops dead orders only.  Behind it the zero that a shift feeds in at the top lane (row_shr / row_shl) stands for

@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/epgx.h"
+#include "epgx_records.h"   // the fused record, its flags and leaf numbers (shared with the host's planner)
 
 namespace epgx {
 
@@ -50,60 +51,6 @@ typedef const EPGX_CONSTANT int32_t *const_i32_t;
 typedef double f64x8 __attribute__((ext_vector_type(8), aligned(8)));
 typedef double f64x4 __attribute__((ext_vector_type(4), aligned(8)));
 typedef double f64x2 __attribute__((ext_vector_type(2), aligned(8)));
-
-// ---------------------------------------------------------------- fused record (32 bytes)
-enum : uint32_t {
-    F_T = 1u << 0,       // symmetric 3x3 with real m00 (8 coefficients)
-    F_MAT = 1u << 1,     // general symmetric 3x3 (9 coefficients, padded to 10)
-    F_E = 1u << 2,       // diagonal (4 coefficients)
-    F_S = 1u << 3,       // shift by `shift`
-    F_TRUNC = 1u << 4,   // zero orders above `kmax` after the shift
-    F_ADC = 1u << 5,     // record F0 ...
-    F_ADC_Z = 1u << 6,   // ... or Z0
-    F_SPOIL = 1u << 7,
-    F_RESET = 1u << 8,
-    F_PD = 1u << 9,      // density <- coefficient (uses the E slot's table reference)
-    F_PD_RESET = 1u << 10,
-    F_FOLD_SPOIL = 1u << 11,  // with F_FOLD: a spoiler stood right in front of the rotation -- it is part of the fold (the F columns
-                         // of E_b count as zero: T only sees Z), so a spoiled repetition runs a straight-line body
-    F_TX = 1u << 12,     // with F_T: every entry has Im m01 = Re m02 = Re m20 = 0 exactly (phi = 0)
-    F_ER = 1u << 13,     // with F_E: every entry has Im e0 = 0 exactly (no precession, g = 0)
-    F_D = 1u << 14,      // per-order real diagonal (diffusion): table entry [3][K] doubles (F, mirrored F, Z)
-    F_GS = 1u << 15,     // host-planned gather shift (n-D integer shift): int32 table [3][K]
-    F_MAT0 = 1u << 16,   // with F_MAT: constant term (o0, conj o0, o2) * density on the k = 0 order
-    F_T0 = 1u << 17,     // with F_T: the same constant term, stored after the 8 coefficients of T
-                         // (with F_TX: Re o0 = 0 exactly as well)
-    F_S0 = 1u << 18,     // shift by +1 (no truncation) BEFORE the T stage
-    F_TY = 1u << 19,     // with F_T: every entry has Im m01 = Im m02 = Im m20 (= Im o0) = 0 exactly (phi = +-90: a real matrix);
-                         // rows_kernel runs shorter chains, the other kernels the plain ones (same bits: the products are zero)
-    F_FOLD = 1u << 20,   // with F_T | F_T0: the rotation's table holds a plain T (8 coefficients); the record's effective
-                         // operator is  E_a . T . E_b  with two precession-free relaxations folded in AT RUN TIME, per voxel
-                         // (fold_T below): rows scaled by E_a, columns by E_b, recoveries -> constant term.  e_off / e_ix
-                         // name E_a's table (the record has no E stage of its own), the `shift` word holds the BYTE OFFSET
-                         // of E_b's table (a shift stage of such a record is always +1), bits 21..23 E_b's geometry:
-    F_FOLD_BSPACE = 3u << 21,   //   index space of E_b's table
-    F_FOLD_BVOX = 1u << 23,     //   E_b's table has one entry per index (else one entry for all voxels)
-                         // A relaxation that is missing on one side is the identity entry {1, 0, 1, 0} kept behind the pool.
-    // bits 24..31: number of the straight-line leaf for this record (leaf_id), 255 = generic
-};
-// table geometry word (entry bytes | index space << 24) of a folded record's E_b
-__host__ __device__ inline uint32_t fold_b_ix(uint32_t flags) {
-    return (flags & F_FOLD_BVOX) ? (32u | (((flags & F_FOLD_BSPACE) >> 21) << 24)) : 0u;
-}
-constexpr int32_t GS_ZERO = -1;          // gather source: nothing (zero)
-constexpr int32_t GS_CONJ = 1 << 30;     // gather source: conjugate of the partner array (A <-> B)
-
-struct Rec {
-    uint32_t flags;
-    int32_t shift;
-    int32_t kmax;
-    int32_t slot;
-    uint32_t t_off;  // byte offset of the T/MAT table in the pool
-    uint32_t e_off;  // byte offset of the E (or PD) table
-    uint32_t t_ix;   // bits 0..23: bytes per table entry (0 = same entry for every voxel), bits 24..25: index space
-    uint32_t e_ix;
-};
-static_assert(sizeof(Rec) == 32, "Rec must be one s_load_dwordx8");
 
 // Kernel parameters.  The eight that the prologue needs first are individual arguments (16 dwords:
 // with -amdgpu-kernarg-preload-count=16 they arrive in SGPRs at wave launch, so the state loads
@@ -855,35 +802,7 @@ __device__ __forceinline__ void fast_record(State<M> &s, const Rec &r, const_f64
 // 2 x 40 scalar instructions in front of the leaves at its end -- the MRF records sat there.)
 // Every leaf ends with a distinct empty asm so that the optimiser cannot sink the leaves' common
 // tails into shared blocks (which turns the control flow into a maze of flag registers).
-// TK: 0 none, 1 T, 2 TX, 3 T + constant term, 4 TX + constant term;  EK: 0 none, 1 E, 2 ER
-constexpr uint32_t LEAF_NONE = 255u;
-constexpr uint32_t LEAF_PAIR = 254u;   // header of a run of record PAIRS (rows_kernel<.., RUNS> only: rows_pair_run)
-constexpr uint32_t LEAF_SINGLE = 253u; // header of a run of folded records of one shape (rows_kernel<.., RUNS> only: rows_single_run)
-__host__ __device__ constexpr uint32_t leaf_id(int TK, int EK, bool HS, bool HA, bool HS0) {
-    return (uint32_t)(TK + 5 * (EK + 3 * ((HS ? 1 : 0) + 2 * ((HA ? 1 : 0) + 2 * (HS0 ? 1 : 0)))));
-}
-// which (TK, EK, HS, HA, HS0) combinations have a leaf
-__host__ __device__ constexpr bool leaf_exists(int TK, int EK, bool HS, bool HA, bool HS0) {
-    if (HS0) return TK >= 1 && EK == 0;                  // leading shift: rotation (+ constant), no E
-    if (TK >= 3) return EK == 0;                         // constant term: no E
-    if (TK == 0 && EK == 0) return HS || HA;             // S / ADC only
-    return true;
-}
-// leaf of a packed record (flags without the id), or LEAF_NONE.  The host stores record_leaf<false>: a
-// record that truncates after its shift is a generic record for run_kernel; rows_kernel, whose leaves
-// handle the truncation, recomputes the number with WITH_TRUNC = true for the records marked LEAF_NONE.
-template <bool WITH_TRUNC>
-__host__ __device__ inline uint32_t record_leaf(uint32_t f, int shift) {
-    const uint32_t slow = F_MAT | (WITH_TRUNC ? 0u : (uint32_t)F_TRUNC) | F_ADC_Z | F_SPOIL | F_RESET | F_PD | F_PD_RESET | F_D |
-                          F_GS | F_MAT0;
-    if ((f & slow) || ((f & F_S) && !(f & F_FOLD) && shift != 1)) return LEAF_NONE;   // (folded records: the shift word is E_b's table)
-    const int TK = !(f & F_T) ? 0 : ((f & F_T0) ? ((f & F_TX) ? 4 : 3) : ((f & F_TX) ? 2 : 1));
-    const int EK = !(f & F_E) ? 0 : ((f & F_ER) ? 2 : 1);
-    const bool HS = f & F_S, HA = f & F_ADC, HS0 = f & F_S0;
-    if ((f & F_T0) && !(f & F_T)) return LEAF_NONE;
-    if (!leaf_exists(TK, EK, HS, HA, HS0)) return LEAF_NONE;
-    return leaf_id(TK, EK, HS, HA, HS0);
-}
+// (leaf_id, record_leaf and the LEAF_* numbers: epgx_records.h)
 
 #ifndef EPGX_LEAF_MAX_M
 #define EPGX_LEAF_MAX_M 8   // orders per lane up to which run_kernel instantiates the straight-line leaves (K <= 512)

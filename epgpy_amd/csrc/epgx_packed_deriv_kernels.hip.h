@@ -155,7 +155,7 @@ __device__ __forceinline__ void pd_generic_record(State<1> &s, State<1> (&ds)[V]
 }
 
 // A run of `count` repetitions folded at run time (E_a . T . E_b as ONE stage, logarithmic relaxation partials: the host's fold
-// pass in get_packed, the mathematics in epgx_drun_kernels.hip.h) with one order per lane: a rotation writes new registers
+// pass in build_range, the mathematics in epgx_drun_kernels.hip.h) with one order per lane: a rotation writes new registers
 // anyway, so there are no slots to rotate and ONE loop serves every shape -- the stages of a record are wave-uniform flag
 // tests.  A repetition  [T E ADC] [E S]  is one record with one set of fetches instead of two records with a relaxation stage
 // over every state each; the next record's lines are in flight while a record computes.
@@ -389,7 +389,7 @@ __global__ void __launch_bounds__(256, 4) packed_deriv_kernel(const DerivArgs a)
 }
 
 
-// ---- the kernel for plans whose records are mostly runs of folded repetitions (get_packed puts headers in front of them):
+// ---- the kernel for plans whose records are mostly runs of folded repetitions (build_range puts headers in front of them):
 // the runs through pdfold_loop, everything else a flag-tested record at a time.  Its own kernel: packed_deriv_kernel with its
 // fifty straight-line leaves sits at the 128-register budget already (the loop added there spilled 160 registers).
 template <int NSP, int V, int KP>

@@ -445,7 +445,10 @@ int epgx_state_merge(epgx_ctx *ctx, epgx_state *dst, const epgx_state *src, int3
  * With in = out = NULL the state never leaves registers (state-resident mode); calling it once
  * per echo with in = out streams the state through HBM once per call (per-timestep mode).
  * State-resident launches from equilibrium at K >= 256 whose records mostly run while the state matrix is still short (every
- * shift adds one order: epgpy/shift.py:86,98) walk them with 1, 2, 4 .. K / 64 orders per lane -- the same bits.
+ * shift adds one order: epgpy/shift.py:86,98) walk them with 1, 2, 4 .. K / 64 orders per lane -- the same bits
+ * (run_contig_grow_kernel).  At K = 128 the same kernel takes the launch, in place of the four-voxels-per-wavefront kernel
+ * below, when at least 60 % of the records run while at most 64 orders can hold anything (with EPGX_CGROW=2 in the
+ * environment: whenever the larger capacities would take it) -- again the same bits.
  * One wavefront owns one voxel for the whole range, except in state-resident launches with
  * K <= 128 of ranges made of T / T0 / E / S(+-1) / probe operators only: there one wavefront owns
  * four voxels (16 lanes each, K / 16 orders per lane) -- same results, bit for bit; except rotations about x

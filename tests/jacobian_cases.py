@@ -1,6 +1,6 @@
 """The derivative cases that tests/test_gpu_jacobian_paths.py runs on the device and tests/test_jacobian_recurrence_host.py
 measures on the CPU -- oracle tuples, the variables of the plan, the capacity and the kernel name each case must get from
-choose_kernel (csrc/epgx_api.hip) -- and the per-column check both use:
+choose_kernel (csrc/epgx_planner.cpp) -- and the per-column check both use:
 
     err_v = max|got[..., v] - ref[..., v]| / max|ref[..., v]|   <=   16 x the case's float64 floor   (never above 1e-11)
 

@@ -1,4 +1,4 @@
-"""Sequences for the ranges of rows_grow_kernel that run at the orders which can still reach a probe (grow_reach, epgx_api.hip):
+"""Sequences for the ranges of rows_grow_kernel that run at the orders which can still reach a probe (grow_reach, epgx_planner.cpp):
 run as a script it writes their signals to an .npz -- tests/test_gpu_reach.py runs it in a child process with EPGX_REACH=0
 (the library reads the variable once per process) and compares with its own results.
 

@@ -197,7 +197,7 @@ def test_user_written_operators_and_callable_probes_inside_simulate():
 
 # ------------------------------------------------------------------ which kernel a configuration takes
 def test_kernel_of_every_baseline_config():
-    """epgx_kernel_for: the ONE decision function of the library (choose_kernel, epgx_api.hip) pinned for every
+    """epgx_kernel_for: the ONE decision function of the library (choose_kernel, epgx_planner.cpp) pinned for every
     BASELINE.json configuration, their Jacobian variants and the capacity classes -- on small grids: the decision depends on
     the plan, the range, the capacity and on whether states are given, never on the number of voxels"""
     from epgpy_amd import _lib, functions, workloads as wl

@@ -3,7 +3,7 @@ np.clongdouble), PER COLUMN: for every variable v  max|gpu[..., v] - ref[..., v]
 is what the float64 oracle itself achieves on that case (tests/test_jacobian_recurrence_host.py FLOORS) -- the columns of a
 Jacobian differ by five orders of magnitude, and a bound scaled by the whole array hides an error in a small one.
 
-Every case first asks the library which kernel it would launch (choose_kernel, csrc/epgx_api.hip) and asserts the exact
+Every case first asks the library which kernel it would launch (choose_kernel, csrc/epgx_planner.cpp) and asserts the exact
 name, so that a selection change that drops a path fails here by name:
   (a) deriv_kernel<M, NSP, V, CONTIG> from equilibrium     (b) deriv_kernel from a state input
   (c) packed_deriv_kernel<NSP, V, 16|32>                    (d) rows_deriv_kernel<NSP, 4, V>

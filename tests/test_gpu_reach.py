@@ -1,5 +1,5 @@
 """rows_grow_kernel runs each of its three ranges at the smallest of 16 / 32 / 64 orders per voxel that holds the orders which
-can still reach an order-0 probe (grow_reach, epgx_api.hip; EPGX_REACH=0: at 16 / 32 / 64 as before).  Orders above the
+can still reach an order-0 probe (grow_reach, epgx_planner.cpp; EPGX_REACH=0: at 16 / 32 / 64 as before).  Orders above the
 number of shifts left before the last probe cannot influence it (tests/test_reach_rule.py), so the signals must be those of
 EPGX_REACH=0 BIT FOR BIT, and agree with the oracle as everywhere else."""
 import os

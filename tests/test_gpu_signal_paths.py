@@ -5,7 +5,7 @@ float64 oracle itself achieves on that case (tests/signal_cases.py FLOORS, kept 
 tests/test_signal_recurrence_host.py).  A bound scaled by the whole array hides the late records of a decaying train and
 the high orders of a state.
 
-Every case first asks the library which kernel it would launch (choose_kernel, csrc/epgx_api.hip) and asserts the exact name
+Every case first asks the library which kernel it would launch (choose_kernel, csrc/epgx_planner.cpp) and asserts the exact name
 BEFORE launching.  Without derivative states choose_kernel can return 96 names that the launch tables instantiate
 (epgx_launch*.h, epgx_inst.hip, epgx_split.hip; tests/signal_cases.py ALL_NAMES), and the cases name every one of them:
   (a) rows_kernel<NSP, R, RUNS>: NSP 1 / 2 / 4, R 1 / 2 / 4 with and without RUNS, R 8 without      21

@@ -1,4 +1,4 @@
-"""The rule behind the capacities of rows_grow_kernel's ranges (grow_reach, epgx_api.hip), checked on the oracle's NumPy port
+"""The rule behind the capacities of rows_grow_kernel's ranges (grow_reach, epgx_planner.cpp), checked on the oracle's NumPy port
 alone -- no device code takes part.
 
 A launch whose only outputs are order-0 probes (F0 / Z0) needs, at a point of its sequence with `rem` shifts left before the
