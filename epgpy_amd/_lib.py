@@ -66,6 +66,9 @@ class PlanDesc(ctypes.Structure):
 MAX_VARS = 3
 DERIV_THROUGH_PLAIN_OPS = 1
 PLAN_NO_FOLD = 2      # keep every relaxation a stage of its own (include/epgx.h EPGX_PLAN_NO_FOLD)
+DERIV_SECOND = 4      # the plan is a one-pair second-order pass (include/epgx.h EPGX_DERIV_SECOND): hess_kernel
+HESS_CROSS_A, HESS_CROSS_B = 1, 2    # epgx_dop::reserved of such a plan: which cross terms the operator contributes
+HESS_MAX_K = 512      # capacities of the fused second-order pass: 64 .. 512 (where max_vars(K) == 3)
 FUSE_DTYPE = np.dtype([("dst_off", "<i8"), ("src_off", "<i8"), ("e_off", "<i8"), ("dst_space", "<i4"),
                        ("src_space", "<i4"), ("e_space", "<i4"), ("src_ncoef", "<i4"), ("after", "<i4"),
                        ("reserved", "<i4")])

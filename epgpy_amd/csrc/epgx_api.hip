@@ -38,6 +38,7 @@
 #include "epgx_xrun_kernels.hip.h"
 #include "epgx_deriv_kernels.hip.h"
 #include "epgx_launch.h"
+#include "epgx_launch_hess.h"
 #include "epgx_planner.h"
 #include "epgx_chain.h"
 #include "epgx_dft.h"
@@ -558,6 +559,17 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
     if (n_pool >= ((int64_t)1 << 29) - 16)
         return fail(EPGX_ERR_UNSUPPORTED, "epgx_plan_create: coefficient pool larger than 4 GiB (split the grid)");
     if (d->n_adc < 0) return fail(EPGX_ERR_INVALID, "epgx_plan_create: n_adc < 0");
+    if (d->deriv_flags & EPGX_DERIV_SECOND) {   // a one-pair second-order pass (hess_kernel): what such a plan cannot carry, before its lists are read
+        if (d->n_vars != 2 && d->n_vars != 3)
+            return fail(EPGX_ERR_INVALID, "epgx_plan_create: EPGX_DERIV_SECOND needs n_vars = 3 (S_a, S_b, H_ab) or 2 (S_a, H_aa), got %d", d->n_vars);
+        if (!d->dops) return fail(EPGX_ERR_INVALID, "epgx_plan_create: EPGX_DERIV_SECOND without dops");
+        if (!(d->deriv_flags & EPGX_PLAN_NO_FOLD))
+            return fail(EPGX_ERR_UNSUPPORTED, "epgx_plan_create: EPGX_DERIV_SECOND without EPGX_PLAN_NO_FOLD: the run-time fold implements the first-order product rule only");
+        if (d->n_fuse > 0 || d->n_fuse_partial > 0)
+            return fail(EPGX_ERR_UNSUPPORTED, "epgx_plan_create: EPGX_DERIV_SECOND with device-generated tables (n_fuse, n_fuse_partial): epgx_fuse_partial implements the first-order product rule only");
+        if (n_chain > 0)
+            return fail(EPGX_ERR_UNSUPPORTED, "epgx_plan_create: EPGX_DERIV_SECOND with chains: a collapsed run of operators has no second-order partials");
+    }
 
     const bool trace = getenv("EPGX_TRACE") != nullptr;
     const auto tic = std::chrono::steady_clock::now();
@@ -753,6 +765,25 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
     }
     pl->host.n_vars = d->n_vars;
     pl->deriv_flags = d->deriv_flags;
+    if (d->deriv_flags & EPGX_DERIV_SECOND) {   // a one-pair second-order pass (hess_kernel)
+        const char *why = nullptr;
+        int code = EPGX_ERR_UNSUPPORTED;
+        for (int i = 0; i < d->n_ops && !why; ++i) {
+            const epgx_dop &dp = d->dops[i];
+            if (pl->host.ops[i].opcode == EPGX_OP_T0) why = "EPGX_DERIV_SECOND with an EPGX_OP_T0 operator: the constant term of a fused table has no second-order partial";
+            else if (pl->host.ops[i].opcode == EPGX_OP_X) why = "EPGX_DERIV_SECOND with exchange (EPGX_OP_X)";
+            else if ((dp.reserved & ~(EPGX_HESS_CROSS_A | EPGX_HESS_CROSS_B)) || ((dp.reserved & EPGX_HESS_CROSS_A) && dp.coef_off[0] < 0) ||
+                     ((dp.reserved & EPGX_HESS_CROSS_B) && (d->n_vars != 3 || dp.coef_off[1] < 0))) {
+                why = "EPGX_DERIV_SECOND: a cross-term bit (epgx_dop::reserved) without its first-order partial";
+                code = EPGX_ERR_INVALID;
+            }
+        }
+        if (why) {
+            delete pl;
+            return fail(code, "epgx_plan_create: %s", why);
+        }
+        pl->host.second = true;
+    }
     {
         const int env = knobs().fold ? 1 : 0;   // (EPGX_FOLD=0: measurements)
         pl->host.fold = env != 0 && !(d->deriv_flags & EPGX_PLAN_NO_FOLD) && d->n_vars == 0;
@@ -2089,6 +2120,7 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
                         rl.n_druns, rl.n_rec, rl.drun_headers, rl.drun_ident, rl.drun_inside, da.grow1, da.grow1, da.grow2);
         }
         switch (c.family) {
+        case FAM_HESS: e = epgx_launch_hess(ctx->stream, da, K, pl->host.n_spaces, pl->host.n_vars == 2); break;
         case FAM_PACKED_DFOLD: e = epgx_launch_packed_dfold(ctx->stream, da, K, pl->host.n_vars); break;
         case FAM_DRUN:
             if (c.split3) {

@@ -84,6 +84,10 @@ void pack_records(const PlanHost &ph, int begin, int end, int K, const Knobs &kn
             const bool with_const = t_stage && (pattern & (256u << v));   // generated partial of a T0 table: 14 per entry
             const uint32_t bytes = t_stage ? (with_const ? 112u : 80u) : 32u;
             const uint32_t ix = dp.space[v] < 0 ? 0u : (bytes | ((uint32_t)dp.space[v] << 24));
+            if (ph.second && v < ph.n_vars - 1) {   // which cross terms of the H row this stage takes: the host's decision
+                if (dp.reserved & (v == 0 ? EPGX_HESS_CROSS_A : EPGX_HESS_CROSS_B))
+                    dcur.pad0 |= (v == 0 ? (t_stage ? HESS_T_XA : HESS_E_XA) : (t_stage ? HESS_T_XB : HESS_E_XB));
+            }
             if (t_stage) {
                 dcur.t_off[v] = (uint32_t)(dp.coef_off[v] * 8);
                 dcur.t_ix[v] = ix;
@@ -907,7 +911,7 @@ RangeLists build_range(const PlanHost &ph, int begin, int end, int K, const Knob
     fold_runs(pr, K);
     grow_phases(pr, K, kn);
     cgrow_phases(pr, K);
-    deriv_runs(ph, pr, K, kn, elog);
+    if (!ph.second) deriv_runs(ph, pr, K, kn, elog);   // (second-order passes walk the plain record list: hess_kernel)
     return pr;
 }
 
@@ -1054,6 +1058,20 @@ int choose_kernel(const PlanHost &ph, const RangeLists &lists, int op_begin, int
     if (packed16 && pl->n_vars > 0 && pr->use_lds) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: K = 16 / 32 derivative plans handle shifts by +-1 only");
     const int nsp = pl->n_spaces <= 2 ? pl->n_spaces : 4, V = pl->n_vars;
     const bool plain_ops = !has_general && !has_nd && !pr->use_lds;   // rotations, relaxation, shifts by +-1, probes, SPOILER / RESET / PD
+    if (V > 0 && pl->second) {
+        // one-pair second-order pass: S, S_a, (S_b,) H_ab in registers -- the capacities at which a launch carries three derivative states
+        if (has_in || has_out) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: second-order plans run state-resident from equilibrium (in = out = NULL)");
+        if (K != 64 && K != 128 && K != 256 && K != 512)
+            return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: second-order plans support K = 64, 128, 256, 512, got %d", K);
+        const bool diag = V == 2;
+        c->family = FAM_HESS;
+        c->why = diag ? "second-order pass for a diagonal pair: S, S_a, H_aa, one wavefront per voxel"
+                      : "second-order pass for one variable pair: S, S_a, S_b, H_ab, one wavefront per voxel";
+        // (hess_kernel<8, 1, false> alone needs scratch (32 bytes per lane): such plans run the two-space instantiation, whose second
+        // space no record refers to)
+        snprintf(c->name, sizeof(c->name), "hess_kernel<%d, %d, %s>", K / 64, (K == 512 && !diag && nsp == 1) ? 2 : nsp, diag ? "true" : "false");
+        return EPGX_OK;
+    }
     if (V > 0) {
         if (has_out) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: derivative plans run state-resident (out = NULL)");
         if (K > 1024) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: derivative plans support K <= 1024, got %d", K);

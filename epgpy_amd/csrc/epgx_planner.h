@@ -52,6 +52,8 @@ struct PlanHost {
     std::vector<uint16_t> dpattern; // per op: bits 2v, 2v + 1 = zero pattern of variable v's partial table (1: phi = 0 / real E, 2: real matrix);
                                     // bit 8 + v: the partial is a generated one (14 per entry: with the partial of the constant term)
     int32_t n_vars = 0;
+    bool second = false;      // EPGX_DERIV_SECOND: a one-pair second-order pass (n_vars 3: S_a, S_b, H_ab; 2: S_a, H_aa); epgx_dop::reserved
+                              // then carries the operator's EPGX_HESS_CROSS_* bits (-> DRec.pad0)
     int32_t n_spaces = 0;
     int64_t n_pool = 0;       // doubles in the device pool: n_coef + the device-generated part; behind it 32 doubles of
                               // padding that start with the identity relaxation {1, 0, 1, 0} (folded records)
@@ -154,7 +156,8 @@ enum Family {
     FAM_PACKED_DERIV,  // packed_deriv_kernel<NSP, V, KP>: 16 / 32 orders, four / two voxels per wavefront, 1 + V states
     FAM_ROWS_DERIV,    // rows_deriv_kernel<NSP, 4, V>: the rows layout with one or two derivative states
     FAM_DRUN,          // drun_kernel<NSP, V, SHAPE, V0>: rotating order slots, runs of fused / folded records, 1 + V states
-    FAM_PACKED_DFOLD   // packed_dfold_kernel: 16 / 32 orders, repetitions folded at run time, 1 + V states
+    FAM_PACKED_DFOLD,  // packed_dfold_kernel: 16 / 32 orders, repetitions folded at run time, 1 + V states
+    FAM_HESS           // hess_kernel<M, NSP, DIAG>: one-pair second-order pass, one wavefront per voxel, S, S_a, (S_b,) H
 };
 struct Choice {
     Family family = FAM_RUN;

@@ -107,12 +107,16 @@ struct DRec {                 // 64 bytes = two s_load_dwordx8
     uint32_t present;         // bit v: T partial for variable v; bit 4 + v: E partial; bit 16 + v: the T partial is a REAL matrix;
                               // bit 8 + v: the T partial has the phi = 0 zero pattern (Im m00 = Im m01 =
                               // Re m02 = Re m20 = 0 for every entry); bit 12 + v: the E partial is real
-    uint32_t pad0;
+    uint32_t pad0;            // second-order plans (hess_kernel): HESS_* bits, which cross terms enter the H row at the T / E stage
     uint32_t e_off[MAX_VARS]; // byte offset of d(E stage)/dv, 4 doubles per entry
     uint32_t e_ix[MAX_VARS];
     uint32_t pad1[2];
 };
 static_assert(sizeof(DRec) == 64, "DRec must be two s_load_dwordx8");
+
+// DRec.pad0 of a one-pair second-order plan (EPGX_DERIV_SECOND; epgx_hess_kernels.hip.h): cross term a = (dOp/da) S_b (the doubled
+// term (dOp/da) S_a of a diagonal pair), cross term b = (dOp/db) S_a.  The second-order term is `present` of the H slot.
+enum : uint32_t { HESS_T_XA = 1u << 0, HESS_T_XB = 1u << 1, HESS_E_XA = 1u << 4, HESS_E_XB = 1u << 5 };
 
 // records folded at run time in derivative plans (drun_kernel, DRUN_FOLD): E_a . T . E_b as ONE stage.  DRec then holds, per
 // variable, the rotation's partial (t_off / t_ix, folded like the rotation) and E_a's table of logarithmic partials (e_off /

@@ -11,9 +11,20 @@ keeps S and up to three dS_v of its voxel in registers, and every operator that 
 combination over parameters is linear in the tables, so it is done once on the host).  The
 `Jacobian` probe reads F0 / Z0 of S ("magnitude") and of every dS_v at each ADC.
 
-Second-order derivatives (order2, Hessian) follow the reference's recurrence operator by operator
-(`_apply_order2`): every term is a device state matrix, updated with the same kernels and
-`epgx_state_axpy`; there is no fused kernel for them.
+Second-order derivatives (order2, Hessian).  The reference's recurrence (diff.py:290-379) is, per variable pair (a, b),
+
+    H_ab <- Op H_ab + (dOp/da) S_b + (dOp/db) S_a + (d2Op/da db) S
+
+with a per-operator selection of the terms: a cross term enters only when the pair is in the operator's `order2` or, with
+`auto_cross_derivatives`, when the other variable is alive in the state's `order1`; the second-order term follows
+`parameters_order2` and the coefficients of `order2`.  Two paths:
+
+  * `simulate(..., mode="resident")` runs one launch of hess_kernel per pair (csrc/epgx_hess_kernels.hip.h): S, S_a, S_b and
+    H_ab of a voxel stay in registers.  The host combines the second-order table of every operator (`_second_table`) and
+    decides the cross terms while the sequence is encoded (`hessian_terms`, `Encoder.alive`); functions._simulate_hessian
+    compiles the passes.
+  * `mode="auto"` / `"stepwise"` and op(sm) follow the recurrence operator by operator (`_apply_order2`): every term is a
+    device state matrix, updated with the per-timestep kernels and `epgx_state_axpy`.
 """
 import numpy as np
 
@@ -143,8 +154,62 @@ class DiffMixin:
             self._dtables = tables
         return self._dtables
 
+    def _second_table(self, a, b):
+        """the combined second-order table of the pair (a, b) in the device layout of the first-order tables,
+            sum_p order2[pair][p] dOp/dp + sum_{p1, p2} c1 c2 d2Op/dp1 dp2,
+        or None when the operator contributes no such term -- the first two loops of `_apply_order2` (a parameter pair
+        counts once, as there)"""
+        pair = Pair(a, b)
+        if pair not in self.order2:
+            return None
+        terms = []
+        first = self._partial_tables(set(self.order2[pair])) if self.order2[pair] else {}
+        for param, coeff in self.order2[pair].items():
+            terms.append((first[param], coeff))
+        coeffs = {Pair(p1, p2): c1 * c2 for p1, c1 in self.order1.get(pair[0], {}).items()
+                  for p2, c2 in self.order1.get(pair[1], {}).items()}
+        wanted = [pp for pp in coeffs if pp in self.parameters_order2]
+        if wanted:
+            from . import opmatrix
+            raw = {Pair(key): value for key, value in self._raw_partials2().items()}
+            pack = pack_matrix_partial if isinstance(self, opmatrix.MatrixOp) else pack_scalar_partial
+            for pp in wanted:
+                arr, arr0 = raw[pp]
+                terms.append((pack(arr) if arr0 is None else pack(arr, arr0), coeffs[pp]))
+        total = None
+        for tab, coeff in terms:
+            if np.ndim(coeff):
+                raise NotImplementedError("array-valued coefficients in order2")
+            term = tab * float(coeff)
+            total = term if total is None else total + term
+        if total is None:
+            return None
+        if self._daxes is not None:
+            total = common.set_axes(1, total, self._daxes)
+        return np.ascontiguousarray(total, dtype=np.float64)
+
     def _encode(self, enc):
         super()._encode(enc)
+        pair = getattr(enc, "hessian", None)
+        if pair is not None:
+            # a one-pair second-order pass: the pair's first-order tables, the combined second-order table under the
+            # pass's key, and which cross terms this operator contributes (the state's alive variables: Encoder.alive)
+            a, b = pair
+            tables = {var: ("entry", enc.partial_table(self, var)) for var in self.order1 if var in pair}
+            second = self._second_table(a, b)
+            if second is not None:
+                tables[hessian_key(a, b)] = (second, ("D2", id(self), a, b))
+            if tables:
+                enc.add_partials(tables)
+            # (the reference runs its order-2 step only once the state carries a second-order entry or the operator declares
+            # one -- DiffOperator.__call__; before that, operators with order1 alone take no cross terms)
+            if enc.alive2 or self.order2:
+                cross_a, cross_b = hessian_terms(self, a, b, enc.alive)
+                if cross_a or cross_b:
+                    enc.add_cross(cross_a, cross_b and a != b)
+                enc.alive2 |= order2_created(self, enc.alive)
+            enc.alive |= set(self.order1)
+            return
         if self.order1:
             enc.add_partials({var: ("entry", enc.partial_table(self, var)) for var in self.order1})
 
@@ -272,6 +337,36 @@ class DiffMixin:
         return super().combine(other, **kwargs)
 
 
+def hessian_key(a, b):
+    """name of the H slot among an encoder's variables (a tuple: no order1 variable can collide with it)"""
+    return ("order2",) + Pair(a, b)
+
+
+def hessian_terms(op, a, b, alive):
+    """(cross_a, cross_b): does the operator `op` contribute (dOp/da) S_b / (dOp/db) S_a to H_ab, given the variables
+    `alive` in the state's order1 BEFORE the operator -- the cross-term loop of `_apply_order2`: the term (dOp/dv2) S_v1
+    enters when v1 is alive, v2 is one of the operator's variables, and the pair is in the operator's order2 or, with
+    auto_cross_derivatives, always.  For a == b the two terms are the same one, taken twice (cross_a)."""
+    order1 = getattr(op, "order1", None) or {}
+    allowed = op.auto_cross_derivatives or Pair(a, b) in op.order2
+    cross_a = bool(allowed and a in order1 and b in alive)
+    cross_b = bool(allowed and b in order1 and a in alive)
+    return cross_a, cross_b
+
+
+def order2_created(op, alive):
+    """the pairs whose second-order state exists after `op` because of `op` (the three loops of `_apply_order2`), given the
+    variables `alive` in the state's order1 before it"""
+    created = {pair for pair, coeffs in op.order2.items() if coeffs}
+    available = op.parameters_order2
+    for v1, v2 in op.order2:
+        if any(Pair(p1, p2) in available for p1 in op.order1.get(v1, {}) for p2 in op.order1.get(v2, {})):
+            created.add(Pair(v1, v2))
+    cross = {Pair(v1, v2) for v1 in op.order1 for v2 in alive} if op.auto_cross_derivatives else set(op.order2)
+    created |= {Pair(v1, v2) for v1 in alive for v2 in op.order1 if Pair(v1, v2) in cross}
+    return created
+
+
 def _accumulate(dsm, part, alpha=1.0):
     """dsm += alpha * part on the device (same grid and capacity first)"""
     grid = common.broadcast_shapes(dsm.shape, part.shape, append=True)
@@ -361,8 +456,8 @@ class Jacobian(_probe.Probe):
 
 class Hessian(_probe.Probe):
     """probe of the signal's second derivatives: [..., len(variables1), len(variables2)]  (diff.py:419-472);
-    evaluated operator by operator (simulate() takes the stepwise path), "magnitude" rows / columns
-    give the first derivatives"""
+    "magnitude" rows / columns give the first derivatives.  simulate(mode="resident") runs one fused launch per variable
+    pair (F0 / Z0 probes); mode="auto" / "stepwise" evaluate operator by operator"""
 
     def __init__(self, variables1, variables2=None, *, probe="F0"):
         self.probe = probe
@@ -380,7 +475,39 @@ class Hessian(_probe.Probe):
         return f"Hessian({self.probe})"
 
     def _device_kind(self):
-        return None
+        return _probe.DEVICE_KINDS.get(self.probe)
+
+    def pairs(self):
+        """the sorted variable pairs the probe reads second derivatives of, each once, in first-use order"""
+        out = []
+        for v1 in self.variables1:
+            for v2 in self.variables2:
+                if "magnitude" not in (v1, v2) and Pair(v1, v2) not in out:
+                    out.append(Pair(v1, v2))
+        return out
+
+    def first_order(self):
+        """variables whose first derivatives the "magnitude" rows / columns read"""
+        out = [v for v in self.variables2 if v != "magnitude"] if "magnitude" in self.variables1 else []
+        out += [v for v in self.variables1 if v != "magnitude" and v not in out] if "magnitude" in self.variables2 else []
+        return out
+
+    def _assemble2(self, base, first, second):
+        """first: {variable: probe of S_v}; second: {sorted pair: probe of H}; what is missing is zeros, as in _acquire"""
+        missing = np.zeros(base.shape)
+        rows = []
+        for v1 in self.variables1:
+            row = []
+            for v2 in self.variables2:
+                if v1 == "magnitude":
+                    src = first.get(v2)
+                elif v2 == "magnitude":
+                    src = first.get(v1)
+                else:
+                    src = second.get(Pair(v1, v2))
+                row.append(src if src is not None else missing)
+            rows.append(np.stack(row, axis=-1))
+        return np.stack(rows, axis=-2)
 
     def _acquire(self, sm):
         order1 = getattr(sm, "order1", None) or {}

@@ -592,8 +592,13 @@ def simulate_sharded(sequence, *, group=None, dst=0, probe=None, adc_time=False,
     dtype = functions.signal_dtype(dtype)
     if dtype != np.complex128 and out == "device":
         raise NotImplementedError('out="device" keeps complex128 records')
-    rank, world = dist.get_rank(group), dist.get_world_size(group)    # ranks of the GROUP
     flat = functions.flatten_sequence(sequence)
+    from .diff import Hessian
+    if any(isinstance(pb, Hessian) for pb in (list(probe) if isinstance(probe, (tuple, list)) else [probe]) + flat):
+        # (the fused second-order passes run on one GPU; the same refusal sits in compile_sequence for ShardedPlan)
+        raise NotImplementedError("Hessian probes: simulate_sharded does not carry second-order passes; use simulate(mode='resident') "
+                                  "on one GPU, or mode='stepwise'")
+    rank, world = dist.get_rank(group), dist.get_world_size(group)    # ranks of the GROUP
     if functions.has_exchange(flat):
         raise NotImplementedError("X (exchange) runs on one GPU: simulate_sharded does not carry it")
     probes = []

@@ -13,6 +13,7 @@ both stay within 1e-12).
 Sequences with a `callback`, or with probes the kernel cannot record itself, run
 segment-wise and evaluate the probes on a host view of the device state.
 """
+import numbers
 import os
 
 import numpy as np
@@ -189,13 +190,15 @@ def _fusion_pays(sequence, variables, nstate0, options, from_state=False):
 
 
 def compile_sequence(sequence, probes=None, *, shape=None, options=None, nstate0=0, kspace0=None,
-                     dense_start=False, variables=(), fuse=True, collapse=True):
+                     dense_start=False, variables=(), fuse=True, collapse=True, hessian=None):
     """flatten + encode; returns (encoder, records) with records = [(op, [(probe, slot)...])]
 
     variables: names of the (at most 3) order1 variables whose derivative states the plan
     propagates; every probe then owns 1 + len(variables) consecutive signal rows from `slot`
     collapse: operators flagged `collapsible` (RF pulses) become ONE record each, their table multiplied up on the device
-    (collapse.py); False: their members, one by one"""
+    (collapse.py); False: their members, one by one
+    hessian: (a, b) -- a one-pair second-order pass (diff.py): `variables` = [a, b, diff.hessian_key(a, b)] ([a, key] for
+    a == b), the plan carries EPGX_DERIV_SECOND; the caller passes fuse=False, collapse=False"""
     sequence = flatten_sequence(sequence, keep_collapsible=collapse)
     grid = getshape(sequence)
     if shape is not None:
@@ -208,6 +211,9 @@ def compile_sequence(sequence, probes=None, *, shape=None, options=None, nstate0
                    else kspace.KSpace.equilibrium(kdim))
     enc = _plan.Encoder(grid, options=options, nstate0=nstate0, kspace0=kspace0)
     enc.variables = list(variables)
+    if hessian is not None:
+        enc.hessian = tuple(hessian)
+        enc.deriv_flags |= _lib.DERIV_SECOND | _lib.PLAN_NO_FOLD
     if not fuse:     # operator-by-operator arithmetic: no host-side E.T.E tables, no run-time fold in the library either
         enc.deriv_flags |= _lib.PLAN_NO_FOLD
     records, bounds = [], []
@@ -229,6 +235,10 @@ def compile_sequence(sequence, probes=None, *, shape=None, options=None, nstate0
                 kind = (pb or op)._device_kind()
                 if kind is None:
                     raise NotImplementedError(f"probe {pb or op!r} cannot be recorded on the device")
+                if hessian is None and hasattr(pb or op, "_assemble2"):
+                    # (a Hessian probe is recorded by one-pair second-order passes only: _simulate_hessian compiles them)
+                    raise NotImplementedError(f"probe {pb or op!r} cannot be recorded on the device by this path: Hessian probes run "
+                                              "with simulate(mode='resident') on one GPU, or operator by operator")
                 slots.append((pb or op, enc.add_adc(kind)))
             records.append((op, slots))
             bounds.append(len(enc.records))
@@ -260,6 +270,10 @@ def simulate(sequence, *, adc_time=False, init=None, squeeze=False, probe=None, 
     on the GPU and never need the 16 GB of a 10^6-voxel MRF signal on the host.  A Jacobian probe (at most three
     variables, one GPU) leaves a `DeviceJacobian`: per ADC the probed state and its derivative rows, `.column(var)` a
     `DeviceSignal` on one of them.
+
+    A Hessian probe runs operator by operator under mode="auto" / "stepwise"; mode="resident" runs ONE fused launch per variable
+    pair (F0 / Z0 probes, at most 512 orders, one GPU, from equilibrium; NotImplementedError names what it does not take) and with
+    out="device" leaves a `DeviceHessian`.
 
     `collapse`: shaped RF pulses (rfpulse.RFPulse, and what `modify` / `encode_phase` make of one) run as ONE operator each,
     their members multiplied up on the device once per voxel (collapse.py; results differ from the member-by-member run by
@@ -318,8 +332,18 @@ def simulate(sequence, *, adc_time=False, init=None, squeeze=False, probe=None, 
         if mode not in ("auto", "stepwise"):
             raise NotImplementedError(f"mode={mode!r} with a general equilibrium: only the operator-by-operator path carries one")
         mode = "stepwise"
-    if mode == "auto":
-        mode = "resident" if (on_device and not callback) else "stepwise"
+    from .diff import Hessian
+    second = any(isinstance(pb or op, Hessian) for op in sequence if isinstance(op, Probe) for pb in (probes or [op]))
+    if mode == "auto":      # (Hessian probes: the fused passes are taken on request, mode="resident")
+        mode = "resident" if (on_device and not callback and not second) else "stepwise"
+    if second and mode == "stream":
+        raise NotImplementedError("Hessian probes run state-resident (mode='resident') or operator by operator (no mode='stream')")
+    if second and mode == "resident":
+        if callback:
+            raise NotImplementedError("Hessian probes with mode='resident': no callback (PartialsPruner works on the operator-by-operator path)")
+        if not on_device:
+            raise NotImplementedError("Hessian probes with mode='resident': float shifts, user-written operators and probes other "
+                                      "than F0 / Z0 run operator by operator")
     if mode in ("resident", "stream") and (callback or not on_device):
         raise ValueError(f"mode={mode!r} needs device-recordable probes (F0/Z0), library operators only and no callback")
     if out not in ("host", "device"):
@@ -765,6 +789,9 @@ def _finish_jacobian(sequence, records, base, partials):
 
 def _simulate_device(sequence, probes, init, mode, devices, options, exact_partials=False, fuse=True, packed=True,
                      progress=None, to_host=True, dtype=np.complex128, shape=None, collapse=True):
+    from .diff import Hessian
+    if any(isinstance(pb or op, Hessian) for op in sequence if isinstance(op, Probe) for pb in (probes or [op])):
+        return _simulate_hessian(sequence, probes, init, devices, options, exact_partials, to_host, dtype, shape)
     variables = _jacobian_variables(sequence, probes)
     if variables:
         if mode == "stream":
@@ -831,6 +858,155 @@ def _simulate_device(sequence, probes, init, mode, devices, options, exact_parti
         else:
             fleet.run(K_run, state_in)
     return _finish_device(sequence, records, enc, fleet, groups, need_raw, raw, to_host, dtype)
+
+
+def hessian_passes(sequence, probes):
+    """the one-pair passes of a call with Hessian probes: [(a, b)] sorted pairs, each once.  Every pair a Hessian probe reads
+    whose two variables some operator declares (another pair is zeros); then, for every first-order variable that a
+    Jacobian probe or a "magnitude" row / column reads and no pass carries yet, the diagonal pass (v, v)"""
+    from .diff import Hessian, Pair
+    known = {var for op in sequence for var in (getattr(op, "order1", None) or {})}
+    pairs, first = [], []
+    for op in sequence:
+        if isinstance(op, Probe):
+            for pb in (probes or [op]):
+                pb = pb or op
+                if isinstance(pb, Hessian):
+                    pairs += [pair for pair in pb.pairs() if pair not in pairs and set(pair) <= known]
+                    first += [v for v in pb.first_order() if v not in first]
+                else:
+                    first += [v for v in getattr(pb, "_device_variables", list)() if v not in first]
+    for var in first:
+        if var in known and not any(var in pair for pair in pairs):
+            pairs.append(Pair(var, var))
+    return pairs
+
+
+def _simulate_hessian(sequence, probes, init, devices, options, exact_partials=False, to_host=True, dtype=np.complex128, shape=None):
+    """Hessian probes, mode="resident": one launch of hess_kernel per variable pair (diff.py), each pass a plan of its own
+    built without fusion, collapse or fold.  All passes write into ONE signal buffer [pass][row][voxel]; a pass's S, S_a,
+    S_b rows also serve the Jacobian and plain probes of the call.  What the fused path does not take raises
+    NotImplementedError (mode="auto" / "stepwise" run operator by operator)"""
+    from .diff import Hessian, hessian_key
+    why = None
+    if len(devices) > 1:
+        why = "ngpu > 1"
+    elif init is not None:
+        why = "init= / a general equilibrium (the passes start from equilibrium)"
+    elif any(isinstance(op, _operator.MultiOperator) and op.collapsible for op in sequence):
+        why = "an RFPulse (a collapsed operator has no second-order partials)"
+    elif any(isinstance(part, _shift.S) and not isinstance(part.k, numbers.Integral) for op in sequence for part in op._parts()):
+        why = "n-D shifts"
+    elif np.dtype(dtype) != np.complex128:
+        why = "dtype=complex64"
+    if why:
+        raise NotImplementedError(f"Hessian probes with mode='resident': {why}; use mode='stepwise'")
+    sequence = flatten_sequence(sequence)
+    passes = hessian_passes(sequence, probes)
+    if not passes:
+        raise NotImplementedError("Hessian probes with mode='resident': no variable of the probes is declared by an operator; use mode='stepwise'")
+    ctx = _lib.get_context(devices[0])
+    plans, K, records = [], 0, None
+    for a, b in passes:
+        variables = [a, hessian_key(a, b)] if a == b else [a, b, hessian_key(a, b)]
+        enc, records, _ = compile_sequence(sequence, probes, options=dict(options), variables=variables, shape=shape, fuse=False,
+                                           collapse=False, hessian=(a, b))
+        if any(rec[0] in (_lib.OP_D, _lib.OP_GS, _lib.OP_X) for rec in enc.records) or enc.deferred:
+            raise NotImplementedError("Hessian probes with mode='resident': diffusion, n-D shifts and exchange run operator by "
+                                      "operator; use mode='stepwise'")
+        enc.deriv_flags |= _lib.DERIV_THROUGH_PLAIN_OPS if exact_partials else 0
+        K = enc.capacity()
+        if K > _lib.HESS_MAX_K:
+            raise NotImplementedError(f"Hessian probes with mode='resident': {enc.peak + 1} phase states per voxel, the fused pass "
+                                      f"keeps at most {_lib.HESS_MAX_K}; bound the state matrix with max_nstate=... or use mode='stepwise'")
+        plans.append((enc, enc.device_plan(ctx, K)))
+    grid, nvox = plans[0][0].grid, plans[0][0].nvox
+    stride = max(enc.n_adc for enc, _ in plans)             # rows per pass (diagonal passes use fewer)
+    nbytes = 16 * len(passes) * stride * nvox
+    if nbytes > ctx.info()["hbm_bytes"] // 2:      # (every pass keeps its rows until the call returns: no chunking over voxels yet)
+        raise NotImplementedError(f"Hessian probes with mode='resident': the records of {len(passes)} passes over {nvox} voxels take "
+                                  f"{nbytes / 2 ** 30:.1f} GiB in one buffer, more than half the device memory; split the grid or the "
+                                  "probe's variables over several calls, or use mode='stepwise'")
+    buf = _lib.DeviceBuffer(ctx, nbytes)
+    for p, (enc, plan) in enumerate(plans):
+        _lib.run(ctx, plan, 0, plan.n_ops, 0, nvox, None, None, K, buf.ptr.value + 16 * p * stride * nvox, nvox, 0)
+    # where every row lives: per probe position j of record i the slot is the same in every pass up to its row count
+    nprobe = len(records[0][1]) if records else 0
+    layout = _HessianLayout(passes, stride, nprobe, grid, len(records))
+    if not to_host:
+        return _Stacked(_hessian_handles(records, buf, layout)), _probe_times(sequence)
+    raw = buf.download(np.complex128, (len(passes), stride) + tuple(grid))
+    buf.free()
+    values = []
+    for i, (op, slots) in enumerate(records):
+        row = []
+        for j, (pb, _) in enumerate(slots):
+            base = raw[0, layout.row(0, i, j, 0)]
+            first = {var: raw[p, layout.row(p, i, j, r)] for var, (p, r) in layout.first.items()}
+            if isinstance(pb, Hessian):
+                second = {pair: raw[p, layout.row(p, i, j, layout.nrow(p) - 1)] for p, pair in enumerate(passes)}
+                row.append(op.post(pb._assemble2(base, first, second)))
+            elif hasattr(pb, "_assemble"):
+                row.append(op.post(pb._assemble(base, first)))
+            else:
+                row.append(op.post(np.array(pb._finish(base))))
+        values.append(row)
+    return values, _probe_times(sequence)
+
+
+class _HessianLayout:
+    """rows of the signal buffer of a Hessian call, [pass][row][voxel] with `stride` rows per pass: pass p holds, per record
+    and probe position, nrow(p) = 3 (diagonal pair) or 4 consecutive rows -- S, S_a, (S_b,) H"""
+
+    def __init__(self, passes, stride, nprobe, grid, nrec):
+        self.passes, self.stride, self.nprobe, self.grid, self.nrec = list(passes), int(stride), int(nprobe), tuple(grid), int(nrec)
+        self.first = {}           # variable -> (pass, row inside a record) of its first-order state
+        for p, (a, b) in enumerate(self.passes):
+            self.first.setdefault(a, (p, 1))
+            if a != b:
+                self.first.setdefault(b, (p, 2))
+
+    def nrow(self, p):
+        a, b = self.passes[p]
+        return 3 if a == b else 4
+
+    def row(self, p, i, j, r):
+        """row (inside pass p) of row r of probe position j of record i"""
+        return (i * self.nprobe + j) * self.nrow(p) + r
+
+
+def _hessian_handles(records, buf, layout):
+    """out="device": per probe position a handle on the shared buffer -- DeviceHessian / DeviceJacobian-like rows are
+    described by element offsets, since the entries of one probe live in several passes"""
+    from .diff import Hessian, Pair
+    if not records:
+        return []
+    if not all(op._is_plain() or (hasattr(op, "_assemble") and not op._post) or (isinstance(op, Hessian) and not op._post) for op, _ in records):
+        raise NotImplementedError('out="device" returns raw records: no weights / reduce / phase / post on the probes')
+    nvox = int(np.prod(layout.grid))
+    handles = []
+    for j in range(layout.nprobe):
+        pb = records[0][1][j][0]
+        if len({id(slots[j][0]) for _, slots in records}) != 1:
+            raise NotImplementedError('out="device": one probe object per position of the probe list')
+        if not isinstance(pb, Hessian):
+            raise NotImplementedError('out="device" with Hessian probes: every probe of the list is a Hessian (run the Jacobian / '
+                                      'plain probes in a call of their own)')
+        if pb._post:
+            raise NotImplementedError('out="device" returns raw records: no post on the probes')
+        where = np.full((len(pb.variables1), len(pb.variables2), 2), -1, dtype=np.int64)     # (pass, row of record 0) or -1: zeros
+        for i1, v1 in enumerate(pb.variables1):
+            for i2, v2 in enumerate(pb.variables2):
+                if "magnitude" in (v1, v2):
+                    other = v2 if v1 == "magnitude" else v1
+                    if other in layout.first:
+                        p, r = layout.first[other]
+                        where[i1, i2] = (p, layout.row(p, 0, j, r))
+                elif Pair(v1, v2) in layout.passes:
+                    p = layout.passes.index(Pair(v1, v2))
+                    where[i1, i2] = (p, layout.row(p, 0, j, layout.nrow(p) - 1))
+        handles.append(DeviceHessian(buf, layout, where, pb.variables1, pb.variables2))
+    return handles
 
 
 def _device_records(records, enc, to_host):
@@ -944,6 +1120,50 @@ class DeviceJacobian:
         block = full.reshape((self.nrec, self._nprobe, self._nrow) + self.grid)[:, self._j]
         block = block if self.rows == list(range(self._nrow)) else block[:, self.rows]
         return np.moveaxis(block, 1, -1)
+
+    def __array__(self, dtype=None, copy=None):
+        out = self.download()
+        return out if dtype is None else out.astype(dtype)
+
+    def __len__(self):
+        return self.nrec
+
+
+class DeviceHessian:
+    """the records of one Hessian probe left in HBM (`simulate(..., probe=Hessian(...), mode="resident", out="device")`).
+    The call ran one pass per variable pair into one buffer [pass][row][voxel] complex128; entry (i1, i2) of the probe
+    (`variables1[i1]`, `variables2[i2]`) of record n starts at element
+        offsets[i1, i2] + n * record_strides[i1, i2]          (from `ptr`; offsets < 0: the entry is identically zero)
+    and is `nvox` elements long (`row_stride` = nvox: the rows of a record follow each other).  `nrec`, `grid`,
+    `variables1`, `variables2` as in the probe.  `np.asarray(h)` / `h.download()` gives what the host path returns:
+    [nrec, *grid, n1, n2].  The buffer goes back to the context's pool with its last handle."""
+
+    def __init__(self, buf, layout, where, variables1, variables2):
+        self._buf, self._layout, self._where = buf, layout, where
+        self.nrec, self.grid = layout.nrec, tuple(layout.grid)
+        self.nvox = int(np.prod(self.grid))
+        self.variables1, self.variables2 = list(variables1), list(variables2)
+        self.shape = (self.nrec,) + self.grid + (len(self.variables1), len(self.variables2))
+        self.dtype = np.dtype(np.complex128)
+        self.device = buf.ctx.device
+        self.ptr = buf.ptr.value
+        self.row_stride = self.nvox
+        p, r = where[..., 0], where[..., 1]
+        nrow = np.array([layout.nrow(q) for q in range(len(layout.passes))], dtype=np.int64)
+        self.offsets = np.where(p >= 0, (p * layout.stride + r) * self.nvox, -1)
+        self.record_strides = np.where(p >= 0, layout.nprobe * nrow[np.maximum(p, 0)] * self.nvox, 0)
+
+    def download(self):
+        npass, stride = len(self._layout.passes), self._layout.stride
+        flat = self._buf.download(np.complex128, (npass * stride * self.nvox,))
+        out = np.zeros(self.shape, dtype=np.complex128)
+        for i1 in range(len(self.variables1)):
+            for i2 in range(len(self.variables2)):
+                off, step = int(self.offsets[i1, i2]), int(self.record_strides[i1, i2])
+                if off >= 0:
+                    for n in range(self.nrec):
+                        out[(n,) + (slice(None),) * len(self.grid) + (i1, i2)] = flat[off + n * step: off + n * step + self.nvox].reshape(self.grid)
+        return out
 
     def __array__(self, dtype=None, copy=None):
         out = self.download()

@@ -45,6 +45,15 @@ class Encoder:
         self.partials = {}
         self.variables = []
         self.deriv_flags = 0
+        # one-pair second-order pass (diff.py, hess_kernel): the pair (a, b); variables = [a, b, hessian_key], or
+        # [a, hessian_key] for a == b.
+        #   alive: order1 variables of the state at this point of the sequence (resets do not clear it: a cleared state
+        #          contributes zeros)
+        #   cross: record index -> HESS_CROSS_* bits of the operator (epgx_dop::reserved)
+        self.hessian = None
+        self.alive = set()
+        self.alive2 = set()        # pairs whose second-order state exists at this point (any pair, not only the pass's)
+        self.cross = {}
         # tables the library generates on the device (epgx_fuse): offsets in the generated part of
         # the pool are kept as -(offset + 1) until the size of the host part is final
         self.generated = {}        # key -> (space, tagged offset, ncoef)
@@ -255,6 +264,10 @@ class Encoder:
         {variable: ("entry", pool entry)} for a partial the library generates (add_fuse_partial)"""
         self.partials[len(self.records) - 1] = tables
 
+    def add_cross(self, cross_a, cross_b):
+        """cross terms the operator just added contributes to the H row of a second-order pass (diff.hessian_terms)"""
+        self.cross[len(self.records) - 1] = (_lib.HESS_CROSS_A if cross_a else 0) | (_lib.HESS_CROSS_B if cross_b else 0)
+
     def add_deferred(self, opcode, builder):
         """operator whose table is laid out [*opshape, 3, K]: built once the capacity K is known"""
         self.deferred.append((len(self.records), builder))
@@ -459,6 +472,8 @@ class Encoder:
             dops["space"], dops["coef_off"] = -1, -1
             for (index, v), (space, off, _) in partial_entries.items():
                 dops[index]["space"][v], dops[index]["coef_off"][v] = space, fix(off)
+            for index, bits in self.cross.items():
+                dops[index]["reserved"] = bits
         coef = np.concatenate(self.pool) if self.pool else np.zeros(0)
         return ops, np.asarray(self.grid, dtype=np.int64), list(self.spaces), coef, dops
 

@@ -91,7 +91,7 @@ def crlb(J, H=None, *, W=None, sigma2=1, log=False):
     Returns `[...]` (device: float64 `grid`).  Singular voxels give NaN (module docstring)."""
     if _reject_handles(J):
         if H is not None:
-            raise NotImplementedError("H: the gradient of the bound is not computed on the device; download J (np.asarray) and H")
+            raise NotImplementedError("H: the gradient of the bound is not computed on the device; download J (np.asarray) and H (a DeviceHessian downloads with np.asarray as well)")
         return _device_bounds(J, W, sigma2, log, split=False)
 
     J, lb, noise = _fisher_inverse(J, sigma2)

@@ -136,7 +136,7 @@ typedef struct epgx_op {
  * T2 only): coef_off then names the recipe's destination. */
 typedef struct epgx_dop {
     int32_t space[EPGX_MAX_VARS]; /* index space of the partial's table, or -1 */
-    int32_t reserved;
+    int32_t reserved;             /* 0; under EPGX_DERIV_SECOND: EPGX_HESS_CROSS_* bits of this operator  */
     int64_t coef_off[EPGX_MAX_VARS];
 } epgx_dop; /* 40 bytes */
 
@@ -296,6 +296,25 @@ typedef struct epgx_plan_desc {
  * relaxation-only partials of epgx_fuse_partial tables inside runs.  Results equal the unfolded recurrence to rounding;
  * this flag switches all of it off. */
 #define EPGX_PLAN_NO_FOLD 2
+/* Also carried in `deriv_flags`: the plan is a ONE-PAIR SECOND-ORDER PASS for the variable pair (a, b)
+ * (DiffOperator order2, epgpy/diff.py:290-379).  Per operator:
+ *     H_ab <- Op H_ab + (dOp/da) S_b + (dOp/db) S_a + (d2Op/da db) S,   S_a, S_b, S as in a first-order plan.
+ * n_vars = 3 (a != b): slots 0 and 1 of every epgx_dop hold dOp/da and dOp/db, slot 2 the COMBINED second-order table
+ *     sum_p order2[pair][p] dOp/dp + sum_{p1, p2} c1 c2 d2Op/dp1 dp2   (same layouts as the first-order tables; combined
+ * on the host), acting on S (with its recovery term); every ADC writes four rows: the probe of S, S_a, S_b, H_ab.
+ * n_vars = 2 (a == b): slot 0 holds dOp/da, slot 1 the combined second-order table, the cross term is 2 (dOp/da) S_a;
+ * every ADC writes three rows: S, S_a, H_aa.
+ * Which cross terms enter at an operator is the HOST's decision (the reference takes a cross term only when the pair is in the
+ * operator's order2 or, with auto_cross_derivatives, when the other variable is alive in the state): epgx_dop::reserved
+ * carries EPGX_HESS_CROSS_A (the term (dOp/da) S_b; for a == b the doubled term) and EPGX_HESS_CROSS_B ((dOp/db) S_a);
+ * a cross bit whose first-order slot is empty is EPGX_ERR_INVALID.  The second-order term enters where its slot is filled.
+ * Plain operators act on H as on the first-order states (EPGX_DERIV_THROUGH_PLAIN_OPS); a reset clears H.
+ * Such a plan must set EPGX_PLAN_NO_FOLD and may not carry device-generated tables (n_fuse, n_fuse_partial) or chains: the
+ * run-time fold and epgx_fuse_partial implement the first-order product rule only (EPGX_ERR_UNSUPPORTED).  It runs
+ * state-resident from equilibrium on hess_kernel<K / 64, NSP, a == b> at K = 64, 128, 256, 512 (EPGX_ERR_UNSUPPORTED otherwise). */
+#define EPGX_DERIV_SECOND 4
+#define EPGX_HESS_CROSS_A 1
+#define EPGX_HESS_CROSS_B 2
 
 /* Record type of HOST-side signal arrays (and of narrowed device buffers, epgx_signal_narrow).  The reference returns
  * complex128 (statematrix.py:392); complex64 halves what crosses PCIe / xGMI -- the part of a large simulate() its caller
