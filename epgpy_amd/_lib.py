@@ -150,6 +150,7 @@ SYMBOLS = {
                              ctypes.POINTER(_i32), ctypes.c_char_p, _i64]),
     "epgx_signal_reduce": (_i, [_p, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _i64, _i64]),
     "epgx_signal_crlb": (_i, [_p, _p, _i64, _i64, _i32, _i32, _i32, _p, _i64, _i64, _p, _d, _i32, _p]),
+    "epgx_signal_crlb_grad": (_i, [_p, _p, _i64, _i64, _i32, _i32, _i32, _p, _i64, _i64, _p, _i64, _i32, _p, _p, _p, _d, _i32, _p, _p]),
     "epgx_simulate_f64": (_i, [_p, ctypes.POINTER(PlanDesc), _i32, _p, _p, _p, _p, _i32]),
     "epgx_simulate_sharded_f64": (_i, [ctypes.POINTER(PlanDesc), _i32, _i32, _p, _p, _i32]),
     "epgx_comm_unique_id": (_i, [_p]),
@@ -748,6 +749,34 @@ def signal_crlb(ctx, signal_ptr, record_stride, row_stride, nrow, nrec, rows, vo
                                        w.ctypes.data if w is not None else None, float(sigma2),
                                        (CRLB_SPLIT if split else 0) | (CRLB_LOG10 if log else 0), out.ptr), "epgx_signal_crlb")
         return out.download(np.float64, shape)
+    finally:
+        out.free()         # (back to the context's pool)
+
+
+def signal_crlb_grad(ctx, signal_ptr, record_stride, row_stride, nrow, nrec, rows, vox0, nvox, hess_ptr, hess_len, offsets,
+                     record_strides, weights=None, sigma2=1.0, log=False):
+    """epgx_signal_crlb_grad: the cost of `signal_crlb` and its gradient with respect to nx design variables, from second
+    derivatives in device memory (entry (c, x) of record r at hess_ptr + 16 * (offsets[c, x] + r * record_strides[c, x] +
+    voxel), offsets < 0: zero; hess_len: elements of the buffer at hess_ptr).  Returns float64 (cost [nvox], grad [nx, nvox]);
+    only these cross PCIe"""
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    step = np.ascontiguousarray(record_strides, dtype=np.int64)
+    if rows.ndim != 1 or (w is not None and w.shape != rows.shape) or off.ndim != 2 or off.shape != step.shape or off.shape[0] != len(rows):
+        raise ValueError(f"signal_crlb_grad: rows {rows.shape}, weights {None if w is None else w.shape}, offsets {off.shape} and "
+                         f"record_strides {step.shape} do not fit together")
+    nx, nvox = off.shape[1], int(nvox)
+    out = DeviceBuffer(ctx, 8 * max((1 + nx) * nvox, 1), itemsize=8)      # cost [nvox], then grad [nx][nvox]
+    try:
+        check(ctx.lib.epgx_signal_crlb_grad(ctx.handle, ctypes.c_void_p(signal_ptr) if signal_ptr else None, int(record_stride),
+                                            int(row_stride), int(nrow), int(nrec), len(rows), rows.ctypes.data, int(vox0), nvox,
+                                            ctypes.c_void_p(hess_ptr) if hess_ptr else None, int(hess_len), nx, off.ctypes.data,
+                                            step.ctypes.data, w.ctypes.data if w is not None else None, float(sigma2),
+                                            CRLB_LOG10 if log else 0, out.ptr, ctypes.c_void_p(out.ptr.value + 8 * nvox)),
+              "epgx_signal_crlb_grad")
+        both = out.download(np.float64, (1 + nx, nvox))
+        return both[0], both[1:]
     finally:
         out.free()         # (back to the context's pool)
 

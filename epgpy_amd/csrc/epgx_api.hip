@@ -1464,40 +1464,37 @@ extern "C" int epgx_signal_reduce(epgx_ctx *ctx, const void *signal, int64_t sig
 }
 
 // ------------------------------------------------------------------------------ Cramer-Rao bounds (epgx_stats.hip)
-extern "C" int epgx_signal_crlb(epgx_ctx *ctx, const void *signal, int64_t record_stride, int64_t row_stride, int32_t nrow,
-                                int32_t nrec, int32_t nparam, const int32_t *rows, int64_t vox0, int64_t nvox,
-                                const double *weights, double sigma2, int32_t flags, void *out) {
-    if (!ctx || !signal || !rows || !out) return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: NULL argument");
-    if (((uintptr_t)signal & 15) || ((uintptr_t)out & 7))
-        return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: signal must be aligned to 16 bytes, out to 8");
+// the Jacobian block, weights, sigma2 and flags of epgx_signal_crlb / epgx_signal_crlb_grad (`who`), checked and put into `a`
+// (everything but `out`); nothing here touches the device
+static int crlb_jacobian_args(const char *who, const void *signal, int64_t record_stride, int64_t row_stride, int32_t nrow, int32_t nrec,
+                              int32_t nparam, const int32_t *rows, int64_t vox0, int64_t nvox, const double *weights, double sigma2,
+                              int32_t flags, int32_t known_flags, CrlbArgs &a) {
+    if ((uintptr_t)signal & 15) return fail(EPGX_ERR_INVALID, "%s: signal must be aligned to 16 bytes", who);
     if (nparam < 1 || nparam > CRLB_MAX_P)
-        return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: nparam = %d not in [1, %d]", nparam, CRLB_MAX_P);
-    if (nrec < 1 || nrow < 1) return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: nrec = %d, nrow = %d: both must be >= 1", nrec, nrow);
+        return fail(EPGX_ERR_INVALID, "%s: nparam = %d not in [1, %d]", who, nparam, CRLB_MAX_P);
+    if (nrec < 1 || nrow < 1) return fail(EPGX_ERR_INVALID, "%s: nrec = %d, nrow = %d: both must be >= 1", who, nrec, nrow);
     if (vox0 < 0 || nvox < 0 || row_stride < 1 || nvox > row_stride - vox0)
-        return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: voxels [%lld, %lld + %lld) outside a row of %lld", (long long)vox0,
+        return fail(EPGX_ERR_INVALID, "%s: voxels [%lld, %lld + %lld) outside a row of %lld", who, (long long)vox0,
                     (long long)vox0, (long long)nvox, (long long)row_stride);
     if (record_stride / nrow < row_stride)
-        return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: record_stride = %lld holds fewer than nrow = %d rows of %lld",
+        return fail(EPGX_ERR_INVALID, "%s: record_stride = %lld holds fewer than nrow = %d rows of %lld", who,
                     (long long)record_stride, nrow, (long long)row_stride);
     int64_t span, last;      // elements from `signal` to the end of the last record: must be expressible (the kernel's pointer arithmetic)
     if (__builtin_mul_overflow((int64_t)(nrec - 1), record_stride, &span) || __builtin_mul_overflow((int64_t)nrow, row_stride, &last) ||
         __builtin_add_overflow(span, last, &span) || span > INT64_MAX / 16)
-        return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: nrec = %d records of record_stride = %lld elements overflow the address range",
+        return fail(EPGX_ERR_INVALID, "%s: nrec = %d records of record_stride = %lld elements overflow the address range", who,
                     nrec, (long long)record_stride);
-    if (flags & ~(EPGX_CRLB_SPLIT | EPGX_CRLB_LOG10)) return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: unknown flags 0x%x", flags);
-    if (!(sigma2 > 0.0) || !std::isfinite(sigma2)) return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: sigma2 = %g is not a positive finite number", sigma2);
-    CrlbArgs a;
+    if (flags & ~known_flags) return fail(EPGX_ERR_INVALID, "%s: unknown flags 0x%x", who, flags);
+    if (!(sigma2 > 0.0) || !std::isfinite(sigma2)) return fail(EPGX_ERR_INVALID, "%s: sigma2 = %g is not a positive finite number", who, sigma2);
     memset(&a, 0, sizeof(a));
     for (int c = 0; c < nparam; ++c) {
         if (rows[c] < 0 || rows[c] >= nrow)
-            return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: rows[%d] = %d not in [0, nrow = %d)", c, rows[c], nrow);
-        if (weights && !std::isfinite(weights[c])) return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: weights[%d] is not finite", c);
+            return fail(EPGX_ERR_INVALID, "%s: rows[%d] = %d not in [0, nrow = %d)", who, c, rows[c], nrow);
+        if (weights && !std::isfinite(weights[c])) return fail(EPGX_ERR_INVALID, "%s: weights[%d] is not finite", who, c);
         a.rows[c] = rows[c];
         a.w[c] = weights ? weights[c] : 1.0;
     }
-    if (nvox / 64 >= 0x7fffffff) return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: %lld voxels in one call", (long long)nvox);
-    if (nvox == 0) return EPGX_OK;
-    if (int rc = set_device(ctx)) return rc;
+    if (nvox / 64 >= 0x7fffffff) return fail(EPGX_ERR_INVALID, "%s: %lld voxels in one call", who, (long long)nvox);
     a.signal = (const d2 *)signal;
     a.record_stride = record_stride;
     a.row_stride = row_stride;
@@ -1507,9 +1504,77 @@ extern "C" int epgx_signal_crlb(epgx_ctx *ctx, const void *signal, int64_t recor
     a.inv_sigma2 = 1.0 / sigma2;
     a.flags = flags;
     crlb_slices(nrec, &a.slices, &a.slice_len);
+    return EPGX_OK;
+}
+
+extern "C" int epgx_signal_crlb(epgx_ctx *ctx, const void *signal, int64_t record_stride, int64_t row_stride, int32_t nrow,
+                                int32_t nrec, int32_t nparam, const int32_t *rows, int64_t vox0, int64_t nvox,
+                                const double *weights, double sigma2, int32_t flags, void *out) {
+    if (!ctx || !signal || !rows || !out) return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: NULL argument");
+    if ((uintptr_t)out & 7) return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: out must be aligned to 8 bytes");
+    CrlbArgs a;
+    if (int rc = crlb_jacobian_args("epgx_signal_crlb", signal, record_stride, row_stride, nrow, nrec, nparam, rows, vox0, nvox, weights,
+                                    sigma2, flags, EPGX_CRLB_SPLIT | EPGX_CRLB_LOG10, a))
+        return rc;
+    if (nvox == 0) return EPGX_OK;
+    if (int rc = set_device(ctx)) return rc;
     a.out = (double *)out;
     hipError_t e = epgx_launch_crlb(ctx->stream, nparam, a);
     if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_signal_crlb: %s", hipGetErrorString(e));
+    return EPGX_OK;
+}
+
+extern "C" int epgx_signal_crlb_grad(epgx_ctx *ctx, const void *signal, int64_t record_stride, int64_t row_stride, int32_t nrow,
+                                     int32_t nrec, int32_t nparam, const int32_t *rows, int64_t vox0, int64_t nvox,
+                                     const void *hess, int64_t hess_len, int32_t nx, const int64_t *offsets,
+                                     const int64_t *record_strides, const double *weights, double sigma2, int32_t flags,
+                                     void *out_cost, void *out_grad) {
+    const char *who = "epgx_signal_crlb_grad";
+    if (!ctx || !signal || !rows || !hess || !offsets || !record_strides || !out_cost || !out_grad)
+        return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
+    if (((uintptr_t)hess & 15) || ((uintptr_t)out_cost & 7) || ((uintptr_t)out_grad & 7))
+        return fail(EPGX_ERR_INVALID, "%s: hess must be aligned to 16 bytes, out_cost and out_grad to 8", who);
+    CrlbArgs a;
+    if (int rc = crlb_jacobian_args(who, signal, record_stride, row_stride, nrow, nrec, nparam, rows, vox0, nvox, weights, sigma2, flags,
+                                    EPGX_CRLB_LOG10, a))
+        return rc;
+    if (nx < 1) return fail(EPGX_ERR_INVALID, "%s: nx = %d must be >= 1", who, nx);
+    if (hess_len < 0 || hess_len > INT64_MAX / 16) return fail(EPGX_ERR_INVALID, "%s: hess_len = %lld", who, (long long)hess_len);
+    int64_t grad_len;
+    if (__builtin_mul_overflow((int64_t)nx, nvox, &grad_len) || grad_len > INT64_MAX / 8)
+        return fail(EPGX_ERR_INVALID, "%s: nx = %d maps of %lld voxels overflow the address range", who, nx, (long long)nvox);
+    // every entry of H that is read lies inside [hess, hess + hess_len): the kernel reads elements
+    // offset + r * stride + vox0 + j,  r < nrec, j < nvox
+    for (int64_t i = 0; i < (int64_t)nparam * nx; ++i) {
+        const int64_t off = offsets[i], step = record_strides[i];
+        if (off < 0) continue;
+        int64_t end;
+        if (step < 0 || (nrec > 1 && step < nvox) || __builtin_mul_overflow((int64_t)(nrec - 1), step, &end) ||
+            __builtin_add_overflow(end, off, &end) || __builtin_add_overflow(end, vox0, &end) || __builtin_add_overflow(end, nvox, &end) ||
+            end > hess_len)
+            return fail(EPGX_ERR_INVALID, "%s: entry (%lld, %lld) of H: offset = %lld, record stride = %lld, %d records of voxels [%lld, %lld + %lld) "
+                        "do not lie inside hess_len = %lld elements (or the records overlap)", who, (long long)(i / nx), (long long)(i % nx),
+                        (long long)off, (long long)step, nrec, (long long)vox0, (long long)vox0, (long long)nvox, (long long)hess_len);
+    }
+    if (nvox == 0) return EPGX_OK;
+    if (int rc = set_device(ctx)) return rc;
+    a.out = (double *)out_cost;
+    for (int32_t x0 = 0; x0 < nx; x0 += CRLB_GRAD_XB) {      // one launch per chunk of design variables
+        CrlbGradArgs h;
+        memset(&h, 0, sizeof(h));
+        h.hess = (const d2 *)hess;
+        h.nx = std::min<int32_t>(CRLB_GRAD_XB, nx - x0);
+        h.write_cost = x0 == 0;
+        h.grad = (double *)out_grad + (int64_t)x0 * nvox;
+        for (int x = 0; x < CRLB_GRAD_XB; ++x)
+            for (int c = 0; c < CRLB_MAX_P; ++c) {
+                const bool used = x < h.nx && c < nparam;
+                h.off[x][c] = used ? offsets[(int64_t)c * nx + x0 + x] : -1;
+                h.stride[x][c] = used ? record_strides[(int64_t)c * nx + x0 + x] : 0;
+            }
+        hipError_t e = epgx_launch_crlb_grad(ctx->stream, nparam, a, h);
+        if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
     return EPGX_OK;
 }
 

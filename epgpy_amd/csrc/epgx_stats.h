@@ -1,4 +1,4 @@
-// epgx_stats.h -- arguments and host-side launcher of the Cramer-Rao kernel (epgx_stats.hip).  Not part of the public ABI.
+// epgx_stats.h -- arguments and host-side launchers of the Cramer-Rao kernels (epgx_stats.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "epgx_kernels.hip.h"
@@ -11,6 +11,7 @@ constexpr int CRLB_SLICE = 64;             // up to this many records one wavefr
 constexpr int CRLB_MAX_SLICES = 8;         // wavefronts that share the records of a voxel (1, 2, 4 or 8)
 constexpr int CRLB_FLAG_SPLIT = 1;         // = EPGX_CRLB_SPLIT: one bound per column instead of their weighted sum
 constexpr int CRLB_FLAG_LOG10 = 2;         // = EPGX_CRLB_LOG10
+constexpr int CRLB_GRAD_XB = 4;            // design variables one crlb_grad_kernel launch takes together (G_x of XB variables in registers)
 
 struct CrlbArgs {
     const d2 *signal;             // record r, column c, voxel v at signal[r * record_stride + rows[c] * row_stride + v]
@@ -23,6 +24,16 @@ struct CrlbArgs {
     int32_t flags;
     int32_t slices, slice_len;    // crlb_slices(nrec): a function of nrec ALONE (the order of the sum must not depend on nvox)
     double *out;                  // [nvox], or with CRLB_FLAG_SPLIT [P][nvox]
+};
+
+// one chunk of up to CRLB_GRAD_XB design variables for crlb_grad_kernel, next to the CrlbArgs of the Jacobian (whose `out` is
+// the cost [nvox], written when `write_cost` is set: every chunk computes it, the first one stores it)
+struct CrlbGradArgs {
+    const d2 *hess;               // entry (a, x) of record r, voxel v at hess[off[x][a] + r * stride[x][a] + v]; off < 0: all zero
+    int64_t off[CRLB_GRAD_XB][CRLB_MAX_P], stride[CRLB_GRAD_XB][CRLB_MAX_P];
+    int32_t nx;                   // design variables of this chunk, 1 .. CRLB_GRAD_XB
+    int32_t write_cost;
+    double *grad;                 // [nx][nvox] of this chunk
 };
 
 // how the records of a voxel are cut into slices: 1 slice up to 64 records, then 2, 4, 8 -- by nrec alone, so that the
@@ -42,3 +53,5 @@ inline int crlb_voxel_groups(int slices) { return slices >= 4 ? 1 : 4 / slices; 
 
 // nparam = 1 .. CRLB_MAX_P; every other field of `a` validated by the caller (epgx_signal_crlb)
 hipError_t epgx_launch_crlb(hipStream_t stream, int nparam, const epgx::CrlbArgs &a);
+// the same for one chunk of design variables (epgx_signal_crlb_grad); CRLB_FLAG_SPLIT must not be set
+hipError_t epgx_launch_crlb_grad(hipStream_t stream, int nparam, const epgx::CrlbArgs &a, const epgx::CrlbGradArgs &h);

@@ -9,6 +9,9 @@ Two kinds of input:
   handle (its axis 0) are the points: `crlb(jac_dev, ...)` is `crlb(np.moveaxis(np.asarray(jac_dev), 0, -2), ...)`.
   This path takes `W` as a vector of `nparam` values (or None) and a scalar `sigma2`; `H`, a `W` / `sigma2` that varies over the
   grid and handles of a run over several GPUs raise `NotImplementedError` naming the argument.
+  With a `DeviceHessian` next to it (`simulate(..., probe=epg.Hessian(params, design), mode="resident", out="device")`)
+  `crlb_grad` returns the cost and its gradient with respect to the design variables: `crlb_grad_kernel` through
+  `epgx_signal_crlb_grad` reads both where they lie, and 8 (1 + nx) bytes per voxel cross PCIe.
 * **A NumPy array** `[..., npoint, nparam]` the caller already holds: the reference's formulas in NumPy, any `nparam`, `H`
   included.  Post-processing on the host, like `utils.imaging` -- not a CPU path of the simulation.
 
@@ -22,7 +25,7 @@ import math
 
 import numpy as np
 
-__all__ = ["crlb", "crlb_split", "confint"]
+__all__ = ["crlb", "crlb_grad", "crlb_split", "confint"]
 
 
 # ------------------------------------------------------------------------------------------------ device branch
@@ -36,8 +39,8 @@ def _device_kind(J):
     return None
 
 
-def _device_bounds(J, W, sigma2, log, split):
-    from . import _lib
+def _device_weights(J, W, sigma2):
+    """W as the device path takes it (a vector of nparam values or None); raises for what it does not take"""
     nparam = len(J.rows)
     if W is not None:
         W = np.asarray(W)
@@ -46,6 +49,13 @@ def _device_bounds(J, W, sigma2, log, split):
                                       f"{W.shape} ({W.dtype}); download the Jacobian for weights that vary over the grid")
     if np.ndim(sigma2) != 0 or np.iscomplexobj(sigma2):
         raise NotImplementedError("sigma2: on a DeviceJacobian a real scalar; download the Jacobian for a noise map")
+    return W
+
+
+def _device_bounds(J, W, sigma2, log, split):
+    from . import _lib
+    nparam = len(J.rows)
+    W = _device_weights(J, W, sigma2)
     buf = J._buf
     # (a handle whose buffer was freed hands over NULL: the library's EpgxError, as for a download)
     res = _lib.signal_crlb(buf.ctx, J.ptr if buf.ptr else None, J.record_stride, J.row_stride, J._nrow,
@@ -91,7 +101,8 @@ def crlb(J, H=None, *, W=None, sigma2=1, log=False):
     Returns `[...]` (device: float64 `grid`).  Singular voxels give NaN (module docstring)."""
     if _reject_handles(J):
         if H is not None:
-            raise NotImplementedError("H: the gradient of the bound is not computed on the device; download J (np.asarray) and H (a DeviceHessian downloads with np.asarray as well)")
+            raise NotImplementedError("H: crlb takes second derivatives as host arrays only; stats.crlb_grad(J, H) computes cost and "
+                                      "gradient from a DeviceJacobian and a DeviceHessian on the device (or download both with np.asarray)")
         return _device_bounds(J, W, sigma2, log, split=False)
 
     J, lb, noise = _fisher_inverse(J, sigma2)
@@ -109,6 +120,51 @@ def crlb(J, H=None, *, W=None, sigma2=1, log=False):
     if log:      # d log10(c) = dc / (c ln 10)
         return np.log10(cost), grad / (cost[..., np.newaxis] * math.log(10.0))
     return cost, grad
+
+
+MAX_DEVICE_PARAMS = 4      # CRLB_MAX_P of csrc/epgx_stats.h
+
+
+def crlb_grad(J, H, *, W=None, sigma2=1, log=False):
+    """The cost of `crlb` and its gradient with respect to nx design variables: `(cost, grad)`.
+
+    On the device: J a DeviceJacobian and H a DeviceHessian of the same run parameters -- `Jacobian(params)` and
+    `Hessian(params, design)` from two `simulate(..., out="device")` calls on one GPU, the same grid and records,
+    `J.variables == H.variables1`.  Returns float64 `cost` of shape `grid` and `grad` of shape `grid + (nx,)`, nx =
+    `len(H.variables2)`; the cost has the bits of `crlb(J, ...)`.  W a vector of nparam values or None, sigma2 a scalar, at most
+    4 parameters, as for `crlb` on a DeviceJacobian.  A singular voxel has NaN in the cost and in its whole gradient.
+    On host arrays (J `[..., npoint, nparam]`, H `[..., npoint, nparam, nx]`): exactly `crlb(J, H=H, ...)`."""
+    from . import functions, _lib
+    kinds = {}
+    for name, arg, handle in (("J", J, functions.DeviceJacobian), ("H", H, functions.DeviceHessian)):
+        if isinstance(arg, handle):
+            kinds[name] = True
+        elif isinstance(arg, (functions.DeviceSignal, functions.ShardedDeviceSignal, functions.DeviceJacobian, functions.DeviceHessian)):
+            raise NotImplementedError(f"{name}: {type(arg).__name__}; the device path takes a {handle.__name__} of a run on one GPU")
+        else:
+            kinds[name] = False
+    if not kinds["J"] and not kinds["H"]:
+        return crlb(J, H=H, W=W, sigma2=sigma2, log=log)
+    if not kinds["H"]:
+        raise NotImplementedError("H: a host array next to a DeviceJacobian; download J (np.asarray, records to axis -2) and call "
+                                  'crlb(J, H=H), or compute H with out="device" too')
+    if not kinds["J"]:
+        raise NotImplementedError("J: a host array next to a DeviceHessian; download H (np.asarray, records to axis -3) and call "
+                                  'crlb(J, H=H), or compute J with out="device" too')
+    if J._buf.ctx is not H._buf.ctx or J.device != H.device:
+        raise ValueError(f"H: lives on device {H.device} in another context than J (device {J.device}); both must come from one GPU context")
+    if J.grid != H.grid or J.nrec != H.nrec:
+        raise ValueError(f"H: {H.nrec} records over the grid {H.grid}, J has {J.nrec} records over {J.grid}")
+    if list(J.variables) != list(H.variables1):
+        raise ValueError(f"H: variables1 = {H.variables1} must be the variables of J, {J.variables}, in this order")
+    nparam = len(J.rows)
+    if nparam > MAX_DEVICE_PARAMS:
+        raise NotImplementedError(f"J: {nparam} parameters; the device path takes up to {MAX_DEVICE_PARAMS}, download J and H for more")
+    W = _device_weights(J, W, sigma2)
+    cost, grad = _lib.signal_crlb_grad(J._buf.ctx, J.ptr if J._buf.ptr else None, J.record_stride, J.row_stride, J._nrow, J.nrec, J.rows,
+                                       0, J.nvox, H.ptr if H._buf.ptr else None, H._buf.nbytes // 16, H.offsets, H.record_strides,
+                                       weights=W, sigma2=float(sigma2), log=log)
+    return cost.reshape(J.grid), np.ascontiguousarray(grad.T).reshape(J.grid + (grad.shape[0],))
 
 
 def crlb_split(J, W=None, sigma2=1, log=False):

@@ -4,8 +4,8 @@ minimising the Cramer-Rao bound of T2 (magnitude unknown as well) averaged over 
 The cost needs the Jacobian of the signal w.r.t. (magnitude, T2) and its derivative w.r.t. every angle -- a Hessian over
 (tissue parameter x design variable) pairs.  `simulate(..., mode="resident")` computes each pair in ONE launch of the fused
 second-order kernel (state, both first-order states and the second-order state of a voxel in registers) instead of hundreds
-of launches operator by operator; `stats.crlb(J, H=H)` then gives cost and gradient (on the host: the gradient form of the
-bound does not run on device handles yet).
+of launches operator by operator.  Both calls leave their records in HBM (`out="device"`; a Jacobian and a Hessian probe do not
+share a device call), and `stats.crlb_grad` computes cost and gradient there: only the two maps cross PCIe.
 
     python examples/optim_mse_crlb.py [necho] [n_T2] [steps]      # defaults 8, 32, 6
 """
@@ -34,10 +34,9 @@ def cost_and_gradient(angles):
     seq = [epg.T(90, 90)]
     for rf in pulses:
         seq += [epg.S(1), half, rf, epg.S(1), half, epg.ADC]
-    jac, hes = epg.simulate(seq, probe=[epg.Jacobian(["magnitude", "T2"]), epg.Hessian(["magnitude", "T2"], names)], mode="resident")
-    J = np.moveaxis(jac, 0, -2)              # [n_T2, necho, 2]
-    H = np.moveaxis(hes, 0, -3)              # [n_T2, necho, 2, necho]: d(dS/dp)/d(angle)
-    cost, grad = stats.crlb(J, H=H, W=[0.0, 1.0], sigma2=sigma2, log=True)
+    jac = epg.simulate(seq, probe=epg.Jacobian(["magnitude", "T2"]), out="device")                               # [necho, n_T2, 2]
+    hes = epg.simulate(seq, probe=epg.Hessian(["magnitude", "T2"], names), mode="resident", out="device")       # [necho, n_T2, 2, necho]: d(dS/dp)/d(angle)
+    cost, grad = stats.crlb_grad(jac, hes, W=[0.0, 1.0], sigma2=sigma2, log=True)
     return float(np.mean(cost)), np.mean(grad, axis=0)
 
 

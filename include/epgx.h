@@ -572,6 +572,29 @@ int epgx_signal_crlb(epgx_ctx *ctx, const void *signal, int64_t record_stride, i
                      int32_t nparam, const int32_t *rows, int64_t vox0, int64_t nvox, const double *weights, double sigma2,
                      int32_t flags, void *out);
 
+/* The cost of epgx_signal_crlb (without EPGX_CRLB_SPLIT) and its gradient with respect to nx design variables, from second
+ * derivatives that stay on the device as well (epgpy/stats.py:31-33, stats.crlb(J, H) of the reference), per voxel v:
+ *   S = lb diag(W) lb,   G_x[a][b] = sum_r Re( conj(H_rax) J_rb ),
+ *   out_cost[v - vox0]             = sum_p W_p lb_pp(v)                        -- the bits epgx_signal_crlb writes
+ *   out_grad[x * nvox + v - vox0]  = -2 / sigma2 * sum_ab S_ab G_x[a][b],     x = 0 .. nx - 1
+ * and with EPGX_CRLB_LOG10 log10(cost) and grad / (cost ln 10).  The Jacobian (signal ... nvox) as for epgx_signal_crlb.
+ * H_rax, the derivative of column a of the Jacobian with respect to design variable x in record r, is the complex128 value
+ *   hess[offsets[a * nx + x] + r * record_strides[a * nx + x] + v]
+ * (elements of 16 bytes): the layout of a DeviceHessian, whose entries lie in the passes of their variable pairs.
+ *   hess, hess_len   : DEVICE buffer and its length in elements
+ *   offsets, record_strides : host [nparam][nx]; offsets < 0: the entry is identically zero and nothing is read for it
+ *   weights, sigma2  : as for epgx_signal_crlb;  flags: EPGX_CRLB_LOG10 only
+ *   out_cost         : DEVICE, float64 [nvox];  out_grad: DEVICE, float64 [nx][nvox]
+ * A singular voxel (epgx_signal_crlb) gets NaN in the cost and in all nx gradient entries.  A voxel's bits depend on its own
+ * records, nrec and the arguments only.  One launch per 4 design variables, stream-ordered; nothing is uploaded or synchronised.
+ * Errors (nothing is launched): EPGX_ERR_INVALID for what epgx_signal_crlb refuses, EPGX_CRLB_SPLIT, nx < 1, and any entry with
+ * offset >= 0 whose last record ends outside the buffer (offset + (nrec - 1) * stride + vox0 + nvox > hess_len) or whose records
+ * overlap (nrec > 1 and stride < nvox). */
+int epgx_signal_crlb_grad(epgx_ctx *ctx, const void *signal, int64_t record_stride, int64_t row_stride, int32_t nrow, int32_t nrec,
+                          int32_t nparam, const int32_t *rows, int64_t vox0, int64_t nvox, const void *hess, int64_t hess_len,
+                          int32_t nx, const int64_t *offsets, const int64_t *record_strides, const double *weights, double sigma2,
+                          int32_t flags, void *out_cost, void *out_grad);
+
 /* Convenience for bindings that only have host arrays (what a ctypes/NumPy binding inside
  * the reference would call once per simulate()): builds the plan, runs the whole sequence
  * state-resident over the full grid, copies signal (and optionally the final state) back. */
