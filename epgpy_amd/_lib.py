@@ -151,6 +151,8 @@ SYMBOLS = {
     "epgx_signal_reduce": (_i, [_p, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _i64, _i64]),
     "epgx_signal_crlb": (_i, [_p, _p, _i64, _i64, _i32, _i32, _i32, _p, _i64, _i64, _p, _d, _i32, _p]),
     "epgx_signal_crlb_grad": (_i, [_p, _p, _i64, _i64, _i32, _i32, _i32, _p, _i64, _i64, _p, _i64, _i32, _p, _p, _p, _d, _i32, _p, _p]),
+    "epgx_signal_norms": (_i, [_p, _p, _i64, _i32, _i64, _p]),
+    "epgx_signal_match": (_i, [_p, _p, _i64, _p, _i64, _p, _i64, _i32, _i64, _i32, _p, _p, _p]),
     "epgx_simulate_f64": (_i, [_p, ctypes.POINTER(PlanDesc), _i32, _p, _p, _p, _p, _i32]),
     "epgx_simulate_sharded_f64": (_i, [ctypes.POINTER(PlanDesc), _i32, _i32, _p, _p, _i32]),
     "epgx_comm_unique_id": (_i, [_p]),
@@ -777,6 +779,46 @@ def signal_crlb_grad(ctx, signal_ptr, record_stride, row_stride, nrow, nrec, row
               "epgx_signal_crlb_grad")
         both = out.download(np.float64, (1 + nx, nvox))
         return both[0], both[1:]
+    finally:
+        out.free()         # (back to the context's pool)
+
+
+def signal_norms(ctx, dict_ptr, row_stride, nrec, natoms):
+    """epgx_signal_norms: n_a = sum_t |D[t, a]|^2 of a dictionary in device memory (atom a of record t at dict_ptr + 16 *
+    (t * row_stride + a)).  Returns the DeviceBuffer that holds float64 [natoms]; nothing crosses PCIe"""
+    out = DeviceBuffer(ctx, 8 * max(int(natoms), 1), itemsize=8)
+    try:
+        check(ctx.lib.epgx_signal_norms(ctx.handle, ctypes.c_void_p(dict_ptr) if dict_ptr else None, int(row_stride), int(nrec),
+                                        int(natoms), out.ptr), "epgx_signal_norms")
+    except Exception:
+        out.free()
+        raise
+    return out
+
+
+def match_split_bounds(natoms, nsplit):
+    """atoms [lo, hi) of every range `epgx_signal_match` cuts `natoms` atoms into (include/epgx.h): [(lo, hi)] * nsplit"""
+    q, r = divmod(int(natoms), int(nsplit))
+    return [(s * q + min(s, r), s * q + min(s, r) + q + (1 if s < r else 0)) for s in range(int(nsplit))]
+
+
+def signal_match(ctx, dict_ptr, dict_row_stride, norms_ptr, natoms, sig_ptr, sig_row_stride, nrec, nmeas, nsplit=0):
+    """epgx_signal_match: per measured voxel the best atom of a dictionary in device memory, its complex scale and score (signals
+    at sig_ptr + 16 * (t * sig_row_stride + m), `norms_ptr` from `signal_norms`; nsplit = 0: the library chooses).  Returns
+    (index int64 [nmeas], scale complex128 [nmeas], score float64 [nmeas]); only these 32 bytes per voxel cross PCIe"""
+    nmeas = int(nmeas)
+    n = max(nmeas, 1)
+    out = DeviceBuffer(ctx, 32 * n, itemsize=8)      # scale [nmeas] complex128, then index [nmeas] int64, then score [nmeas]
+    try:
+        check(ctx.lib.epgx_signal_match(ctx.handle, ctypes.c_void_p(dict_ptr) if dict_ptr else None, int(dict_row_stride),
+                                        ctypes.c_void_p(norms_ptr) if norms_ptr else None, int(natoms),
+                                        ctypes.c_void_p(sig_ptr) if sig_ptr else None, int(sig_row_stride), int(nrec), nmeas,
+                                        int(nsplit), ctypes.c_void_p(out.ptr.value + 16 * n), out.ptr,
+                                        ctypes.c_void_p(out.ptr.value + 24 * n)), "epgx_signal_match")
+        if nmeas == 0:
+            return np.empty(0, np.int64), np.empty(0, np.complex128), np.empty(0, np.float64)
+        raw = out.download(np.float64, (4 * n,))
+        return raw[2 * n:3 * n].view(np.int64), raw[:2 * n].view(np.complex128), raw[3 * n:]
     finally:
         out.free()         # (back to the context's pool)
 

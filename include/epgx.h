@@ -595,6 +595,34 @@ int epgx_signal_crlb_grad(epgx_ctx *ctx, const void *signal, int64_t record_stri
                           int32_t nx, const int64_t *offsets, const int64_t *record_strides, const double *weights, double sigma2,
                           int32_t flags, void *out_cost, void *out_grad);
 
+/* Dictionary matching on records that stay on the device (csrc/epgx_match.hip): the consumer of a dictionary left in HBM by
+ * simulate(..., out="device").  Dictionary D[t][a] = dict[t * dict_row_stride + a], records t = 0 .. nrec - 1, atoms a = 0 ..
+ * natoms - 1; measured signals S[t][m] = sig[t * sig_row_stride + m], m = 0 .. nmeas - 1; complex128, strides in elements of 16
+ * bytes.
+ *   n_a      = sum_t |D[t,a]|^2                                        (epgx_signal_norms: out[a], once per dictionary)
+ *   c[a,m]   = sum_t conj(D[t,a]) S[t,m],     q[a,m] = |c[a,m]|^2 / n_a
+ *   out_index[m] = argmax_a q[a,m] over the atoms whose n_a is a finite number > 0; among equal q the LOWEST a
+ *   out_scale[m] = c[idx,m] / n_idx             (the complex proton density: S[:,m] ~ scale D[:,idx])
+ *   out_score[m] = sqrt(q[idx,m] / sum_t |S[t,m]|^2), at most 1;  0 where the signal is identically zero
+ * Invalid atoms: an all-zero atom or one holding a NaN / Inf is never chosen.  Where no atom is valid, or the best q is not
+ * finite, the voxel gets index -1, scale 0, score 0; never an error.  (q is evaluated as (Re c^2 + Im c^2) * (1 / n_a).)
+ * Invariance: the records are consumed in steps of 4 from t = 0, the tail padded with zeros, so the bits of c[a,m] depend on
+ * column a, column m and nrec alone, and with them index, scale and score of a voxel -- not on nmeas, the voxel's place in
+ * the call, nsplit, or other atoms and voxels.
+ *   norms  : DEVICE float64 [natoms], what epgx_signal_norms wrote for this dictionary
+ *   nsplit : the atoms are cut into nsplit ranges that run side by side (a small nmeas still fills the device); range s holds
+ *            atoms [s * (natoms / nsplit) + min(s, natoms % nsplit), ... of the next s).  0: the library chooses.  Every (range,
+ *            voxel) leaves 32 bytes in scratch of the context; a second kernel reduces the ranges by the rule above.
+ *   out_index : DEVICE int64 [nmeas];  out_scale : DEVICE complex128 [nmeas];  out_score : DEVICE float64 [nmeas]
+ * Both calls are stream-ordered; nothing is uploaded or synchronised.
+ * Errors (nothing is launched): EPGX_ERR_INVALID for a NULL or misaligned pointer (16 bytes: dict, sig, out_scale; 8: the
+ * others), nrec < 1, natoms < 1, nmeas < 0, nsplit < 0 or > natoms, dict_row_stride (row_stride) < natoms, sig_row_stride <
+ * nmeas, an extent (nrec - 1) * stride + columns or a launch nsplit * ceil(nmeas / 64) that overflows.  nmeas = 0: nothing to do. */
+int epgx_signal_norms(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int64_t natoms, void *out);
+int epgx_signal_match(epgx_ctx *ctx, const void *dict, int64_t dict_row_stride, const void *norms, int64_t natoms,
+                      const void *sig, int64_t sig_row_stride, int32_t nrec, int64_t nmeas, int32_t nsplit,
+                      void *out_index, void *out_scale, void *out_score);
+
 /* Convenience for bindings that only have host arrays (what a ctypes/NumPy binding inside
  * the reference would call once per simulate()): builds the plan, runs the whole sequence
  * state-resident over the full grid, copies signal (and optionally the final state) back. */
