@@ -27,6 +27,7 @@
 #include <string>
 #include <thread>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <unordered_map>
 #include <utility>
@@ -40,6 +41,7 @@
 #include "epgx_launch.h"
 #include "epgx_launch_hess.h"
 #include "epgx_planner.h"
+#include "epgx_plan_check.h"
 #include "epgx_chain.h"
 #include "epgx_dft.h"
 #include "epgx_stats.h"
@@ -213,21 +215,15 @@ static void free_range(epgx_ctx *ctx, PackedRange &pr) {
     }
 }
 
-struct epgx_plan {
+struct epgx_plan : PlanGeometry {   // ndim, shape, strides, nvox_total, dense_spaces, x_span, x_ncomp (epgx_plan_check.h)
     epgx_ctx *ctx = nullptr;
     PlanHost host;            // the host-only part: the primitive stream and what planning reads of it (epgx_planner.h)
     int32_t deriv_flags = 0;
     std::vector<PackedRange> packed;
     double *d_coef = nullptr;
     int64_t n_coef = 0;
-    int32_t ndim = 0, n_adc = 0;
-    int64_t shape[EPGX_MAX_DIMS];
-    int64_t strides[EPGX_MAX_SPACES][EPGX_MAX_DIMS];
-    int64_t nvox_total = 0;
-    int64_t x_span = 0;         // EPGX_OP_X in the plan: voxels per block of whole compartment groups (N * ib), else 0
-    int32_t x_ncomp = 0;        // ... and its N
+    int32_t n_adc = 0;
     epgx_op *d_ops = nullptr;   // device copy of `ops` (xrun_kernel walks the primitive list), made on first use
-    uint32_t dense_spaces = 0;  // bit s: space s has the grid's own C-order strides
     // `cache_lock` guards `packed` and the vidx cache (two host threads running ranges of one plan)
     std::mutex cache_lock;
     // cached table indices for one voxel range
@@ -510,20 +506,6 @@ extern "C" int epgx_timer_stop(epgx_ctx *ctx, float *elapsed_ms) {
 }
 
 // ------------------------------------------------------------------------------ plan
-static int ncoef_expected(int opcode) {
-    switch (opcode) {
-    case EPGX_OP_T: return 8;
-    case EPGX_OP_MAT: return 10;  // 9 used, padded to 10
-    case EPGX_OP_MAT0: return 14;
-    case EPGX_OP_T0: return 12;
-    case EPGX_OP_E: return 4;
-    case EPGX_OP_PD: return 1;
-    case EPGX_OP_D: case EPGX_OP_GS: return -1;  // depends on K: checked in epgx_run
-    case EPGX_OP_X: return -1;                  // 3 N^2: checked with N below
-    default: return 0;
-    }
-}
-
 static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_ext *ext, epgx_plan **out);
 
 extern "C" int epgx_plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, epgx_plan **out) { return plan_create(ctx, d, nullptr, out); }
@@ -538,652 +520,16 @@ extern "C" int epgx_plan_create_ext(epgx_ctx *ctx, const epgx_plan_desc *d, cons
     return plan_create(ctx, d, ext, out);
 }
 
-static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_ext *ext, epgx_plan **out) {
-    if (!ctx || !d || !out) return fail(EPGX_ERR_INVALID, "epgx_plan_create: NULL argument");
-    *out = nullptr;
-    const int n_chain = ext ? ext->n_chain : 0;
-    // (the first member: readable whatever the caller's idea of the struct is)
-    if (d->struct_size != sizeof(epgx_plan_desc))
-        return fail(EPGX_ERR_INVALID, "epgx_plan_create: struct_size = %u, but epgx_plan_desc has %zu bytes in this library (ABI %d): "
-                    "set struct_size = sizeof(epgx_plan_desc) and rebuild the caller against include/epgx.h", d->struct_size,
-                    sizeof(epgx_plan_desc), EPGX_ABI_VERSION);
-    if (d->n_ops <= 0 || !d->ops) return fail(EPGX_ERR_INVALID, "epgx_plan_create: empty operator list");
-    if (d->ndim < 1 || d->ndim > EPGX_MAX_DIMS || !d->grid_shape)
-        return fail(EPGX_ERR_INVALID, "epgx_plan_create: ndim %d not in [1,%d]", d->ndim, EPGX_MAX_DIMS);
-    if (d->n_spaces < 0 || d->n_spaces > EPGX_MAX_SPACES || (d->n_spaces && !d->space_strides))
-        return fail(EPGX_ERR_UNSUPPORTED, "epgx_plan_create: %d index spaces, at most %d supported",
-                    d->n_spaces, EPGX_MAX_SPACES);
-    if (d->n_coef < 0 || (d->n_coef && !d->coef)) return fail(EPGX_ERR_INVALID, "epgx_plan_create: bad coefficient pool");
-    if (d->n_coef_generated < 0 || d->n_fuse < 0 || (d->n_fuse && !d->fuse) || d->n_assemble < 0 || (d->n_assemble && !d->assemble))
-        return fail(EPGX_ERR_INVALID, "epgx_plan_create: bad generated-table description");
-    const int64_t n_pool = d->n_coef + d->n_coef_generated;   // host part + device-generated part
-    if (n_pool >= ((int64_t)1 << 29) - 16)
-        return fail(EPGX_ERR_UNSUPPORTED, "epgx_plan_create: coefficient pool larger than 4 GiB (split the grid)");
-    if (d->n_adc < 0) return fail(EPGX_ERR_INVALID, "epgx_plan_create: n_adc < 0");
-    if (d->deriv_flags & EPGX_DERIV_SECOND) {   // a one-pair second-order pass (hess_kernel): what such a plan cannot carry, before its lists are read
-        if (d->n_vars != 2 && d->n_vars != 3)
-            return fail(EPGX_ERR_INVALID, "epgx_plan_create: EPGX_DERIV_SECOND needs n_vars = 3 (S_a, S_b, H_ab) or 2 (S_a, H_aa), got %d", d->n_vars);
-        if (!d->dops) return fail(EPGX_ERR_INVALID, "epgx_plan_create: EPGX_DERIV_SECOND without dops");
-        if (!(d->deriv_flags & EPGX_PLAN_NO_FOLD))
-            return fail(EPGX_ERR_UNSUPPORTED, "epgx_plan_create: EPGX_DERIV_SECOND without EPGX_PLAN_NO_FOLD: the run-time fold implements the first-order product rule only");
-        if (d->n_fuse > 0 || d->n_fuse_partial > 0)
-            return fail(EPGX_ERR_UNSUPPORTED, "epgx_plan_create: EPGX_DERIV_SECOND with device-generated tables (n_fuse, n_fuse_partial): epgx_fuse_partial implements the first-order product rule only");
-        if (n_chain > 0)
-            return fail(EPGX_ERR_UNSUPPORTED, "epgx_plan_create: EPGX_DERIV_SECOND with chains: a collapsed run of operators has no second-order partials");
-    }
+// The device half of plan creation.  Each step queues its work on ctx->stream and returns the first HIP error; plan_create
+// synchronises once behind the last.
 
-    const bool trace = getenv("EPGX_TRACE") != nullptr;
-    const auto tic = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (trace)
-            fprintf(stderr, "[epgx] plan_create %-12s +%.3f ms\n", what,
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tic).count());
-    };
-    epgx_plan *pl = new (std::nothrow) epgx_plan();
-    if (!pl) return fail(EPGX_ERR_NOMEM, "epgx_plan_create: host allocation failed");
-    pl->ctx = ctx;
-    pl->ndim = d->ndim;
-    pl->host.n_spaces = d->n_spaces;
-    pl->n_adc = d->n_adc;
-    pl->n_coef = d->n_coef;
-    int64_t nvox = 1;
-    for (int i = 0; i < EPGX_MAX_DIMS; ++i) pl->shape[i] = 1;
-    for (int i = 0; i < d->ndim; ++i) {
-        if (d->grid_shape[i] < 1) {
-            delete pl;
-            return fail(EPGX_ERR_INVALID, "epgx_plan_create: grid_shape[%d] < 1", i);
-        }
-        pl->shape[i] = d->grid_shape[i];
-        nvox *= d->grid_shape[i];
-        if (nvox > (int64_t)1 << 40) {
-            delete pl;
-            return fail(EPGX_ERR_UNSUPPORTED, "epgx_plan_create: grid too large");
-        }
-    }
-    pl->nvox_total = nvox;
-    // largest table index each space can produce
-    int64_t space_extent[EPGX_MAX_SPACES];
-    memset(pl->strides, 0, sizeof(pl->strides));
-    for (int s = 0; s < d->n_spaces; ++s) {
-        int64_t ext = 0;
-        for (int i = 0; i < d->ndim; ++i) {
-            int64_t st = d->space_strides[(size_t)s * EPGX_MAX_DIMS + i];
-            if (st < 0) {
-                delete pl;
-                return fail(EPGX_ERR_INVALID, "epgx_plan_create: negative stride in space %d", s);
-            }
-            pl->strides[s][i] = st;
-            ext += (pl->shape[i] - 1) * st;
-        }
-        if (ext >= ((int64_t)1 << 31)) {
-            delete pl;
-            return fail(EPGX_ERR_UNSUPPORTED, "epgx_plan_create: table of space %d too large", s);
-        }
-        space_extent[s] = ext;
-        bool dense = true;  // C-order strides of the full grid (axes of extent 1 are irrelevant)
-        int64_t acc = 1;
-        for (int i = d->ndim - 1; i >= 0; --i) {
-            if (pl->shape[i] > 1 && pl->strides[s][i] != acc) dense = false;
-            acc *= pl->shape[i];
-        }
-        if (dense) pl->dense_spaces |= 1u << s;
-    }
-    // device-assembled tables (epgx_assemble): checked first, operators and fuse recipes may refer to them
-    struct Assembled { int32_t ncoef, space; bool im_zero; };   // im_zero: column 1 of a 4-column (relaxation) table is all zero
-    std::map<int64_t, Assembled> assembled;
-    for (int i = 0; i < d->n_assemble; ++i) {
-        const epgx_assemble &as = d->assemble[i];
-        const char *why = nullptr;
-        if (as.dst_space < -1 || as.dst_space >= d->n_spaces) why = "index space out of range";
-        if (!why && (as.ncoef < 1 || as.ncoef > EPGX_MAX_ASM_COLS || as.n_src < 1 || as.n_src > EPGX_MAX_ASM_SRC)) why = "bad column / source count";
-        const int64_t entries = why ? 0 : (as.dst_space < 0 ? 0 : space_extent[as.dst_space]) + 1;
-        if (!why && (as.dst_off < d->n_coef || as.dst_off + entries * as.ncoef > n_pool)) why = "destination outside the generated part of the pool";
-        int64_t src_entries[EPGX_MAX_ASM_SRC] = {0, 0, 0, 0};
-        for (int k = 0; k < as.n_src && !why; ++k) {
-            const epgx_asm_src &sr = as.src[k];
-            int64_t last = 0;
-            for (int dd = 0; dd < d->ndim && !why; ++dd) {
-                if (sr.strides[dd] < 0) why = "negative source stride";
-                const int64_t ds = as.dst_space < 0 ? 0 : pl->strides[as.dst_space][dd];
-                if (!why && pl->shape[dd] > 1 && sr.strides[dd] != 0 && ds == 0) why = "a source varies along an axis the destination does not";
-                last += (pl->shape[dd] - 1) * sr.strides[dd];
-            }
-            if (!why && (sr.ncol < 1 || sr.off < 0 || sr.off + (last + 1) * sr.ncol > d->n_coef)) why = "source columns outside the host part of the pool";
-            src_entries[k] = last + 1;
-        }
-        for (int c = 0; c < as.ncoef && !why; ++c)
-            if (as.col_src[c] >= as.n_src || as.col_idx[c] >= as.src[as.col_src[c]].ncol) why = "column refers to a missing source column";
-        if (why) {
-            delete pl;
-            return fail(EPGX_ERR_INVALID, "epgx_plan_create: assembled table %d: %s", i, why);
-        }
-        bool im_zero = false;
-        if (as.ncoef == 4) {   // relaxation layout: is Im e0 (column 1) zero in every entry?
-            const epgx_asm_src &sr = as.src[as.col_src[1]];
-            im_zero = true;
-            for (int64_t j = 0; j < src_entries[as.col_src[1]] && im_zero; ++j) im_zero = d->coef[sr.off + j * sr.ncol + as.col_idx[1]] == 0.0;
-        }
-        assembled[as.dst_off] = {as.ncoef, as.dst_space, im_zero};
-    }
-    auto is_assembled = [&](int64_t off, int ncoef, int space) {
-        const auto hit = assembled.find(off);
-        return hit != assembled.end() && hit->second.ncoef == ncoef && hit->second.space == space;
-    };
-    // device-collapsed tables (epgx_chain): EPGX_OP_MAT0 operators may refer to their destinations
-    std::map<int64_t, int32_t> chained;   // dst_off -> dst_space
-    for (int i = 0; i < n_chain; ++i) {
-        const epgx_chain &ch = ext->chain[i];
-        const char *why = nullptr;
-        auto space_ok = [&](int sp) { return sp >= -1 && sp < d->n_spaces; };
-        auto entries_of = [&](int sp) { return (sp < 0 ? 0 : space_extent[sp]) + 1; };
-        if (!space_ok(ch.dst_space)) why = "index space of the destination out of range";
-        if (!why && (ch.n_steps < 1 || !ch.steps)) why = "no steps";
-        if (!why && (ch.dst_off < d->n_coef || ch.dst_off + entries_of(ch.dst_space) * 14 > n_pool)) why = "destination outside the generated part of the pool";
-        int64_t reps = 1;   // repetitions of the group the current step belongs to
-        for (int k = 0, left = 0; !why && k < ch.n_steps; ++k, --left) {
-            const epgx_chain_step &st = ch.steps[k];
-            if (left == 0) {   // first step of a group
-                if (st.group < 1 || st.group > EPGX_CHAIN_GROUP || k + st.group > ch.n_steps || st.count < 1) why = "malformed group (1 .. EPGX_CHAIN_GROUP steps inside the list, count >= 1)";
-                left = st.group;
-                reps = st.count;
-            }
-            if (why) break;
-            const int nc = st.kind == EPGX_OP_T ? 8 : (st.kind == EPGX_OP_MAT ? 10 : (st.kind == EPGX_OP_MAT0 ? 14 : (st.kind == EPGX_OP_E ? 4 : 0)));
-            if (!nc) why = "unknown kind of source (EPGX_OP_T, EPGX_OP_MAT, EPGX_OP_MAT0 or EPGX_OP_E)";
-            if (!why && !space_ok(st.space)) why = "index space of a source out of range";
-            if (!why && (st.off < 0 || st.stride < 0)) why = "negative source offset or stride";
-            if (!why && !(is_assembled(st.off, nc, st.space) && (st.stride == 0 || reps == 1)) &&
-                st.off + (reps - 1) * st.stride + entries_of(st.space) * nc > d->n_coef)
-                why = "source neither inside the host part of the pool nor an assembled table";
-            for (int dd = 0; dd < d->ndim && !why; ++dd) {
-                const int64_t ds = ch.dst_space < 0 ? 0 : pl->strides[ch.dst_space][dd];
-                const int64_t ss = st.space < 0 ? 0 : pl->strides[st.space][dd];
-                if (pl->shape[dd] > 1 && ds == 0 && ss != 0) why = "a source varies along an axis the destination does not";
-            }
-        }
-        if (why) {
-            delete pl;
-            return fail(EPGX_ERR_INVALID, "epgx_plan_create: collapsed table %d: %s", i, why);
-        }
-        chained[ch.dst_off] = ch.dst_space;
-    }
-    auto is_chained = [&](const epgx_op &op) {
-        const auto hit = chained.find(op.coef_off);
-        return op.opcode == EPGX_OP_MAT0 && hit != chained.end() && hit->second == op.space;
-    };
-    pl->host.ops.assign(d->ops, d->ops + d->n_ops);
-    for (int i = 0; i < d->n_ops; ++i) {
-        const epgx_op &op = pl->host.ops[i];
-        const char *why = nullptr;
-        if (op.opcode < 0 || op.opcode >= EPGX_OP__COUNT) why = "unknown opcode";
-        int need = why ? 0 : ncoef_expected(op.opcode);
-        if (!why && need >= 0 && op.ncoef != need) why = "wrong ncoef for opcode";
-        if (!why && need < 0 && op.ncoef <= 0) why = "table-driven operator without a table";
-        if (!why && need) {
-            if (op.space < -1 || op.space >= d->n_spaces) why = "index space out of range";
-            int64_t last = op.space < 0 ? 0 : space_extent[op.space];
-            if (!why && (op.coef_off < 0 || op.coef_off + (last + 1) * (int64_t)op.ncoef > n_pool))
-                why = "coefficient table exceeds the pool";
-        }
-        if (!why && need && op.opcode != EPGX_OP_T0 && !is_assembled(op.coef_off, op.ncoef, op.space) && !is_chained(op) &&
-            op.coef_off + (op.space < 0 ? 1 : space_extent[op.space] + 1) * (int64_t)op.ncoef > d->n_coef)
-            why = "a table in the generated part of the pool needs a recipe (epgx_assemble, epgx_chain for EPGX_OP_MAT0, or epgx_fuse for EPGX_OP_T0)";
-        if (!why && op.opcode == EPGX_OP_S) {
-            if (op.ia == 0) why = "shift by 0";
-            if (op.ia >= EPGX_MAX_K || op.ia <= -EPGX_MAX_K) why = "shift exceeds EPGX_MAX_K";
-            if (op.ib < 0) why = "negative truncation order";
-        }
-        if (!why && op.opcode == EPGX_OP_X) {
-            // N compartments at stride ib: the grid axis of extent N behind which the grid holds ib voxels
-            int ax = -1;
-            int64_t behind = 1;
-            for (int dd = d->ndim - 1; dd >= 0 && ax < 0; --dd) {
-                if (pl->shape[dd] == op.ia && behind == op.ib) ax = dd;
-                behind *= pl->shape[dd];
-            }
-            if (op.ia < 2 || op.ia > 8) why = "exchange between 2 .. 8 compartments";
-            else if (op.ncoef != 3 * op.ia * op.ia) why = "X table needs 3 N^2 doubles per entry";
-            else if (ax < 0) why = "no grid axis of extent N = ia with ib voxels behind it";
-            else if (pl->x_span && pl->x_span != (int64_t)op.ia * op.ib) why = "X operators of one plan must share N and the compartment axis";
-            else {
-                pl->x_span = (int64_t)op.ia * op.ib;
-                pl->x_ncomp = op.ia;
-            }
-        }
-        if (!why && op.opcode == EPGX_OP_ADC) {
-            if (op.ia < 0 || op.ia >= d->n_adc) why = "ADC slot out of range";
-            if (op.ib != 0 && op.ib != 1) why = "unknown ADC probe";
-        }
-        if (why) {
-            const int opcode = op.opcode;   // `op` lives in the plan that is about to go
-            delete pl;
-            return fail(EPGX_ERR_INVALID, "epgx_plan_create: operator %d (opcode %d): %s", i, opcode, why);
-        }
-    }
-    if (d->n_vars < 0 || d->n_vars > EPGX_MAX_VARS || (d->n_vars > 0 && !d->dops)) {
-        delete pl;
-        return fail(EPGX_ERR_INVALID, "epgx_plan_create: n_vars=%d (at most %d) or dops missing", d->n_vars, EPGX_MAX_VARS);
-    }
-    pl->host.n_vars = d->n_vars;
-    pl->deriv_flags = d->deriv_flags;
-    if (d->deriv_flags & EPGX_DERIV_SECOND) {   // a one-pair second-order pass (hess_kernel)
-        const char *why = nullptr;
-        int code = EPGX_ERR_UNSUPPORTED;
-        for (int i = 0; i < d->n_ops && !why; ++i) {
-            const epgx_dop &dp = d->dops[i];
-            if (pl->host.ops[i].opcode == EPGX_OP_T0) why = "EPGX_DERIV_SECOND with an EPGX_OP_T0 operator: the constant term of a fused table has no second-order partial";
-            else if (pl->host.ops[i].opcode == EPGX_OP_X) why = "EPGX_DERIV_SECOND with exchange (EPGX_OP_X)";
-            else if ((dp.reserved & ~(EPGX_HESS_CROSS_A | EPGX_HESS_CROSS_B)) || ((dp.reserved & EPGX_HESS_CROSS_A) && dp.coef_off[0] < 0) ||
-                     ((dp.reserved & EPGX_HESS_CROSS_B) && (d->n_vars != 3 || dp.coef_off[1] < 0))) {
-                why = "EPGX_DERIV_SECOND: a cross-term bit (epgx_dop::reserved) without its first-order partial";
-                code = EPGX_ERR_INVALID;
-            }
-        }
-        if (why) {
-            delete pl;
-            return fail(code, "epgx_plan_create: %s", why);
-        }
-        pl->host.second = true;
-    }
-    {
-        const int env = knobs().fold ? 1 : 0;   // (EPGX_FOLD=0: measurements)
-        pl->host.fold = env != 0 && !(d->deriv_flags & EPGX_PLAN_NO_FOLD) && d->n_vars == 0;
-    }
-    if (d->n_vars > 0) {
-        pl->host.dops.assign(d->dops, d->dops + d->n_ops);
-        for (int i = 0; i < d->n_ops; ++i) {
-            const epgx_op &op = pl->host.ops[i];
-            for (int v = 0; v < EPGX_MAX_VARS; ++v) {
-                const int64_t off = pl->host.dops[i].coef_off[v];
-                if (off < 0) continue;
-                const char *why = nullptr;
-                int nc = 0;
-                if (v >= d->n_vars) why = "partial for a variable beyond n_vars";
-                else if (op.opcode == EPGX_OP_T || op.opcode == EPGX_OP_MAT || op.opcode == EPGX_OP_MAT0 || op.opcode == EPGX_OP_T0) nc = 10;
-                else if (op.opcode == EPGX_OP_E) nc = 4;
-                else why = "only T / MAT / E operators can carry partial derivatives";
-                const int sp = pl->host.dops[i].space[v];
-                if (!why && (sp < -1 || sp >= d->n_spaces)) why = "index space of a partial out of range";
-                if (!why) {
-                    const int64_t last = sp < 0 ? 0 : space_extent[sp];
-                    if (op.opcode == EPGX_OP_T0 && off >= d->n_coef) {   // generated next to the table itself (epgx_fuse_partial)
-                        if (off + (last + 1) * 14 > n_pool) why = "generated partial table exceeds the pool";
-                    } else if (is_assembled(off, nc, sp)) {              // assembled on the device from per-axis columns (epgx_assemble)
-                    } else if (off + (last + 1) * nc > d->n_coef) why = "partial table exceeds the host part of the pool";
-                }
-                if (why) {
-                    delete pl;
-                    return fail(EPGX_ERR_INVALID, "epgx_plan_create: operator %d, variable %d: %s", i, v, why);
-                }
-            }
-            if (op.opcode == EPGX_OP_ADC && op.ia + d->n_vars >= d->n_adc) {
-                delete pl;
-                return fail(EPGX_ERR_INVALID, "epgx_plan_create: operator %d: ADC rows [%d,%d] exceed n_adc=%d", i,
-                            op.ia, op.ia + d->n_vars, d->n_adc);
-            }
-        }
-    }
-    // exact-zero patterns that let the kernel drop products without changing a single bit:
-    // T(alpha, 0): Im m01 = Re m02 = Re m20 = 0;  E with g = 0: Im e0 = 0
-    // device-generated tables: check the references, derive their zero pattern from the sources
-    std::map<int64_t, uint8_t> generated_pattern;   // dst_off -> 1 if the phi = 0 pattern holds
-    // Zero patterns of rotation tables (they select shorter fma chains in the kernels):
-    //   1 "TX": Im m01 = Re m02 = Re m20 (= Re o0) = 0 -- rotations about x, phi = 0 or 180 deg
-    //   3 "TY": Im m01 = Im m02 = Im m20 (= Im o0) = 0 -- real matrices, phi = +-90 deg
-    // The reference computes e^{i phi} with phi in radians, so only phi = 0 gives exact zeros:
-    // cos(pi/2) = 6e-17, sin(pi) = 1.2e-16.  A component below 2^-48 (3.6e-15) of its own entry's
-    // modulus in EVERY entry of the table counts as the rounding residue it is and is cleared in the
-    // device copy of the table (snap list below), so that every kernel sees exact zeros: a deviation
-    // of <= 4e-15 relative from the reference's arithmetic, against a parity bar of 1e-6.
-    struct Snap { int64_t off; int64_t entries; int nc; uint32_t mask; };
-    std::vector<Snap> snaps;
-    auto t_pattern = [&](int64_t off, int space, int nc) -> uint8_t {
-        const int64_t entries = (space < 0 ? 0 : space_extent[space]) + 1;
-        const double *tab = d->coef + off;
-        const double tol = 1.0 / 281474976710656.0;   // 2^-48
-        bool tx = true, ty = true, exact_x = true, exact_y = true;
-        // is `v` (the other component of the same complex entry: `w`) zero / a rounding residue?  (hypot only when needed)
-        auto residue = [&](double v, double w, bool &exact) {
-            if (v == 0.0) return true;
-            exact = false;
-            return std::fabs(v) <= tol * std::hypot(v, w);
-        };
-        for (int64_t j = 0; j < entries && (tx || ty); ++j) {
-            const double *c = tab + j * nc;
-            bool ep = true;
-            const bool im_p = residue(c[2], c[1], ep);
-            exact_x = exact_x && ep;
-            exact_y = exact_y && ep;
-            tx = tx && im_p && residue(c[3], c[4], exact_x) && residue(c[5], c[6], exact_x) && (nc == 8 || residue(c[8], c[9], exact_x));
-            ty = ty && im_p && residue(c[4], c[3], exact_y) && residue(c[6], c[5], exact_y) && (nc == 8 || residue(c[9], c[8], exact_y));
-        }
-        if (tx) {
-            if (!exact_x) snaps.push_back({off, entries, nc, (1u << 2) | (1u << 3) | (1u << 5) | (nc == 12 ? 1u << 8 : 0u)});
-            return 1;
-        }
-        if (ty) {
-            if (!exact_y) snaps.push_back({off, entries, nc, (1u << 2) | (1u << 4) | (1u << 6) | (nc == 12 ? 1u << 9 : 0u)});
-            return 3;
-        }
-        return 0;
-    };
-    // relaxation table without a precession term (Im e0 == 0 in every entry)?  Scanned once per table; a table over a
-    // 1024 x 1024 grid is 34 MB, so large tables are split over a few threads
-    std::map<std::pair<int64_t, int32_t>, bool> e_real_known;
-    auto e_is_real = [&](int64_t off, int space) {
-        if (off >= d->n_coef) {   // assembled on the device: known from its column
-            const auto as = assembled.find(off);
-            return as != assembled.end() && as->second.ncoef == 4 && as->second.im_zero;
-        }
-        const auto key = std::make_pair(off, (int32_t)(space + 1));
-        const auto hit = e_real_known.find(key);
-        if (hit != e_real_known.end()) return hit->second;
-        const int64_t entries = (space < 0 ? 0 : space_extent[space]) + 1;
-        const double *tab = d->coef + off;
-        std::atomic<bool> real{true};
-        auto scan = [&](int64_t j0, int64_t j1) {
-            for (int64_t j = j0; j < j1; ++j)
-                if (tab[j * 4 + 1] != 0.0) {
-                    real.store(false, std::memory_order_relaxed);
-                    return;
-                }
-        };
-        const int nthreads = entries >= (1 << 17) ? 4 : 1;
-        if (nthreads == 1) scan(0, entries);
-        else {
-            std::vector<std::thread> pool;
-            for (int t = 0; t < nthreads; ++t) pool.emplace_back(scan, entries * t / nthreads, entries * (t + 1) / nthreads);
-            for (auto &th : pool) th.join();
-        }
-        e_real_known[key] = real.load();
-        return real.load();
-    };
-    std::map<std::pair<int64_t, int32_t>, uint8_t> scanned;  // a table referenced by many operators / recipes is scanned once
-    auto t_pattern_once = [&](int64_t off, int space, int nc) -> uint8_t {
-        const auto key = std::make_pair(off, (int32_t)(nc * 8 + space + 1));
-        const auto hit = scanned.find(key);
-        if (hit != scanned.end()) return hit->second;
-        const uint8_t pat = t_pattern(off, space, nc);
-        scanned[key] = pat;
-        return pat;
-    };
-    for (int i = 0; i < d->n_fuse; ++i) {
-        const epgx_fuse &fu = d->fuse[i];
-        const char *why = nullptr;
-        auto space_ok = [&](int sp) { return sp >= -1 && sp < d->n_spaces; };
-        auto ext = [&](int sp) { return (sp < 0 ? 0 : space_extent[sp]) + 1; };
-        if (!space_ok(fu.dst_space) || !space_ok(fu.src_space) || !space_ok(fu.e_space)) why = "index space out of range";
-        if (!why && fu.src_ncoef != 8 && fu.src_ncoef != 12) why = "source must have 8 or 12 coefficients";
-        if (!why && (fu.dst_off < d->n_coef || fu.dst_off + ext(fu.dst_space) * 12 > n_pool)) why = "destination outside the generated part of the pool";
-        if (!why && !is_assembled(fu.e_off, 4, fu.e_space) && (fu.e_off < 0 || fu.e_off + ext(fu.e_space) * 4 > d->n_coef))
-            why = "E source neither in the host part of the pool nor an assembled table";
-        if (!why && (fu.src_off < 0 || fu.src_off + ext(fu.src_space) * fu.src_ncoef > n_pool)) why = "rotation source outside the pool";
-        if (!why && fu.src_off >= d->n_coef && (fu.src_ncoef != 12 || !generated_pattern.count(fu.src_off)))
-            why = "a generated source must be the destination of an earlier entry";
-        if (!why)
-            for (int dd = 0; dd < d->ndim && !why; ++dd) {
-                const int64_t ds = fu.dst_space < 0 ? 0 : pl->strides[fu.dst_space][dd];
-                const int64_t ss = fu.src_space < 0 ? 0 : pl->strides[fu.src_space][dd];
-                const int64_t es = fu.e_space < 0 ? 0 : pl->strides[fu.e_space][dd];
-                if (pl->shape[dd] > 1 && ds == 0 && (ss != 0 || es != 0)) why = "a source varies along an axis the destination does not";
-            }
-        if (!why && !e_is_real(fu.e_off, fu.e_space)) why = "E source has a precession term (Im e0 != 0)";
-        if (why) {
-            delete pl;
-            return fail(EPGX_ERR_INVALID, "epgx_plan_create: generated table %d: %s", i, why);
-        }
-        generated_pattern[fu.dst_off] = fu.src_off >= d->n_coef ? generated_pattern[fu.src_off]
-                                                                : t_pattern_once(fu.src_off, fu.src_space, fu.src_ncoef);
-    }
-    // zero pattern of a partial-derivative table in the host part of the pool (scanned once per table):
-    //   relaxation (4 per entry):  1 = Im d e0 = 0 in every entry
-    //   rotation (10 per entry, ur ui pr pi qr qi tr ti c22): the partial of a rotation about x (phi = 0) or y (phi = +-90) has
-    //   the zero pattern of its operator: 1 = Im m00 = Im m01 = Re m02 = Re m20 = 0, 2 = all Im = 0 -- exact, or rounding
-    //   residues of e^{i phi} (below 2^-48 of their entry's modulus in every entry), which are then cleared in the device
-    //   copy like those of the operator tables (snap_kernel)
-    std::map<std::pair<int64_t, int32_t>, uint8_t> dscanned;
-    auto d_pattern_once = [&](int64_t off, int sp, bool is_e) -> uint8_t {
-        const auto key = std::make_pair(off, (int32_t)((is_e ? 8 : 0) + sp + 1));
-        const auto hit = dscanned.find(key);
-        if (hit != dscanned.end()) return hit->second;
-        if (off >= d->n_coef) {   // assembled on the device: a relaxation partial's pattern is known from its column, a rotation's is general
-            const auto as = assembled.find(off);
-            const uint8_t pat_as = (is_e && as != assembled.end() && as->second.ncoef == 4 && as->second.im_zero) ? 1 : 0;
-            dscanned[key] = pat_as;
-            return pat_as;
-        }
-        const int64_t entries = (sp < 0 ? 0 : space_extent[sp]) + 1;
-        const int nc = is_e ? 4 : 10;
-        const double *tab = d->coef + off;
-        uint8_t pat = 0;
-        if (is_e) {
-            bool zero = true;
-            for (int64_t j = 0; j < entries && zero; ++j) zero = tab[j * nc + 1] == 0.0;
-            pat = zero ? 1 : 0;
-        } else {
-            const double tol = 1.0 / 281474976710656.0;
-            bool tx = true, ty = true, exact_x = true, exact_y = true;
-            auto residue = [&](double x, double w, bool &exact) {
-                if (x == 0.0) return true;
-                exact = false;
-                return std::fabs(x) <= tol * std::hypot(x, w);
-            };
-            for (int64_t j = 0; j < entries && (tx || ty); ++j) {
-                const double *c = tab + j * nc;
-                bool e0 = true;
-                const bool diag = residue(c[1], c[0], e0) && residue(c[3], c[2], e0);   // Im m00, Im m01
-                exact_x = exact_x && e0;
-                exact_y = exact_y && e0;
-                tx = tx && diag && residue(c[4], c[5], exact_x) && residue(c[6], c[7], exact_x);
-                ty = ty && diag && residue(c[5], c[4], exact_y) && residue(c[7], c[6], exact_y);
-            }
-            if (tx) {
-                pat = 1;
-                if (!exact_x) snaps.push_back({off, entries, nc, (1u << 1) | (1u << 3) | (1u << 4) | (1u << 6)});
-            } else if (ty) {
-                pat = 2;
-                if (!exact_y) snaps.push_back({off, entries, nc, (1u << 1) | (1u << 3) | (1u << 5) | (1u << 7)});
-            }
-        }
-        dscanned[key] = pat;
-        return pat;
-    };
-    // partials of generated tables (epgx_fuse_partial): references checked, zero pattern derived from the sources
-    std::map<int64_t, uint8_t> generated_dpattern;   // dst_off -> 1 (phi = 0 pattern) / 2 (real matrix) / 0
-    if (d->n_fuse_partial < 0 || (d->n_fuse_partial > 0 && (!d->fuse_partial || d->n_vars == 0))) {
-        delete pl;
-        return fail(EPGX_ERR_INVALID, "epgx_plan_create: n_fuse_partial=%d without a list or without variables", d->n_fuse_partial);
-    }
-    for (int i = 0; i < d->n_fuse_partial; ++i) {
-        const epgx_fuse_partial &fp = d->fuse_partial[i];
-        const char *why = nullptr;
-        auto space_ok = [&](int sp) { return sp >= -1 && sp < d->n_spaces; };
-        auto ext = [&](int sp) { return (sp < 0 ? 0 : space_extent[sp]) + 1; };
-        const bool has_dt = fp.dsrc_off >= 0, has_de = fp.de_off >= 0;
-        if (!space_ok(fp.dst_space) || !space_ok(fp.src_space) || !space_ok(fp.e_space) || (has_dt && !space_ok(fp.dsrc_space)) ||
-            (has_de && !space_ok(fp.de_space)))
-            why = "index space out of range";
-        if (!why && !has_dt && !has_de) why = "neither the rotation nor the relaxation has a partial";
-        if (!why && fp.src_ncoef != 8 && fp.src_ncoef != 12) why = "rotation source must have 8 or 12 coefficients";
-        if (!why && has_dt && fp.dsrc_ncoef != 10 && fp.dsrc_ncoef != 14) why = "rotation partial must have 10 or 14 coefficients";
-        if (!why && (fp.dst_off < d->n_coef || fp.dst_off + ext(fp.dst_space) * 14 > n_pool)) why = "destination outside the generated part of the pool";
-        if (!why && (fp.src_off < 0 || fp.src_off + ext(fp.src_space) * fp.src_ncoef > n_pool)) why = "rotation source outside the pool";
-        if (!why && fp.src_off >= d->n_coef && (fp.src_ncoef != 12 || !generated_pattern.count(fp.src_off)))
-            why = "a generated rotation source must be the destination of an entry of `fuse`";
-        if (!why && !is_assembled(fp.e_off, 4, fp.e_space) && (fp.e_off < 0 || fp.e_off + ext(fp.e_space) * 4 > d->n_coef))
-            why = "E source neither in the host part of the pool nor an assembled table";
-        if (!why && !e_is_real(fp.e_off, fp.e_space)) why = "E source has a precession term (Im e0 != 0)";
-        if (!why && has_dt) {
-            if (fp.dsrc_ncoef == 10 ? fp.dsrc_off + ext(fp.dsrc_space) * 10 > d->n_coef
-                                    : (fp.dsrc_off < d->n_coef || !generated_dpattern.count(fp.dsrc_off) || fp.dsrc_off + ext(fp.dsrc_space) * 14 > n_pool))
-                why = "rotation partial: 10 per entry in the host part of the pool, or 14 per entry written by an earlier entry";
-        }
-        if (!why && has_de && !is_assembled(fp.de_off, 4, fp.de_space) && fp.de_off + ext(fp.de_space) * 4 > d->n_coef)
-            why = "E partial outside the host part of the pool (and not an assembled table)";
-        if (!why && has_de && d_pattern_once(fp.de_off, fp.de_space, true) != 1) why = "E partial has a precession term (Im d e0 != 0)";
-        if (!why)
-            for (int dd = 0; dd < d->ndim && !why; ++dd) {
-                auto str = [&](int sp) { return sp < 0 ? (int64_t)0 : pl->strides[sp][dd]; };
-                if (pl->shape[dd] > 1 && str(fp.dst_space) == 0 &&
-                    (str(fp.src_space) != 0 || str(fp.e_space) != 0 || (has_dt && str(fp.dsrc_space) != 0) || (has_de && str(fp.de_space) != 0)))
-                    why = "a source varies along an axis the destination does not";
-            }
-        if (why) {
-            delete pl;
-            return fail(EPGX_ERR_INVALID, "epgx_plan_create: generated partial %d: %s", i, why);
-        }
-        const uint8_t vp = fp.src_off >= d->n_coef ? generated_pattern[fp.src_off] : t_pattern_once(fp.src_off, fp.src_space, fp.src_ncoef);
-        const uint8_t dp = !has_dt ? (uint8_t)255 : (fp.dsrc_ncoef == 14 ? generated_dpattern[fp.dsrc_off] : d_pattern_once(fp.dsrc_off, fp.dsrc_space, false));
-        generated_dpattern[fp.dst_off] = (vp == 1 && (dp == 1 || dp == 255)) ? 1 : ((vp == 3 && (dp == 2 || dp == 255)) ? 2 : 0);
-    }
-    lap("validated");
-    pl->host.zero_pattern.assign((size_t)d->n_ops, 0);
-    for (int i = 0; i < d->n_ops; ++i) {
-        const epgx_op &op = pl->host.ops[i];
-        if (op.opcode != EPGX_OP_T && op.opcode != EPGX_OP_T0 && op.opcode != EPGX_OP_E) continue;
-        if (op.opcode == EPGX_OP_E) {
-            pl->host.zero_pattern[i] = e_is_real(op.coef_off, op.space) ? 2 : 0;
-            continue;
-        }
-        if (op.coef_off >= d->n_coef && op.opcode != EPGX_OP_T0 && is_assembled(op.coef_off, op.ncoef, op.space)) {
-            pl->host.zero_pattern[i] = 0;   // an assembled rotation table: general chains (no host copy to scan)
-            continue;
-        }
-        if (op.coef_off >= d->n_coef) {   // generated on the device: pattern known from its sources
-            const auto g = generated_pattern.find(op.coef_off);
-            if (g == generated_pattern.end() || op.opcode != EPGX_OP_T0) {
-                delete pl;
-                return fail(EPGX_ERR_INVALID, "epgx_plan_create: operator %d refers to the generated part of the pool but no entry of `fuse` writes there", i);
-            }
-            pl->host.zero_pattern[i] = g->second;
-            continue;
-        }
-        pl->host.zero_pattern[i] = t_pattern_once(op.coef_off, op.space, op.ncoef);
-    }
-    if (d->n_vars > 0) {
-        pl->host.dpattern.assign((size_t)d->n_ops, 0);
-        for (int i = 0; i < d->n_ops; ++i)
-            for (int v = 0; v < d->n_vars; ++v) {
-                const int64_t off = pl->host.dops[i].coef_off[v];
-                if (off < 0) continue;
-                if (off >= d->n_coef && pl->host.ops[i].opcode == EPGX_OP_T0) {   // a generated partial (checked above): pattern known from its sources
-                    const auto g = generated_dpattern.find(off);
-                    if (g == generated_dpattern.end()) {
-                        delete pl;
-                        return fail(EPGX_ERR_INVALID, "epgx_plan_create: operator %d, variable %d: the partial refers to the generated part of the pool but no entry of `fuse_partial` writes there", i, v);
-                    }
-                    pl->host.dpattern[i] |= (uint16_t)(((g->second & 3u) << (2 * v)) | (256u << v));
-                    continue;
-                }
-                pl->host.dpattern[i] |= (uint16_t)((d_pattern_once(off, pl->host.dops[i].space[v], pl->host.ops[i].opcode == EPGX_OP_E) & 3u) << (2 * v));
-            }
-    }
-    lap("zero scan");
-    pl->host.gather_tables.resize((size_t)d->n_ops);
-    for (int i = 0; i < d->n_ops; ++i) {
-        const epgx_op &op = pl->host.ops[i];
-        if (op.opcode != EPGX_OP_GS) continue;
-        if (op.space >= 0) {
-            delete pl;
-            return fail(EPGX_ERR_UNSUPPORTED, "epgx_plan_create: operator %d: gather shifts must be the same for all voxels", i);
-        }
-        const int32_t *src = (const int32_t *)(d->coef + op.coef_off);
-        pl->host.gather_tables[i].assign(src, src + 2 * (size_t)op.ncoef);
-    }
-    int rc = set_device(ctx);
-    if (rc) { delete pl; return rc; }
-    lap("host done");
-    hipError_t e = hipSuccess;
+// the pool with its padding and the room of the log tables behind it; the host part uploaded, its rounding residues cleared
+static hipError_t upload_pool(epgx_ctx *ctx, epgx_plan *pl, const epgx_plan_desc *d, const std::vector<Snap> &snaps) {
     // pool padded so that the fixed-width scalar loads of the last entry stay in bounds
-    pl->host.n_pool = n_pool;
-    // derivative plans that may fold (drun_kernel): a table of logarithmic partials per (real relaxation table, real partial
-    // table over the same index space)
-    struct LogJob { int64_t e_off, de_off, entries; };
-    std::vector<LogJob> log_jobs;
-    {
-        const int env = knobs().fold ? 1 : 0;
-        if (d->n_vars > 0 && env != 0 && !(d->deriv_flags & EPGX_PLAN_NO_FOLD)) {
-            pl->host.log_of.assign((size_t)d->n_ops * EPGX_MAX_VARS, -1);
-            std::map<std::pair<int64_t, int64_t>, int32_t> seen;
-            for (int i = 0; i < d->n_ops; ++i) {
-                const epgx_op &op = pl->host.ops[i];
-                if (op.opcode != EPGX_OP_E || op.ncoef != 4 || pl->host.zero_pattern[i] != 2) continue;
-                for (int v = 0; v < d->n_vars; ++v) {
-                    const int64_t doff = pl->host.dops[i].coef_off[v];
-                    if (doff < 0 || ((pl->host.dpattern[i] >> (2 * v)) & 3u) != 1u || pl->host.dops[i].space[v] != op.space) continue;
-                    const auto key = std::make_pair((int64_t)op.coef_off, doff);
-                    auto it = seen.find(key);
-                    if (it == seen.end()) {
-                        LogTab lt;
-                        lt.off = n_pool + 32 + pl->host.n_log;
-                        lt.space = op.space;
-                        const int64_t entries = (op.space < 0 ? 0 : space_extent[op.space]) + 1;
-                        pl->host.n_log += 2 * entries;
-                        log_jobs.push_back({op.coef_off, doff, entries});
-                        it = seen.emplace(key, (int32_t)pl->host.logtabs.size()).first;
-                        pl->host.logtabs.push_back(lt);
-                    }
-                    pl->host.log_of[(size_t)i * EPGX_MAX_VARS + v] = it->second;
-                }
-            }
-            // fused echoes: walk the epgx_fuse_partial chain behind every generated partial of an EPGX_OP_T0 operator
-            if (d->n_fuse_partial > 0) {
-                std::map<int64_t, int> recipe_of;
-                for (int k = 0; k < d->n_fuse_partial; ++k) recipe_of[d->fuse_partial[k].dst_off] = k;
-                pl->host.t0_log.assign((size_t)d->n_ops * EPGX_MAX_VARS * 2, -1);
-                pl->host.t0_logd.assign((size_t)d->n_ops * EPGX_MAX_VARS, 0);
-                std::map<std::pair<int64_t, int>, std::pair<int32_t, int32_t>> walked;   // (partial offset) -> (a, b), -2: not logarithmic
-                for (int i = 0; i < d->n_ops; ++i) {
-                    if (pl->host.ops[i].opcode != EPGX_OP_T0) continue;
-                    for (int v = 0; v < d->n_vars; ++v) {
-                        const int64_t doff = pl->host.dops[i].coef_off[v];
-                        if (doff < d->n_coef) continue;   // (no partial, or not a generated one)
-                        const auto wkey = std::make_pair(doff, 0);
-                        auto w = walked.find(wkey);
-                        if (w == walked.end()) {
-                            int32_t side[2] = {-1, -1};
-                            bool ok = true;
-                            int64_t cur = doff;
-                            for (int depth = 0; ok && depth < 8; ++depth) {
-                                const auto r = recipe_of.find(cur);
-                                if (r == recipe_of.end()) { ok = false; break; }
-                                const epgx_fuse_partial &fp = d->fuse_partial[r->second];
-                                if (fp.de_off >= 0) {
-                                    const int which = fp.after ? 0 : 1;
-                                    if (side[which] != -1 || fp.de_space != fp.e_space) { ok = false; break; }
-                                    const auto key = std::make_pair((int64_t)fp.e_off, (int64_t)fp.de_off);
-                                    auto it = seen.find(key);
-                                    if (it == seen.end()) {
-                                        LogTab lt;
-                                        lt.off = n_pool + 32 + pl->host.n_log;
-                                        lt.space = fp.e_space;
-                                        const int64_t entries = (fp.e_space < 0 ? 0 : space_extent[fp.e_space]) + 1;
-                                        pl->host.n_log += 2 * entries;
-                                        log_jobs.push_back({fp.e_off, fp.de_off, entries});
-                                        it = seen.emplace(key, (int32_t)pl->host.logtabs.size()).first;
-                                        pl->host.logtabs.push_back(lt);
-                                    }
-                                    side[which] = it->second;
-                                }
-                                if (fp.dsrc_off < 0) break;                 // the rotation itself has no partial: relaxations alone
-                                if (fp.dsrc_off < d->n_coef) { ok = false; break; }   // a rotation partial of the host: not this route
-                                cur = fp.dsrc_off;
-                                if (depth == 7) ok = false;
-                            }
-                            w = walked.emplace(wkey, ok ? std::make_pair(side[0], side[1]) : std::make_pair(-2, -2)).first;
-                        }
-                        if (w->second.first == -2) continue;
-                        pl->host.t0_log[((size_t)i * EPGX_MAX_VARS + v) * 2] = w->second.first;
-                        pl->host.t0_log[((size_t)i * EPGX_MAX_VARS + v) * 2 + 1] = w->second.second;
-                        pl->host.t0_logd[(size_t)i * EPGX_MAX_VARS + v] = 1;
-                    }
-                }
-            }
-        }
-    }
-    e = dev_alloc(ctx, (void **)&pl->d_coef, sizeof(double) * (size_t)(n_pool + 32 + pl->host.n_log + (pl->host.n_log ? 32 : 0)));
-    if (e == hipSuccess && pl->host.n_log)
-        e = hipMemsetAsync(pl->d_coef + n_pool + 32 + pl->host.n_log, 0, sizeof(double) * 32, ctx->stream);
+    const int64_t n_pool = pl->host.n_pool, n_log = pl->host.n_log;
+    hipError_t e = dev_alloc(ctx, (void **)&pl->d_coef, sizeof(double) * (size_t)(n_pool + 32 + n_log + (n_log ? 32 : 0)));
+    if (e == hipSuccess && n_log)
+        e = hipMemsetAsync(pl->d_coef + n_pool + 32 + n_log, 0, sizeof(double) * 32, ctx->stream);
     if (e == hipSuccess)   // (the generated part is written entry by entry: only the padding needs zeros)
         e = hipMemsetAsync(pl->d_coef + n_pool, 0, sizeof(double) * 32, ctx->stream);
     static const double identity_relaxation[4] = {1.0, 0.0, 1.0, 0.0};   // e, Im e, e2, r: what a missing E_a / E_b of a folded record reads
@@ -1192,82 +538,92 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
     if (e == hipSuccess && d->n_coef)
         e = hipMemcpyAsync(pl->d_coef, d->coef, sizeof(double) * (size_t)d->n_coef,
                            hipMemcpyHostToDevice, ctx->stream);
-    for (size_t i = 0; i < snaps.size() && e == hipSuccess; ++i) {   // clear the rounding residues (t_pattern)
+    for (size_t i = 0; i < snaps.size() && e == hipSuccess; ++i) {   // clear the rounding residues (analyse_plan)
         const Snap &sn = snaps[i];
         hipLaunchKernelGGL(snap_kernel, dim3((unsigned)((sn.entries + 255) / 256)), dim3(256), 0, ctx->stream,
                            pl->d_coef + sn.off, sn.entries, sn.nc, sn.mask);
         e = hipGetLastError();
     }
-    if (d->n_assemble > 0 && e == hipSuccess) {   // tables assembled from per-axis columns: one launch for all recipes
-        std::vector<AsmArgs> recipes((size_t)d->n_assemble);
-        int64_t most = 1;
-        for (int i = 0; i < d->n_assemble; ++i) {
-            const epgx_assemble &as = d->assemble[i];
-            AsmArgs &aa = recipes[(size_t)i];
-            memset(&aa, 0, sizeof(aa));
-            aa.dst_off = as.dst_off;
-            aa.n_entries = (as.dst_space < 0 ? 0 : space_extent[as.dst_space]) + 1;
-            aa.ndim = d->ndim;
-            aa.ncoef = as.ncoef;
-            aa.n_src = as.n_src;
-            for (int dd = 0; dd < d->ndim; ++dd) {
-                aa.shape[dd] = pl->shape[dd];
-                aa.dst_str[dd] = as.dst_space < 0 ? 0 : pl->strides[as.dst_space][dd];
-            }
-            for (int k = 0; k < as.n_src; ++k) {
-                aa.src_off[k] = as.src[k].off;
-                aa.src_ncol[k] = as.src[k].ncol;
-                for (int dd = 0; dd < d->ndim; ++dd) aa.src_str[k][dd] = as.src[k].strides[dd];
-            }
-            memcpy(aa.col_src, as.col_src, sizeof(aa.col_src));
-            memcpy(aa.col_idx, as.col_idx, sizeof(aa.col_idx));
-            most = std::max(most, aa.n_entries);
+    return e;
+}
+
+// tables assembled from per-axis columns (epgx_assemble): one launch for all recipes
+static hipError_t generate_assembled(epgx_ctx *ctx, epgx_plan *pl, const epgx_plan_desc *d) {
+    if (d->n_assemble <= 0) return hipSuccess;
+    std::vector<AsmArgs> recipes((size_t)d->n_assemble);
+    int64_t most = 1;
+    for (int i = 0; i < d->n_assemble; ++i) {
+        const epgx_assemble &as = d->assemble[i];
+        AsmArgs &aa = recipes[(size_t)i];
+        memset(&aa, 0, sizeof(aa));
+        aa.dst_off = as.dst_off;
+        aa.n_entries = pl->entries(as.dst_space);
+        aa.ndim = pl->ndim;
+        aa.ncoef = as.ncoef;
+        aa.n_src = as.n_src;
+        pl->fill(aa.shape, aa.dst_str, as.dst_space);
+        for (int k = 0; k < as.n_src; ++k) {
+            aa.src_off[k] = as.src[k].off;
+            aa.src_ncol[k] = as.src[k].ncol;
+            for (int dd = 0; dd < pl->ndim; ++dd) aa.src_str[k][dd] = as.src[k].strides[dd];
         }
-        AsmArgs *d_recipes = nullptr;
-        e = dev_alloc(ctx, (void **)&d_recipes, sizeof(AsmArgs) * recipes.size());
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(d_recipes, recipes.data(), sizeof(AsmArgs) * recipes.size(), hipMemcpyHostToDevice, ctx->stream);
-        const unsigned bx = (unsigned)std::min<int64_t>((most + 255) / 256, 4096);
-        for (int first = 0; first < d->n_assemble && e == hipSuccess; first += 32768) {
-            const unsigned by = (unsigned)std::min(d->n_assemble - first, 32768);
-            hipLaunchKernelGGL(assemble_kernel, dim3(bx, by), dim3(256), 0, ctx->stream, pl->d_coef, (const AsmArgs *)(d_recipes + first));
-            e = hipGetLastError();
-        }
-        // (`recipes` is a local: the copy must have left the host before it goes; the plan's final synchronise is below,
-        // so wait here only for the upload)
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        dev_free(ctx, d_recipes);
+        memcpy(aa.col_src, as.col_src, sizeof(aa.col_src));
+        memcpy(aa.col_idx, as.col_idx, sizeof(aa.col_idx));
+        most = std::max(most, aa.n_entries);
     }
-    if (n_chain > 0 && e == hipSuccess) {   // collapsed tables: the steps of all chains in one upload, one launch per chain
-        std::vector<epgx_chain_step> steps;
-        for (int i = 0; i < n_chain; ++i) steps.insert(steps.end(), ext->chain[i].steps, ext->chain[i].steps + ext->chain[i].n_steps);
-        epgx_chain_step *d_steps = nullptr;
-        e = dev_alloc(ctx, (void **)&d_steps, sizeof(epgx_chain_step) * steps.size());
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(d_steps, steps.data(), sizeof(epgx_chain_step) * steps.size(), hipMemcpyHostToDevice, ctx->stream);
-        size_t at = 0;
-        for (int i = 0; i < n_chain && e == hipSuccess; ++i) {
-            const epgx_chain &ch = ext->chain[i];
-            ChainArgs ca;
-            memset(&ca, 0, sizeof(ca));
-            ca.pool = pl->d_coef;
-            ca.steps = d_steps + at;
-            ca.dst_off = ch.dst_off;
-            ca.n_entries = (ch.dst_space < 0 ? 0 : space_extent[ch.dst_space]) + 1;
-            ca.n_steps = ch.n_steps;
-            ca.ndim = d->ndim;
-            for (int dd = 0; dd < d->ndim; ++dd) {
-                ca.shape[dd] = pl->shape[dd];
-                ca.dst_str[dd] = ch.dst_space < 0 ? 0 : pl->strides[ch.dst_space][dd];
-                for (int sp = 0; sp < d->n_spaces; ++sp) ca.sp_str[sp][dd] = pl->strides[sp][dd];
-            }
-            e = epgx_launch_chain(ctx->stream, ca);
-            at += (size_t)ch.n_steps;
-        }
-        // (`steps` is a local: its upload must have left the host before it goes; the kernels have read d_steps by then too)
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        dev_free(ctx, d_steps);
+    AsmArgs *d_recipes = nullptr;
+    hipError_t e = dev_alloc(ctx, (void **)&d_recipes, sizeof(AsmArgs) * recipes.size());
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_recipes, recipes.data(), sizeof(AsmArgs) * recipes.size(), hipMemcpyHostToDevice, ctx->stream);
+    const unsigned bx = (unsigned)std::min<int64_t>((most + 255) / 256, 4096);
+    for (int first = 0; first < d->n_assemble && e == hipSuccess; first += 32768) {
+        const unsigned by = (unsigned)std::min(d->n_assemble - first, 32768);
+        hipLaunchKernelGGL(assemble_kernel, dim3(bx, by), dim3(256), 0, ctx->stream, pl->d_coef, (const AsmArgs *)(d_recipes + first));
+        e = hipGetLastError();
     }
+    // (`recipes` is a local: the copy must have left the host before it goes; the plan's final synchronise is in plan_create,
+    // so wait here only for the upload)
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    dev_free(ctx, d_recipes);
+    return e;
+}
+
+// collapsed tables (epgx_chain): the steps of all chains in one upload, one launch per chain
+static hipError_t generate_chains(epgx_ctx *ctx, epgx_plan *pl, const epgx_plan_ext *ext) {
+    const int n_chain = ext ? ext->n_chain : 0;
+    if (n_chain <= 0) return hipSuccess;
+    std::vector<epgx_chain_step> steps;
+    for (int i = 0; i < n_chain; ++i) steps.insert(steps.end(), ext->chain[i].steps, ext->chain[i].steps + ext->chain[i].n_steps);
+    epgx_chain_step *d_steps = nullptr;
+    hipError_t e = dev_alloc(ctx, (void **)&d_steps, sizeof(epgx_chain_step) * steps.size());
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_steps, steps.data(), sizeof(epgx_chain_step) * steps.size(), hipMemcpyHostToDevice, ctx->stream);
+    size_t at = 0;
+    for (int i = 0; i < n_chain && e == hipSuccess; ++i) {
+        const epgx_chain &ch = ext->chain[i];
+        ChainArgs ca;
+        memset(&ca, 0, sizeof(ca));
+        ca.pool = pl->d_coef;
+        ca.steps = d_steps + at;
+        ca.dst_off = ch.dst_off;
+        ca.n_entries = pl->entries(ch.dst_space);
+        ca.n_steps = ch.n_steps;
+        ca.ndim = pl->ndim;
+        pl->fill(ca.shape, ca.dst_str, ch.dst_space);
+        for (int sp = 0; sp < pl->host.n_spaces; ++sp)
+            for (int dd = 0; dd < pl->ndim; ++dd) ca.sp_str[sp][dd] = pl->strides[sp][dd];
+        e = epgx_launch_chain(ctx->stream, ca);
+        at += (size_t)ch.n_steps;
+    }
+    // (`steps` is a local: its upload must have left the host before it goes; the kernels have read d_steps by then too)
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    dev_free(ctx, d_steps);
+    return e;
+}
+
+// fused tables (epgx_fuse), then their partials (epgx_fuse_partial): one launch per recipe, in list order
+static hipError_t generate_fused(epgx_ctx *ctx, epgx_plan *pl, const epgx_plan_desc *d) {
+    hipError_t e = hipSuccess;
     for (int i = 0; i < d->n_fuse && e == hipSuccess; ++i) {
         const epgx_fuse &fu = d->fuse[i];
         FuseArgs fa;
@@ -1276,16 +632,13 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
         fa.dst_off = fu.dst_off;
         fa.src_off = fu.src_off;
         fa.e_off = fu.e_off;
-        fa.n_entries = (fu.dst_space < 0 ? 0 : space_extent[fu.dst_space]) + 1;
-        fa.ndim = d->ndim;
+        fa.n_entries = pl->entries(fu.dst_space);
+        fa.ndim = pl->ndim;
         fa.src_ncoef = fu.src_ncoef;
         fa.after = fu.after;
-        for (int dd = 0; dd < d->ndim; ++dd) {
-            fa.shape[dd] = pl->shape[dd];
-            fa.dst_str[dd] = fu.dst_space < 0 ? 0 : pl->strides[fu.dst_space][dd];
-            fa.src_str[dd] = fu.src_space < 0 ? 0 : pl->strides[fu.src_space][dd];
-            fa.e_str[dd] = fu.e_space < 0 ? 0 : pl->strides[fu.e_space][dd];
-        }
+        pl->fill(fa.shape, fa.dst_str, fu.dst_space);
+        pl->fill(fa.shape, fa.src_str, fu.src_space);
+        pl->fill(fa.shape, fa.e_str, fu.e_space);
         hipLaunchKernelGGL(fuse_kernel, dim3((unsigned)((fa.n_entries + 255) / 256)), dim3(256), 0, ctx->stream, fa);
         e = hipGetLastError();
     }
@@ -1299,46 +652,49 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
         fa.dsrc_off = fp.dsrc_off < 0 ? -1 : fp.dsrc_off;
         fa.e_off = fp.e_off;
         fa.de_off = fp.de_off < 0 ? -1 : fp.de_off;
-        fa.n_entries = (fp.dst_space < 0 ? 0 : space_extent[fp.dst_space]) + 1;
-        fa.ndim = d->ndim;
+        fa.n_entries = pl->entries(fp.dst_space);
+        fa.ndim = pl->ndim;
         fa.src_ncoef = fp.src_ncoef;
         fa.dsrc_ncoef = fp.dsrc_ncoef;
         fa.after = fp.after;
-        for (int dd = 0; dd < d->ndim; ++dd) {
-            auto str = [&](int sp) { return sp < 0 ? (int64_t)0 : pl->strides[sp][dd]; };
-            fa.shape[dd] = pl->shape[dd];
-            fa.dst_str[dd] = str(fp.dst_space);
-            fa.src_str[dd] = str(fp.src_space);
-            fa.dsrc_str[dd] = fp.dsrc_off < 0 ? 0 : str(fp.dsrc_space);
-            fa.e_str[dd] = str(fp.e_space);
-            fa.de_str[dd] = fp.de_off < 0 ? 0 : str(fp.de_space);
-        }
+        pl->fill(fa.shape, fa.dst_str, fp.dst_space);
+        pl->fill(fa.shape, fa.src_str, fp.src_space);
+        pl->fill(fa.shape, fa.dsrc_str, fp.dsrc_off < 0 ? -1 : fp.dsrc_space);
+        pl->fill(fa.shape, fa.e_str, fp.e_space);
+        pl->fill(fa.shape, fa.de_str, fp.de_off < 0 ? -1 : fp.de_space);
         hipLaunchKernelGGL(fuse_partial_kernel, dim3((unsigned)((fa.n_entries + 255) / 256)), dim3(256), 0, ctx->stream, fa);
         e = hipGetLastError();
     }
-    uint32_t *d_logflags = nullptr;
-    std::vector<uint32_t> logflags(log_jobs.size(), 0u);
-    if (e == hipSuccess && !log_jobs.empty()) {
-        e = dev_alloc(ctx, (void **)&d_logflags, sizeof(uint32_t) * log_jobs.size());
-        if (e == hipSuccess) e = hipMemsetAsync(d_logflags, 0, sizeof(uint32_t) * log_jobs.size(), ctx->stream);
-        for (size_t j = 0; j < log_jobs.size() && e == hipSuccess; ++j) {
-            LogTabArgs la;
-            memset(&la, 0, sizeof(la));
-            la.pool = pl->d_coef;
-            la.e_off = log_jobs[j].e_off;
-            la.de_off = log_jobs[j].de_off;
-            la.dst_off = pl->host.logtabs[j].off;
-            la.n_entries = log_jobs[j].entries;
-            la.flags = d_logflags;
-            la.slot = (int32_t)j;
-            hipLaunchKernelGGL(logtab_kernel, dim3((unsigned)((la.n_entries + 255) / 256)), dim3(256), 0, ctx->stream, la);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(logflags.data(), d_logflags, sizeof(uint32_t) * log_jobs.size(), hipMemcpyDeviceToHost, ctx->stream);
+    return e;
+}
+
+// tables of logarithmic partials (logtab_kernel) and the copy of their flags into `logflags`, which is complete once the stream
+// has been synchronised; *d_logflags is the caller's to free
+static hipError_t generate_log_tables(epgx_ctx *ctx, epgx_plan *pl, const std::vector<LogJob> &log_jobs, uint32_t **d_logflags,
+                                      std::vector<uint32_t> &logflags) {
+    if (log_jobs.empty()) return hipSuccess;
+    hipError_t e = dev_alloc(ctx, (void **)d_logflags, sizeof(uint32_t) * log_jobs.size());
+    if (e == hipSuccess) e = hipMemsetAsync(*d_logflags, 0, sizeof(uint32_t) * log_jobs.size(), ctx->stream);
+    for (size_t j = 0; j < log_jobs.size() && e == hipSuccess; ++j) {
+        LogTabArgs la;
+        memset(&la, 0, sizeof(la));
+        la.pool = pl->d_coef;
+        la.e_off = log_jobs[j].e_off;
+        la.de_off = log_jobs[j].de_off;
+        la.dst_off = pl->host.logtabs[j].off;
+        la.n_entries = log_jobs[j].entries;
+        la.flags = *d_logflags;
+        la.slot = (int32_t)j;
+        hipLaunchKernelGGL(logtab_kernel, dim3((unsigned)((la.n_entries + 255) / 256)), dim3(256), 0, ctx->stream, la);
+        e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (d_logflags) dev_free(ctx, d_logflags);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(logflags.data(), *d_logflags, sizeof(uint32_t) * log_jobs.size(), hipMemcpyDeviceToHost, ctx->stream);
+    return e;
+}
+
+// what logtab_kernel found out about every log table, and the two EPGX_TRACE lines on them
+static void read_log_flags(epgx_plan *pl, const std::vector<LogJob> &log_jobs, const std::vector<uint32_t> &logflags, bool trace) {
     for (size_t j = 0; j < log_jobs.size(); ++j) {
         pl->host.logtabs[j].any = logflags[j] & 3u;
         if (logflags[j] & 4u) pl->host.logtabs[j].off = -1;   // not of the logarithmic form: records that need it do not fold
@@ -1350,18 +706,50 @@ static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_e
     }
     if (trace && !pl->host.t0_logd.empty()) {
         int routed = 0, generated = 0;
-        for (int i = 0; i < d->n_ops; ++i)
-            for (int v = 0; v < d->n_vars; ++v)
-                if (pl->host.ops[i].opcode == EPGX_OP_T0 && pl->host.dops[i].coef_off[v] >= 0) (pl->host.t0_logd[(size_t)i * EPGX_MAX_VARS + v] ? routed : generated)++;
+        for (size_t i = 0; i < pl->host.ops.size(); ++i)
+            for (int v = 0; v < pl->host.n_vars; ++v)
+                if (pl->host.ops[i].opcode == EPGX_OP_T0 && pl->host.dops[i].coef_off[v] >= 0) (pl->host.t0_logd[i * EPGX_MAX_VARS + v] ? routed : generated)++;
         fprintf(stderr, "[epgx] plan_create fused-echo partials: %d relaxation-only (logarithmic route), %d with a rotation partial\n", routed, generated);
     }
+}
+
+static int plan_create(epgx_ctx *ctx, const epgx_plan_desc *d, const epgx_plan_ext *ext, epgx_plan **out) {
+    if (!ctx || !d || !out) return fail(EPGX_ERR_INVALID, "epgx_plan_create: NULL argument");
+    *out = nullptr;
+    // (the first member: readable whatever the caller's idea of the struct is)
+    if (d->struct_size != sizeof(epgx_plan_desc))
+        return fail(EPGX_ERR_INVALID, "epgx_plan_create: struct_size = %u, but epgx_plan_desc has %zu bytes in this library (ABI %d): "
+                    "set struct_size = sizeof(epgx_plan_desc) and rebuild the caller against include/epgx.h", d->struct_size,
+                    sizeof(epgx_plan_desc), EPGX_ABI_VERSION);
+    const Lap lap;
+    PlanAnalysis an;   // everything decided on host data alone, every refusal among it (epgx_plan_check.h)
+    if (int rc = analyse_plan(d, ext, knobs(), &an)) return rc;
+    if (int rc = set_device(ctx)) return rc;
+    lap("host done");
+    // (epgx_plan_destroy copes with a half-built plan: an early return gives back whatever the plan holds by then)
+    std::unique_ptr<epgx_plan, decltype(&epgx_plan_destroy)> pl(new (std::nothrow) epgx_plan(), epgx_plan_destroy);
+    if (!pl) return fail(EPGX_ERR_NOMEM, "epgx_plan_create: host allocation failed");
+    pl->ctx = ctx;
+    static_cast<PlanGeometry &>(*pl) = an.geo;
+    pl->host = std::move(an.host);
+    pl->deriv_flags = d->deriv_flags;
+    pl->n_adc = d->n_adc;
+    pl->n_coef = d->n_coef;
+    uint32_t *d_logflags = nullptr;
+    std::vector<uint32_t> logflags(an.log_jobs.size(), 0u);
+    hipError_t e = upload_pool(ctx, pl.get(), d, an.snaps);
+    if (e == hipSuccess) e = generate_assembled(ctx, pl.get(), d);
+    if (e == hipSuccess) e = generate_chains(ctx, pl.get(), ext);
+    if (e == hipSuccess) e = generate_fused(ctx, pl.get(), d);
+    if (e == hipSuccess) e = generate_log_tables(ctx, pl.get(), an.log_jobs, &d_logflags, logflags);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    dev_free(ctx, d_logflags);
+    read_log_flags(pl.get(), an.log_jobs, logflags, lap.on);
     lap("uploaded");
-    if (e != hipSuccess) {
-        epgx_plan_destroy(pl);
+    if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? EPGX_ERR_NOMEM : EPGX_ERR_HIP, "epgx_plan_create: %s",
                     hipGetErrorString(e));
-    }
-    *out = pl;
+    *out = pl.release();
     return EPGX_OK;
 }
 

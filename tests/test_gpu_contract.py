@@ -262,3 +262,53 @@ def test_kernel_of_every_baseline_config():
             st = _lib.DeviceState(ctx, enc.nvox, K)
             assert _lib.kernel_for(ctx, plan, K, 0, plan.n_ops, st, None) == streamed
             assert _lib.kernel_for(ctx, plan, K, 0, plan.n_ops, st, st) == in_out
+
+
+# ------------------------------------------------------------------ a refused plan leaves nothing behind
+def test_refused_plans_through_the_abi():
+    """epgx_plan_create refuses on host data alone (analyse_plan, epgx_plan_check.cpp: every refusal has its case in
+    tests/host/plan_check.cpp); here a handful travel through the real ABI -- one from the descriptor checks, one from the operator
+    loop, one from a fuse recipe, one from a partial, the late "no entry of `fuse` writes there" and one with another code -- each
+    with its code, the text of epgx_last_error() and a NULL handle; the plan created on the same context afterwards runs and gives
+    what it gave before, and the context's cache can still be released"""
+    import ctypes
+    from epgpy_amd import _lib
+
+    ctx = _lib.get_context()
+    grid, spaces, K = (2, 2), [(2, 1)], 64
+    coef = np.concatenate([[0.9, 0.3, 0, 0, 0.1, 0, -0.1, 0.8], np.tile([0.9, 0.0, 0.95, 0.05], 4) * np.repeat([1.0, 0.9, 0.8, 0.7], 4)])
+    n_coef = len(coef)
+    T, E, ADC, S = (_lib.OP_T, -1, 0, 0, 0, 8, 0), (_lib.OP_E, 0, 0, 0, 8, 4, 0), (_lib.OP_ADC, -1, 0, 0, 0, 0, 0), (_lib.OP_S, -1, 1, K, 0, 0, 0)
+    valid = dict(ops=[T, E, ADC, S], grid_shape=grid, space_strides=spaces, coef=coef, n_adc=1)
+
+    def signal():
+        plan = _lib.DevicePlan(ctx, **valid)
+        sig = _lib.DeviceBuffer(ctx, 16 * 4)
+        _lib.run(ctx, plan, 0, plan.n_ops, 0, 4, None, None, K, sig.ptr.value, 4, 0)
+        return sig.download(np.complex128, (1, 4))
+
+    before = signal()
+    assert np.all(np.isfinite(before)) and np.all(before != 0) and len(set(before.ravel().tolist())) == 4
+
+    no_partial = ((-1, -1, -1), 0, (-1, -1, -1))
+    fuse_bad = [(n_coef, 0, 8, 0, -1, 0, 10, 1, 0)]      # dst, src, e, their spaces, src_ncoef = 10, after
+    T0 = (_lib.OP_T0, 0, 0, 0, n_coef, 12, 0)
+    GS = (_lib.OP_GS, 0, 0, 0, 0, 2, 0)
+    refused = [
+        (dict(n_adc=-1), -1, "epgx_plan_create: n_adc < 0"),
+        (dict(ops=[T, E, ADC, (_lib.OP_S, -1, 0, K, 0, 0, 0)]), -1, "epgx_plan_create: operator 3 (opcode 4): shift by 0"),
+        (dict(fuse=fuse_bad, n_coef_generated=48), -1, "epgx_plan_create: generated table 0: source must have 8 or 12 coefficients"),
+        (dict(n_vars=1, n_adc=2, dops=[((-1, -1, -1), 0, (n_coef - 9, -1, -1)), no_partial, no_partial, no_partial]), -1,
+         "epgx_plan_create: operator 0, variable 0: partial table exceeds the host part of the pool"),
+        (dict(ops=[T, E, ADC, S, T0], n_coef_generated=48), -1,
+         "epgx_plan_create: operator 4 refers to the generated part of the pool but no entry of `fuse` writes there"),
+        (dict(ops=[T, E, ADC, S, GS]), -4, "epgx_plan_create: operator 4: gather shifts must be the same for all voxels"),
+    ]
+    for change, code, text in refused:
+        desc, keep = _lib.plan_desc(**{**valid, **change})
+        handle = ctypes.c_void_p(1)
+        assert ctx.lib.epgx_plan_create(ctx.handle, ctypes.byref(desc), ctypes.byref(handle)) == code, change
+        assert ctx.lib.epgx_last_error().decode() == text and not handle.value
+    assert np.array_equal(signal(), before)
+    ctx.release_cache()
+    assert np.array_equal(signal(), before)
