@@ -153,6 +153,8 @@ SYMBOLS = {
     "epgx_signal_crlb_grad": (_i, [_p, _p, _i64, _i64, _i32, _i32, _i32, _p, _i64, _i64, _p, _i64, _i32, _p, _p, _p, _d, _i32, _p, _p]),
     "epgx_signal_norms": (_i, [_p, _p, _i64, _i32, _i64, _p]),
     "epgx_signal_match": (_i, [_p, _p, _i64, _p, _i64, _p, _i64, _i32, _i64, _i32, _p, _p, _p]),
+    "epgx_signal_gram": (_i, [_p, _p, _i64, _p, _i32, _i64, _i32, _p]),
+    "epgx_signal_project": (_i, [_p, _p, _i32, _p, _i64, _i32, _i64, _p, _i64]),
     "epgx_simulate_f64": (_i, [_p, ctypes.POINTER(PlanDesc), _i32, _p, _p, _p, _p, _i32]),
     "epgx_simulate_sharded_f64": (_i, [ctypes.POINTER(PlanDesc), _i32, _i32, _p, _p, _i32]),
     "epgx_comm_unique_id": (_i, [_p]),
@@ -821,6 +823,47 @@ def signal_match(ctx, dict_ptr, dict_row_stride, norms_ptr, natoms, sig_ptr, sig
         return raw[2 * n:3 * n].view(np.int64), raw[:2 * n].view(np.complex128), raw[3 * n:]
     finally:
         out.free()         # (back to the context's pool)
+
+
+GRAM_BLOCK, GRAM_WORKGROUPS, GRAM_MIN_ATOMS = 64, 2048, 1024      # csrc/epgx_compress.h
+PROJECT_MAX_RANK = 64
+
+
+def gram_nsplit(nrec, natoms):
+    """the ranges `epgx_signal_gram` cuts the atoms into when called with nsplit = 0 (include/epgx.h): a function of
+    (nrec, natoms) alone"""
+    nblock = -(-int(nrec) // GRAM_BLOCK)
+    npair = nblock * (nblock + 1) // 2
+    return min(-(-GRAM_WORKGROUPS // npair), max(int(natoms) // GRAM_MIN_ATOMS, 1))
+
+
+def signal_gram(ctx, dict_ptr, dict_row_stride, norms_ptr, nrec, natoms, nsplit=0):
+    """epgx_signal_gram: G[s, t] = sum over the valid atoms of D[s, a] conj(D[t, a]) of a dictionary in device memory (`norms_ptr`
+    from `signal_norms`; nsplit = 0: `gram_nsplit`).  Returns the DeviceBuffer that holds complex128 [nrec][nrec]"""
+    out = DeviceBuffer(ctx, 16 * max(int(nrec), 1) ** 2)
+    try:
+        check(ctx.lib.epgx_signal_gram(ctx.handle, ctypes.c_void_p(dict_ptr) if dict_ptr else None, int(dict_row_stride),
+                                       ctypes.c_void_p(norms_ptr) if norms_ptr else None, int(nrec), int(natoms), int(nsplit),
+                                       out.ptr), "epgx_signal_gram")
+    except Exception:
+        out.free()
+        raise
+    return out
+
+
+def signal_project(ctx, basis_ptr, rank, src_ptr, src_row_stride, nrec, ncol):
+    """epgx_signal_project: out[r, c] = sum_t conj(B[t, r]) X[t, c] for a basis [nrec][rank] and records X (record t of column c
+    at src_ptr + 16 * (t * src_row_stride + c)), both in device memory.  Returns the DeviceBuffer that holds complex128
+    [rank][ncol], rows dense; nothing crosses PCIe"""
+    out = DeviceBuffer(ctx, 16 * max(int(rank) * int(ncol), 1))
+    try:
+        check(ctx.lib.epgx_signal_project(ctx.handle, ctypes.c_void_p(basis_ptr) if basis_ptr else None, int(rank),
+                                          ctypes.c_void_p(src_ptr) if src_ptr else None, int(src_row_stride), int(nrec), int(ncol),
+                                          out.ptr, int(ncol)), "epgx_signal_project")
+    except Exception:
+        out.free()
+        raise
+    return out
 
 
 def state_dft(ctx, state, vox0, nvox, k, w, pos, phase, out_ptr):

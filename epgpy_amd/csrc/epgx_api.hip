@@ -46,6 +46,7 @@
 #include "epgx_dft.h"
 #include "epgx_stats.h"
 #include "epgx_match.h"
+#include "epgx_compress.h"
 #include "epgx_merge.h"
 #include "epgx_launch_grow.h"
 #include "epgx_launch_tiled.h"
@@ -1055,6 +1056,87 @@ extern "C" int epgx_signal_match(epgx_ctx *ctx, const void *dict, int64_t dict_r
         e = epgx_launch_match_merge(ctx->stream, g);
     }
     dev_free(ctx, part);      // (stream-ordered: the block is recycled behind the kernels that use it)
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return EPGX_OK;
+}
+
+// ------------------------------------------------------------------------------ dictionary compression (epgx_compress.hip)
+extern "C" int epgx_signal_gram(epgx_ctx *ctx, const void *dict, int64_t dict_row_stride, const void *norms, int32_t nrec, int64_t natoms,
+                                int32_t nsplit, void *out) {
+    const char *who = "epgx_signal_gram";
+    if (!ctx || !dict || !norms || !out) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
+    if (((uintptr_t)dict & 15) || ((uintptr_t)out & 15) || ((uintptr_t)norms & 7))
+        return fail(EPGX_ERR_INVALID, "%s: dict and out must be aligned to 16 bytes, norms to 8", who);
+    if (nrec < 1 || natoms < 1) return fail(EPGX_ERR_INVALID, "%s: nrec = %d, natoms = %lld: both must be >= 1", who, nrec, (long long)natoms);
+    if (nsplit < 0 || nsplit > natoms) return fail(EPGX_ERR_INVALID, "%s: nsplit = %d not in [0, natoms = %lld]", who, nsplit, (long long)natoms);
+    if (!match_extent_ok(nrec, dict_row_stride, natoms))
+        return fail(EPGX_ERR_INVALID, "%s: %d records of dict_row_stride = %lld do not hold %lld atoms each (or overflow the address range)", who,
+                    nrec, (long long)dict_row_stride, (long long)natoms);
+    if (nsplit == 0) nsplit = gram_default_nsplit(nrec, natoms);
+    GramArgs a;
+    memset(&a, 0, sizeof(a));
+    a.nblock = gram_nblock(nrec);
+    const int64_t npair = (int64_t)a.nblock * (a.nblock + 1) / 2;
+    int64_t scratch_len;
+    if (npair > (int64_t)0x7fffffff / nsplit || __builtin_mul_overflow((int64_t)nrec * nrec, (int64_t)nsplit, &scratch_len) ||
+        scratch_len > INT64_MAX / (int64_t)sizeof(d2))
+        return fail(EPGX_ERR_INVALID, "%s: nsplit = %d partial Gram matrices of %d x %d in one call", who, nsplit, nrec, nrec);
+    if (int rc = set_device(ctx)) return rc;
+    void *part = nullptr;
+    hipError_t e = dev_alloc(ctx, &part, sizeof(d2) * (size_t)scratch_len);
+    if (e != hipSuccess) return fail(EPGX_ERR_NOMEM, "%s: scratch for %d partial Gram matrices of %d x %d: %s", who, nsplit, nrec, nrec, hipGetErrorString(e));
+    a.dict = (const d2 *)dict;
+    a.dict_stride = dict_row_stride;
+    a.norms = (const double *)norms;
+    a.natoms = natoms;
+    a.nrec = nrec;
+    a.nsplit = nsplit;
+    a.npair = (int32_t)npair;
+    a.part = (d2 *)part;
+    e = epgx_launch_gram(ctx->stream, a);
+    if (e == hipSuccess) {
+        GramReduceArgs g;
+        memset(&g, 0, sizeof(g));
+        g.part = a.part;
+        g.nrec = nrec;
+        g.nsplit = nsplit;
+        g.out = (d2 *)out;
+        e = epgx_launch_gram_reduce(ctx->stream, g);
+    }
+    dev_free(ctx, part);      // (stream-ordered: the block is recycled behind the kernels that use it)
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return EPGX_OK;
+}
+
+extern "C" int epgx_signal_project(epgx_ctx *ctx, const void *basis, int32_t rank, const void *src, int64_t src_row_stride, int32_t nrec,
+                                   int64_t ncol, void *out, int64_t out_row_stride) {
+    const char *who = "epgx_signal_project";
+    if (!ctx || !basis || !src || !out) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
+    if (((uintptr_t)basis & 15) || ((uintptr_t)src & 15) || ((uintptr_t)out & 15))
+        return fail(EPGX_ERR_INVALID, "%s: basis, src and out must be aligned to 16 bytes", who);
+    if (nrec < 1 || ncol < 0) return fail(EPGX_ERR_INVALID, "%s: nrec = %d (>= 1), ncol = %lld (>= 0)", who, nrec, (long long)ncol);
+    if (rank < 1 || rank > PROJ_MAX_RANK || rank > nrec)
+        return fail(EPGX_ERR_INVALID, "%s: rank = %d not in [1, min(%d, nrec = %d)]", who, rank, PROJ_MAX_RANK, nrec);
+    if (!match_extent_ok(nrec, src_row_stride, ncol))
+        return fail(EPGX_ERR_INVALID, "%s: %d records of src_row_stride = %lld do not hold %lld columns each (or overflow the address range)", who,
+                    nrec, (long long)src_row_stride, (long long)ncol);
+    if (!match_extent_ok(rank, out_row_stride, ncol))
+        return fail(EPGX_ERR_INVALID, "%s: %d rows of out_row_stride = %lld do not hold %lld columns each (or overflow the address range)", who,
+                    rank, (long long)out_row_stride, (long long)ncol);
+    if (ncol / (PROJ_WAVES * PROJ_TILE) >= 0x7fffffff) return fail(EPGX_ERR_INVALID, "%s: ncol = %lld columns in one call", who, (long long)ncol);
+    if (ncol == 0) return EPGX_OK;
+    if (int rc = set_device(ctx)) return rc;
+    ProjectArgs a;
+    memset(&a, 0, sizeof(a));
+    a.basis = (const d2 *)basis;
+    a.src = (const d2 *)src;
+    a.src_stride = src_row_stride;
+    a.ncol = ncol;
+    a.out = (d2 *)out;
+    a.out_stride = out_row_stride;
+    a.nrec = nrec;
+    a.rank = rank;
+    hipError_t e = epgx_launch_project(ctx->stream, a);
     if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return EPGX_OK;
 }

@@ -17,13 +17,29 @@ read the dictionary where it lies; the correlation matrix [natoms, nmeas] is nev
 back over PCIe.  Where no atom is valid (all-zero atoms, atoms holding NaN) or the best q is not finite the voxel gets index -1,
 scale 0, score 0.  A voxel's result does not depend on the other voxels of the call or on how the device splits the atoms.
 
+SVD compression (`compress`, csrc/epgx_compress.hip through `epgx_signal_gram` / `epgx_signal_project`): matching is for short
+fingerprints, and a long dictionary is made short without leaving HBM,
+
+    basis = match.compress(dic, rank=8)        # or energy=0.9999
+    res = match.match(basis.dictionary, signals)
+
+    G[s,t]  = sum over valid a of D[s,a] conj(D[t,a])      on the device, [nrec, nrec] comes down
+    G       = U diag(lambda) U^H                            on the host (numpy.linalg.eigh), lambda descending
+    Dc[r,a] = sum_t conj(U[t,r]) D[t,a],  r < rank          on the device: the compressed dictionary [rank, *grid], in HBM
+    Sc[r,m] = sum_t conj(U[t,r]) S[t,m]                     measured signals, projected the same way before matching
+
+The Gram route resolves singular values down to about sqrt(u) sigma_0 only (u = 2^-53): `compress` refuses a rank that reaches
+eigenvalues lambda_r <= nrec 2^-52 lambda_0.  That is far below what compression keeps (1e-4 .. 1e-6 of the energy).
+
 Dictionaries: a `DeviceSignal` over the whole grid on one GPU (any probe of its buffer), a `DeviceJacobian` (its probed-state
 row), or a NumPy array `[nrec, *grid]` (uploaded once).  Signals: a NumPy array `[nrec, *shape]` (real or complex; uploaded as
 complex128) or a whole `DeviceSignal` on the same device.  Dictionaries of a run over several GPUs raise `NotImplementedError`.
 """
 import numpy as np
 
-__all__ = ["Dictionary", "MatchResult", "match"]
+__all__ = ["Dictionary", "MatchResult", "match", "Basis", "compress", "gram_basis", "select_rank", "MAX_RANK"]
+
+MAX_RANK = 64          # basis vectors `epgx_signal_project` takes
 
 
 def _signal_handle(arg, name):
@@ -101,11 +117,19 @@ class Dictionary:
             rec.upload(_lib.get_context(device))
         self._rec = rec
         self.grid, self.natoms, self.nrec, self.device = rec.shape, rec.ncol, rec.nrec, rec.device
+        self.basis = None          # the `Basis` of a dictionary that `compress` made
         self._norms = _lib.signal_norms(rec.ctx, rec.ptr, rec.row_stride, rec.nrec, rec.ncol)
 
     @property
     def norms(self):
         return self._norms.download(np.float64, (self.natoms,)).reshape(self.grid)
+
+    @property
+    def records(self):
+        """the records as a DeviceSignal `[nrec, *grid]` (np.asarray downloads them)"""
+        from . import functions, _lib
+        keep = self._rec.keep
+        return functions.DeviceSignal(keep, self.nrec, self.grid, 0, 1) if isinstance(keep, _lib.DeviceBuffer) else keep
 
 
 class MatchResult:
@@ -128,9 +152,29 @@ def match(dictionary, signals, *, nsplit=0):
     dictionary: a `Dictionary`, or anything `Dictionary` takes (its norms are then computed for this call).
     signals: NumPy array `[nrec, *shape]`, real or complex, or a whole DeviceSignal on the dictionary's device.
     nsplit: ranges the device cuts the atoms into (0: chosen by the library; the result does not depend on it).
-    Returns a `MatchResult` whose arrays have the shape `signals.shape[1:]`."""
+    Returns a `MatchResult` whose arrays have the shape `signals.shape[1:]`.
+
+    With a compressed dictionary (`compress(...).dictionary`, Dc = U^H D) the call is DEFINED as
+    `match(Dictionary(U^H D), U^H S)`: signals with `basis.nrec` records are projected on the device first (`basis.project`),
+    signals with `basis.rank` records are taken as projected already, any other record count raises ValueError (where rank =
+    nrec both counts coincide and the signals count as not yet projected).  `score` is then relative to the energy of the
+    PROJECTED signal, sum_r |Sc[r,m]|^2 -- the part of the signal outside the basis does not lower it."""
     from . import _lib
     sig = _Records(signals, "signals")
+    basis = dictionary.basis if isinstance(dictionary, Dictionary) else None
+    if basis is not None:
+        if sig.nrec != basis.nrec and sig.nrec != basis.rank:
+            raise ValueError(f"signals: {sig.nrec} records; the compressed dictionary takes {basis.nrec} (projected on the device first) "
+                             f"or {basis.rank} (projected already)")
+        if sig.nrec == basis.nrec:
+            rec = dictionary._rec
+            if sig.device is not None and (sig.device != rec.device or sig.ctx is not rec.ctx):
+                raise ValueError(f"signals: on device {sig.device}, the dictionary on device {rec.device}; both must be on one GPU (and context)")
+            proj = basis._project(sig, rec.ctx)
+            try:
+                return _match_records(dictionary, _Records(proj, "signals"), nsplit)
+            finally:
+                proj._buf.free()        # (stream-ordered, as below)
     if not isinstance(dictionary, Dictionary):
         # (checked before the dictionary touches the device)
         probe = _Records(dictionary, "dictionary")
@@ -139,6 +183,11 @@ def match(dictionary, signals, *, nsplit=0):
         if sig.device is not None and probe.device is not None and sig.device != probe.device:
             raise ValueError(f"signals: on device {sig.device}, the dictionary on device {probe.device}; both must be on one GPU")
         dictionary = Dictionary(probe, device=sig.device)
+    return _match_records(dictionary, sig, nsplit)
+
+
+def _match_records(dictionary, sig, nsplit):
+    from . import _lib
     if dictionary.nrec != sig.nrec:
         raise ValueError(f"signals: {sig.nrec} records, the dictionary has {dictionary.nrec}")
     rec = dictionary._rec
@@ -150,3 +199,151 @@ def match(dictionary, signals, *, nsplit=0):
     if isinstance(sig.keep, _lib.DeviceBuffer):
         sig.keep.free()        # (stream-ordered: the block is recycled behind the kernels that read it)
     return MatchResult(index.reshape(sig.shape), scale.reshape(sig.shape), score.reshape(sig.shape), dictionary.grid)
+
+
+# ------------------------------------------------------------------------------------------------ SVD compression
+def gram_basis(G):
+    """the host half of `compress`: Gram matrix `[nrec, nrec]` -> `(U, lam)`, the eigenvectors (columns, complex128) and
+    eigenvalues of `(G + G^H) / 2` by numpy.linalg.eigh, eigenvalues DESCENDING.  The gauge is fixed: every column is scaled by
+    a unit phase so that its component of largest modulus (the lowest index among equal moduli) is real and positive -- U is a
+    function of the bits of G"""
+    G = np.asarray(G, dtype=np.complex128)
+    if G.ndim != 2 or G.shape[0] != G.shape[1] or G.shape[0] < 1:
+        raise ValueError(f"gram_basis: a square matrix, got shape {G.shape}")
+    lam, U = np.linalg.eigh((G + G.conj().T) / 2)
+    lam, U = lam[::-1].copy(), np.ascontiguousarray(U[:, ::-1])
+    cols = np.arange(U.shape[1])
+    k = np.argmax(np.abs(U), axis=0)                 # (the first among equal moduli)
+    pivot = U[k, cols]
+    U = U * (np.conj(pivot) / np.abs(pivot))[None, :]
+    U[k, cols] = np.abs(pivot)                       # exactly real
+    return U, lam
+
+
+def resolved_rank(lam):
+    """the number of leading eigenvalues the Gram route resolves: lam_r > nrec 2^-52 lam_0"""
+    lam = np.asarray(lam, dtype=np.float64)
+    if lam[0] <= 0:
+        return 0
+    return int(np.count_nonzero(lam > len(lam) * 2.0 ** -52 * lam[0]))
+
+
+def select_rank(lam, rank=None, energy=None):
+    """the rank `compress` keeps, from the descending eigenvalues: `rank` itself, or the smallest rank whose eigenvalues reach
+    the share `energy` of trace(G).  ValueError where no eigenvalue is positive (no valid atom), the rank is outside
+    1 .. min(MAX_RANK, nrec), `energy` needs more than MAX_RANK, or the rank reaches eigenvalues that are not resolved"""
+    lam = np.asarray(lam, dtype=np.float64)
+    nrec = len(lam)
+    if (rank is None) == (energy is None):
+        raise ValueError("compress: exactly one of rank= and energy= must be given")
+    if not np.isfinite(lam).all() or lam[0] <= 0:
+        raise ValueError("compress: the dictionary has no valid atom (every atom is all zero or holds a NaN / Inf)")
+    if rank is not None:
+        _check_rank(rank, nrec)
+        rank = int(rank)
+    else:
+        share = np.cumsum(np.clip(lam, 0, None))
+        share /= share[-1]
+        rank = int(np.searchsorted(share, energy, side="left")) + 1
+        if rank > min(MAX_RANK, nrec):
+            raise ValueError(f"compress: energy={energy} needs rank {rank}; at most {MAX_RANK} basis vectors are supported "
+                             f"(the first {min(MAX_RANK, nrec)} keep {share[min(MAX_RANK, nrec) - 1]:.12g})")
+    most = resolved_rank(lam)
+    if rank > most:
+        raise ValueError(f"compress: rank {rank} reaches eigenvalues of the Gram matrix that are not resolved "
+                         f"(lambda_r <= nrec 2^-52 lambda_0); the largest resolvable rank is {most}")
+    return rank
+
+
+def _check_rank(rank, nrec):
+    if int(rank) != rank or not 1 <= rank <= MAX_RANK:
+        raise ValueError(f"compress: rank={rank} not in 1 .. {MAX_RANK}")
+    if rank > nrec:
+        raise ValueError(f"compress: rank={rank} above the {nrec} records of the dictionary")
+
+
+class Basis:
+    """the temporal basis of a compressed dictionary.
+
+    `U` complex128 `[nrec, rank]` (host), `s` the singular values sqrt(lambda) of the dictionary, all nrec of them, descending
+    (negative lambda clipped to 0), `rank`, `nrec`, `energy` the share of trace(G) the rank keeps, `dictionary` the compressed
+    `Dictionary` over `[rank, *grid]` in HBM (its `.basis` is this object)."""
+
+    def __init__(self, U, lam, rank):
+        lam = np.clip(np.asarray(lam, dtype=np.float64), 0, None)
+        self.U = np.ascontiguousarray(U[:, :rank], dtype=np.complex128)
+        self.s = np.sqrt(lam)
+        self.nrec, self.rank = int(U.shape[0]), int(rank)
+        self.energy = float(lam[:rank].sum() / lam.sum())
+        self.dictionary = None
+        self._dev = None             # (context, DeviceBuffer) of U
+
+    def _device(self, ctx):
+        from . import _lib
+        if self._dev is None or self._dev[0] is not ctx:
+            buf = _lib.DeviceBuffer(ctx, self.U.nbytes)
+            buf.upload(self.U)
+            self._dev = (ctx, buf)
+        return self._dev[1]
+
+    def _project(self, rec, ctx):
+        """records `_Records` [nrec][ncol] -> DeviceSignal [rank, *shape] on `ctx`"""
+        from . import _lib, functions
+        rec.upload(ctx)
+        ubuf = self._device(ctx)
+        out = _lib.signal_project(ctx, ubuf.ptr.value if ubuf.ptr else None, self.rank, rec.ptr, rec.row_stride, self.nrec, rec.ncol)
+        if isinstance(rec.keep, _lib.DeviceBuffer):
+            rec.keep.free()          # (stream-ordered: the block is recycled behind the kernel that reads it)
+        return functions.DeviceSignal(out, self.rank, rec.shape, 0, 1)
+
+    def project(self, signals, device=None):
+        """Sc[r, m] = sum_t conj(U[t, r]) S[t, m] on the device: signals NumPy `[nrec, *shape]` or a whole DeviceSignal ->
+        DeviceSignal `[rank, *shape]`"""
+        from . import _lib
+        rec = _Records(signals, "signals")
+        if rec.nrec != self.nrec:
+            raise ValueError(f"signals: {rec.nrec} records, the basis has {self.nrec}")
+        ctx = rec.ctx
+        if ctx is None:
+            ctx = self.dictionary._rec.ctx if self.dictionary is not None and device is None else _lib.get_context(device)
+        return self._project(rec, ctx)
+
+
+def compress(dictionary, rank=None, energy=None, *, nsplit=0, device=None):
+    """SVD compression of a dictionary in HBM (module docstring): returns the `Basis`; `basis.dictionary` is the compressed
+    `Dictionary` [rank, *grid] that `match` takes.
+
+    dictionary: a `Dictionary`, or anything `Dictionary` takes (DeviceSignal, DeviceJacobian, NumPy array `[nrec, *grid]`).
+    Exactly one of rank (1 .. 64, at most nrec) and energy (0 < energy <= 1: the smallest rank whose eigenvalues reach that
+    share of trace(G)).  nsplit: ranges the Gram kernel cuts the atoms into (0: the library's rule, a function of nrec and
+    natoms alone, so that the same dictionary gives the same basis on every machine).
+    ValueError: rank above 64 or nrec, an energy that needs more than 64, a rank that reaches unresolved eigenvalues
+    (lambda_r <= nrec 2^-52 lambda_0), a dictionary without a valid atom.
+    Only G (16 nrec^2 bytes) comes down and U (16 nrec rank bytes) goes up; the dictionary does not move."""
+    from . import _lib, functions
+    if (rank is None) == (energy is None):
+        raise ValueError("compress: exactly one of rank= and energy= must be given")
+    if energy is not None and not 0.0 < energy <= 1.0:
+        raise ValueError(f"compress: energy={energy} not in (0, 1]")
+    if not isinstance(dictionary, Dictionary):
+        probe = _Records(dictionary, "dictionary")      # (sharded and slab handles raise here, before the device)
+        if rank is not None:
+            _check_rank(rank, probe.nrec)
+        dictionary = Dictionary(probe, device=device)
+    elif rank is not None:
+        _check_rank(rank, dictionary.nrec)
+    rec = dictionary._rec
+    ctx = rec.ctx
+    gbuf = _lib.signal_gram(ctx, rec.ptr, rec.row_stride, dictionary._norms.ptr.value if dictionary._norms.ptr else None,
+                            dictionary.nrec, dictionary.natoms, nsplit=nsplit)
+    try:
+        G = gbuf.download(np.complex128, (dictionary.nrec, dictionary.nrec))
+    finally:
+        gbuf.free()
+    U, lam = gram_basis(G)
+    basis = Basis(U, lam, select_rank(lam, rank, energy))
+    ubuf = basis._device(ctx)
+    out = _lib.signal_project(ctx, ubuf.ptr.value, basis.rank, rec.ptr, rec.row_stride, dictionary.nrec, dictionary.natoms)
+    cdic = Dictionary(functions.DeviceSignal(out, basis.rank, dictionary.grid, 0, 1))
+    cdic.basis, basis.dictionary = basis, cdic
+    return basis

@@ -623,6 +623,33 @@ int epgx_signal_match(epgx_ctx *ctx, const void *dict, int64_t dict_row_stride, 
                       const void *sig, int64_t sig_row_stride, int32_t nrec, int64_t nmeas, int32_t nsplit,
                       void *out_index, void *out_scale, void *out_score);
 
+/* SVD compression of a dictionary that stays on the device (csrc/epgx_compress.hip).  The caller takes the eigenvectors of the
+ * Gram matrix on the host (nrec is small) and projects dictionary and measured signals onto the leading `rank` of them; matching
+ * then runs on the projected records with nrec = rank.  Layouts and strides as above.
+ *   G[s,t]   = sum over the atoms a whose norms[a] is a finite number > 0 of D[s,a] conj(D[t,a])       (epgx_signal_gram)
+ *   out[r,c] = sum_t conj(B[t,r]) X[t,c],   B[t][r] = basis[t * rank + r],  r < rank <= 64              (epgx_signal_project)
+ * epgx_signal_gram: out is DEVICE complex128 [nrec][nrec].  out[t][s] holds the exact conjugate bits of out[s][t] and the
+ *   diagonal an imaginary part of exactly 0.  Invalid atoms (all zero, or holding a NaN / Inf) are replaced by zeros when they
+ *   are loaded, so G is finite whatever they hold.  The atoms are cut into nsplit ranges by the rule of epgx_signal_match; every
+ *   range leaves one partial Gram matrix (16 nrec^2 bytes) in scratch of the context and a second kernel adds them in ascending
+ *   order.  No atomics: the bits of G depend on the valid columns of D, nrec, natoms and nsplit only.
+ *   nsplit = 0: the library takes  min(ceil(2048 / npair), max(natoms / 1024, 1)),  npair = nblock (nblock + 1) / 2,
+ *   nblock = ceil(nrec / 64)  -- a function of (nrec, natoms) alone, not of the device or the pool, so that the same dictionary
+ *   gives the same G on every machine.
+ * epgx_signal_project: basis is DEVICE complex128 [nrec][rank]; src [nrec] rows of src_row_stride, out [rank] rows of
+ *   out_row_stride elements, ncol columns each.  Every column of src is read once whatever the rank.  The records are consumed in
+ *   steps of 4 from t = 0, the tail padded with zeros: the bits of out[r,c] depend on column c of src, column r of basis and nrec
+ *   alone -- not on ncol, rank, the column's place in the call or the strides.  Non-finite values propagate to their column.
+ * Both calls are stream-ordered; nothing is uploaded or synchronised.
+ * Errors (nothing is launched or written): EPGX_ERR_INVALID for a NULL or misaligned pointer (16 bytes; norms 8), nrec < 1,
+ * natoms < 1, ncol < 0, nsplit < 0 or > natoms, rank < 1, > 64 or > nrec, dict_row_stride < natoms, src_row_stride or
+ * out_row_stride < ncol, an extent (rows - 1) * stride + columns, a scratch size or a launch that overflows.  ncol = 0: nothing
+ * to do. */
+int epgx_signal_gram(epgx_ctx *ctx, const void *dict, int64_t dict_row_stride, const void *norms, int32_t nrec, int64_t natoms,
+                     int32_t nsplit, void *out);
+int epgx_signal_project(epgx_ctx *ctx, const void *basis, int32_t rank, const void *src, int64_t src_row_stride, int32_t nrec,
+                        int64_t ncol, void *out, int64_t out_row_stride);
+
 /* Convenience for bindings that only have host arrays (what a ctypes/NumPy binding inside
  * the reference would call once per simulate()): builds the plan, runs the whole sequence
  * state-resident over the full grid, copies signal (and optionally the final state) back. */
