@@ -10,7 +10,7 @@ RESET, PD with and without reset, a start state `init`.  A COMBINED operator -- 
 E . T . E that the device runs as ONE general-matrix record (EPGX_OP_MAT) -- is its factors applied one after another.
 
 Out of scope, each with a suite of its own or a float64 oracle only: n-D and gather shifts and 3-D diffusion
-(tests/test_gpu_parity.py against oracle.simulate_nd), DFT probes (tests/test_gpu_imaging.py), float shifts
+(tests/test_gpu_nd_paths.py against tests/nd_recurrence.py), DFT probes (tests/test_gpu_imaging.py), float shifts
 (tests/test_gpu_merge.py), epg.X (tests/test_gpu_exchange_paths.py), RFPulse (tests/test_gpu_rfpulse.py), the tiled path
 (tests/test_gpu_tiled.py)."""
 import numpy as np
