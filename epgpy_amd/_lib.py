@@ -155,6 +155,8 @@ SYMBOLS = {
     "epgx_signal_match": (_i, [_p, _p, _i64, _p, _i64, _p, _i64, _i32, _i64, _i32, _p, _p, _p]),
     "epgx_signal_gram": (_i, [_p, _p, _i64, _p, _i32, _i64, _i32, _p]),
     "epgx_signal_project": (_i, [_p, _p, _i32, _p, _i64, _i32, _i64, _p, _i64]),
+    "epgx_signal_norms_c64": (_i, [_p, _p, _i64, _i32, _i64, _p]),
+    "epgx_signal_match_c64": (_i, [_p, _p, _i64, _p, _i64, _p, _i64, _i32, _i64, _i32, _p, _p, _p]),
     "epgx_simulate_f64": (_i, [_p, ctypes.POINTER(PlanDesc), _i32, _p, _p, _p, _p, _i32]),
     "epgx_simulate_sharded_f64": (_i, [ctypes.POINTER(PlanDesc), _i32, _i32, _p, _p, _i32]),
     "epgx_comm_unique_id": (_i, [_p]),
@@ -785,13 +787,15 @@ def signal_crlb_grad(ctx, signal_ptr, record_stride, row_stride, nrow, nrec, row
         out.free()         # (back to the context's pool)
 
 
-def signal_norms(ctx, dict_ptr, row_stride, nrec, natoms):
+def signal_norms(ctx, dict_ptr, row_stride, nrec, natoms, c64=False):
     """epgx_signal_norms: n_a = sum_t |D[t, a]|^2 of a dictionary in device memory (atom a of record t at dict_ptr + 16 *
-    (t * row_stride + a)).  Returns the DeviceBuffer that holds float64 [natoms]; nothing crosses PCIe"""
+    (t * row_stride + a)).  Returns the DeviceBuffer that holds float64 [natoms]; nothing crosses PCIe.
+    c64: epgx_signal_norms_c64 on complex64 records (elements and strides of 8 bytes)"""
+    entry = "epgx_signal_norms_c64" if c64 else "epgx_signal_norms"
     out = DeviceBuffer(ctx, 8 * max(int(natoms), 1), itemsize=8)
     try:
-        check(ctx.lib.epgx_signal_norms(ctx.handle, ctypes.c_void_p(dict_ptr) if dict_ptr else None, int(row_stride), int(nrec),
-                                        int(natoms), out.ptr), "epgx_signal_norms")
+        check(getattr(ctx.lib, entry)(ctx.handle, ctypes.c_void_p(dict_ptr) if dict_ptr else None, int(row_stride), int(nrec),
+                                      int(natoms), out.ptr), entry)
     except Exception:
         out.free()
         raise
@@ -804,19 +808,22 @@ def match_split_bounds(natoms, nsplit):
     return [(s * q + min(s, r), s * q + min(s, r) + q + (1 if s < r else 0)) for s in range(int(nsplit))]
 
 
-def signal_match(ctx, dict_ptr, dict_row_stride, norms_ptr, natoms, sig_ptr, sig_row_stride, nrec, nmeas, nsplit=0):
+def signal_match(ctx, dict_ptr, dict_row_stride, norms_ptr, natoms, sig_ptr, sig_row_stride, nrec, nmeas, nsplit=0, c64=False):
     """epgx_signal_match: per measured voxel the best atom of a dictionary in device memory, its complex scale and score (signals
     at sig_ptr + 16 * (t * sig_row_stride + m), `norms_ptr` from `signal_norms`; nsplit = 0: the library chooses).  Returns
-    (index int64 [nmeas], scale complex128 [nmeas], score float64 [nmeas]); only these 32 bytes per voxel cross PCIe"""
+    (index int64 [nmeas], scale complex128 [nmeas], score float64 [nmeas]); only these 32 bytes per voxel cross PCIe.
+    c64: epgx_signal_match_c64 on complex64 dictionary and signals (elements and strides of 8 bytes, norms from
+    `signal_norms(..., c64=True)`); the results keep their types"""
+    entry = "epgx_signal_match_c64" if c64 else "epgx_signal_match"
     nmeas = int(nmeas)
     n = max(nmeas, 1)
     out = DeviceBuffer(ctx, 32 * n, itemsize=8)      # scale [nmeas] complex128, then index [nmeas] int64, then score [nmeas]
     try:
-        check(ctx.lib.epgx_signal_match(ctx.handle, ctypes.c_void_p(dict_ptr) if dict_ptr else None, int(dict_row_stride),
-                                        ctypes.c_void_p(norms_ptr) if norms_ptr else None, int(natoms),
-                                        ctypes.c_void_p(sig_ptr) if sig_ptr else None, int(sig_row_stride), int(nrec), nmeas,
-                                        int(nsplit), ctypes.c_void_p(out.ptr.value + 16 * n), out.ptr,
-                                        ctypes.c_void_p(out.ptr.value + 24 * n)), "epgx_signal_match")
+        check(getattr(ctx.lib, entry)(ctx.handle, ctypes.c_void_p(dict_ptr) if dict_ptr else None, int(dict_row_stride),
+                                      ctypes.c_void_p(norms_ptr) if norms_ptr else None, int(natoms),
+                                      ctypes.c_void_p(sig_ptr) if sig_ptr else None, int(sig_row_stride), int(nrec), nmeas,
+                                      int(nsplit), ctypes.c_void_p(out.ptr.value + 16 * n), out.ptr,
+                                      ctypes.c_void_p(out.ptr.value + 24 * n)), entry)
         if nmeas == 0:
             return np.empty(0, np.int64), np.empty(0, np.complex128), np.empty(0, np.float64)
         raw = out.download(np.float64, (4 * n,))

@@ -46,6 +46,7 @@
 #include "epgx_dft.h"
 #include "epgx_stats.h"
 #include "epgx_match.h"
+#include "epgx_match32.h"
 #include "epgx_compress.h"
 #include "epgx_merge.h"
 #include "epgx_launch_grow.h"
@@ -1054,6 +1055,96 @@ extern "C" int epgx_signal_match(epgx_ctx *ctx, const void *dict, int64_t dict_r
         g.scale = (d2 *)out_scale;
         g.score = (double *)out_score;
         e = epgx_launch_match_merge(ctx->stream, g);
+    }
+    dev_free(ctx, part);      // (stream-ordered: the block is recycled behind the kernels that use it)
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return EPGX_OK;
+}
+
+// ------------------------------------------------------------------------------ single-precision matching (epgx_match32.hip)
+// match_extent_ok for elements of `bytes` bytes
+static bool match_extent_ok_bytes(int64_t rows, int64_t row_stride, int64_t cols, int64_t bytes) {
+    int64_t span;
+    return row_stride >= cols && !__builtin_mul_overflow(rows - 1, row_stride, &span) && !__builtin_add_overflow(span, cols, &span) &&
+           span <= INT64_MAX / bytes;
+}
+
+extern "C" int epgx_signal_norms_c64(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int64_t natoms, void *out) {
+    const char *who = "epgx_signal_norms_c64";
+    if (!ctx || !dict || !out) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
+    if (((uintptr_t)dict & 7) || ((uintptr_t)out & 7)) return fail(EPGX_ERR_INVALID, "%s: dict and out must be aligned to 8 bytes", who);
+    if (nrec < 1 || natoms < 1) return fail(EPGX_ERR_INVALID, "%s: nrec = %d, natoms = %lld: both must be >= 1", who, nrec, (long long)natoms);
+    if (!match_extent_ok_bytes(nrec, row_stride, natoms, 8) || natoms / 256 >= 0x7fffffff)
+        return fail(EPGX_ERR_INVALID, "%s: %d records of row_stride = %lld do not hold %lld atoms each (or overflow the address range)", who,
+                    nrec, (long long)row_stride, (long long)natoms);
+    if (int rc = set_device(ctx)) return rc;
+    hipError_t e = epgx_launch_norms32(ctx->stream, dict, row_stride, nrec, natoms, (double *)out);
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return EPGX_OK;
+}
+
+extern "C" int epgx_signal_match_c64(epgx_ctx *ctx, const void *dict, int64_t dict_row_stride, const void *norms, int64_t natoms,
+                                     const void *sig, int64_t sig_row_stride, int32_t nrec, int64_t nmeas, int32_t nsplit,
+                                     void *out_index, void *out_scale, void *out_score) {
+    const char *who = "epgx_signal_match_c64";
+    if (!ctx || !dict || !norms || !sig || !out_index || !out_scale || !out_score) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
+    if (((uintptr_t)out_scale & 15) || ((uintptr_t)dict & 7) || ((uintptr_t)sig & 7) || ((uintptr_t)norms & 7) ||
+        ((uintptr_t)out_index & 7) || ((uintptr_t)out_score & 7))
+        return fail(EPGX_ERR_INVALID, "%s: out_scale must be aligned to 16 bytes, dict, sig, norms, out_index and out_score to 8", who);
+    if (nrec < 1 || natoms < 1 || nmeas < 0)
+        return fail(EPGX_ERR_INVALID, "%s: nrec = %d, natoms = %lld (both >= 1), nmeas = %lld (>= 0)", who, nrec, (long long)natoms, (long long)nmeas);
+    if (nsplit < 0 || nsplit > natoms) return fail(EPGX_ERR_INVALID, "%s: nsplit = %d not in [0, natoms = %lld]", who, nsplit, (long long)natoms);
+    if (!match_extent_ok_bytes(nrec, dict_row_stride, natoms, 8))
+        return fail(EPGX_ERR_INVALID, "%s: %d records of dict_row_stride = %lld do not hold %lld atoms each (or overflow the address range)", who,
+                    nrec, (long long)dict_row_stride, (long long)natoms);
+    if (!match_extent_ok_bytes(nrec, sig_row_stride, nmeas, 8))
+        return fail(EPGX_ERR_INVALID, "%s: %d records of sig_row_stride = %lld do not hold %lld voxels each (or overflow the address range)", who,
+                    nrec, (long long)sig_row_stride, (long long)nmeas);
+    if (nmeas == 0) return EPGX_OK;
+    Match32Args a;
+    memset(&a, 0, sizeof(a));
+    a.nvt = (nmeas + MATCH_VOX - 1) / MATCH_VOX;
+    if (nsplit == 0) {
+        // the rule of epgx_signal_match (by the launch shape alone: the result does not depend on it)
+        const int64_t want = 4 * (int64_t)std::max(ctx->prop.multiProcessorCount, 1);
+        const int64_t most = std::max<int64_t>(natoms / (MATCH_WAVES * MATCH_TILE), 1);
+        nsplit = (int32_t)std::min<int64_t>(std::min<int64_t>((want + a.nvt - 1) / a.nvt, most), 1 << 16);
+    }
+    int64_t scratch_len;
+    if (a.nvt > (int64_t)0x7fffffff / nsplit || __builtin_mul_overflow((int64_t)nsplit, nmeas, &scratch_len) ||
+        scratch_len > INT64_MAX / (int64_t)sizeof(MatchPartial))
+        return fail(EPGX_ERR_INVALID, "%s: nsplit = %d splits of %lld voxels in one call", who, nsplit, (long long)nmeas);
+    if (int rc = set_device(ctx)) return rc;
+    void *part = nullptr;
+    hipError_t e = dev_alloc(ctx, &part, sizeof(MatchPartial) * (size_t)scratch_len);
+    if (e != hipSuccess) return fail(EPGX_ERR_NOMEM, "%s: scratch for %d splits of %lld voxels: %s", who, nsplit, (long long)nmeas, hipGetErrorString(e));
+    a.dict = (const f2 *)dict;
+    a.dict_stride = dict_row_stride;
+    a.norms = (const double *)norms;
+    a.natoms = natoms;
+    a.sig = (const f2 *)sig;
+    a.sig_stride = sig_row_stride;
+    a.nmeas = nmeas;
+    a.nrec = nrec;
+    a.nsplit = nsplit;
+    a.chunk = std::min((nrec + MATCH_STEP - 1) / MATCH_STEP * MATCH_STEP, MATCH32_CHUNK);
+    a.nchunk = (nrec + a.chunk - 1) / a.chunk;
+    a.part = (MatchPartial *)part;
+    e = epgx_launch_match32(ctx->stream, a);
+    if (e == hipSuccess) {
+        Match32MergeArgs g;
+        memset(&g, 0, sizeof(g));
+        g.part = a.part;
+        g.norms = a.norms;
+        g.sig = a.sig;
+        g.sig_stride = sig_row_stride;
+        g.nmeas = nmeas;
+        g.nrec = nrec;
+        g.nsplit = nsplit;
+        g.index = (int64_t *)out_index;
+        g.scale = (d2 *)out_scale;
+        g.score = (double *)out_score;
+        e = epgx_launch_match32_merge(ctx->stream, g);
     }
     dev_free(ctx, part);      // (stream-ordered: the block is recycled behind the kernels that use it)
     if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));

@@ -31,6 +31,14 @@ fingerprints, and a long dictionary is made short without leaving HBM,
 The Gram route resolves singular values down to about sqrt(u) sigma_0 only (u = 2^-53): `compress` refuses a rank that reaches
 eigenvalues lambda_r <= nrec 2^-52 lambda_0.  That is far below what compression keeps (1e-4 .. 1e-6 of the energy).
 
+Single precision (csrc/epgx_match32.hip through `epgx_signal_narrow` / `epgx_signal_norms_c64` / `epgx_signal_match_c64`):
+`Dictionary(handle, dtype=np.complex64)`, `dictionary.astype(np.complex64)` or `compress(..., dtype=np.complex64)` give a
+dictionary of 8 bytes per element.  It is DEFINED as the complex128 one rounded once (`astype(np.complex64)`, on the device for
+a handle), and matching against it as the formulas above on the rounded dictionary and the rounded signals: n_a summed in
+float64, c[a,m] in float32 on the fp32 MFMA, q, the comparison, scale and score in float64 from that c.  Results keep their
+types.  The rate of the correlation doubles and every byte of dictionary and signals halves; c carries the error of a float32
+inner product, about nrec 2^-22 sum_t |D||S| at most.
+
 Dictionaries: a `DeviceSignal` over the whole grid on one GPU (any probe of its buffer), a `DeviceJacobian` (its probed-state
 row), or a NumPy array `[nrec, *grid]` (uploaded once).  Signals: a NumPy array `[nrec, *shape]` (real or complex; uploaded as
 complex128) or a whole `DeviceSignal` on the same device.  Dictionaries of a run over several GPUs raise `NotImplementedError`.
@@ -40,6 +48,19 @@ import numpy as np
 __all__ = ["Dictionary", "MatchResult", "match", "Basis", "compress", "gram_basis", "select_rank", "MAX_RANK"]
 
 MAX_RANK = 64          # basis vectors `epgx_signal_project` takes
+
+
+def _dtype(dtype, name):
+    """np.complex128 for None / complex128, np.complex64 for complex64; ValueError for anything else"""
+    if dtype is None:
+        return np.dtype(np.complex128)
+    try:
+        dt = np.dtype(dtype)
+    except TypeError:
+        dt = None
+    if dt not in (np.dtype(np.complex128), np.dtype(np.complex64)):
+        raise ValueError(f"{name}: dtype={dtype!r}; complex128 (None) or complex64")
+    return dt
 
 
 def _signal_handle(arg, name):
@@ -62,7 +83,10 @@ def _signal_handle(arg, name):
 
 
 class _Records:
-    """complex128 records [nrec][ncol] on one device: a view of a DeviceSignal, or a host array uploaded into a buffer of its own"""
+    """complex128 records [nrec][ncol] on one device: a view of a DeviceSignal, or a host array uploaded into a buffer of its own;
+    `narrowed()` gives the complex64 records (`dtype`), always in a buffer of their own"""
+
+    dtype = np.dtype(np.complex128)
 
     def __init__(self, arg, name):
         handle = _signal_handle(arg, name)
@@ -91,6 +115,22 @@ class _Records:
                 self.keep.upload(self._host)
             del self._host
 
+    def narrowed(self):
+        """these records rounded once to complex64, dense rows: host records by `astype` (uploaded later at 8 bytes per element),
+        device records by epgx_signal_narrow into a new buffer -- the source is only read and not kept"""
+        from . import _lib
+        out = object.__new__(_Records)
+        out.nrec, out.shape, out.ncol, out.row_stride = self.nrec, self.shape, self.ncol, self.ncol
+        out.dtype = np.dtype(np.complex64)
+        if self.keep is None:
+            with np.errstate(over="ignore"):             # (overflow goes to Inf, as on the device)
+                out._host = self._host.astype(np.complex64)
+            out.keep, out.ctx, out.device = None, None, None
+        else:
+            out.keep = _lib.signal_narrow(self.ctx, self.ptr, self.row_stride, self.nrec, self.ncol)
+            out.ctx, out.device = self.ctx, self.device
+        return out
+
     @property
     def ptr(self):
         """address of record 0 (None when the buffer behind a handle was freed: the library's EpgxError)"""
@@ -104,21 +144,29 @@ class Dictionary:
     """a dictionary on the device with its norms `n_a` (computed once, kept in HBM).
 
     handle: DeviceSignal over the whole grid, DeviceJacobian (its probed-state row), or a NumPy array `[nrec, *grid]`.
-    `.grid`, `.natoms`, `.nrec`; `.norms` downloads `n_a` as float64 `grid`."""
+    dtype: None / complex128, or complex64: the dictionary then owns a dense complex64 buffer `[nrec][natoms]` that holds the
+    records rounded once (a handle is narrowed on the device and neither modified nor kept, an array by `astype` on the host).
+    `.grid`, `.natoms`, `.nrec`, `.dtype`; `.norms` downloads `n_a` as float64 `grid`; `.download()` the records."""
 
-    def __init__(self, handle, device=None):
+    def __init__(self, handle, device=None, dtype=None):
         from . import _lib
-        rec = handle if isinstance(handle, _Records) else _Records(handle, "dictionary")
+        internal = isinstance(handle, _Records)
+        want = handle.dtype if internal and dtype is None else _dtype(dtype, "dictionary")
+        rec = handle if internal else _Records(handle, "dictionary")
         if len(rec.shape) == 0 and rec.keep is None:
             raise ValueError(f"dictionary: an array [nrec, *grid] with at least one grid axis, got shape ({rec.nrec},)")
         if rec.nrec < 1 or rec.ncol < 1:
             raise ValueError(f"dictionary: {rec.nrec} records of {rec.ncol} atoms; both must be at least 1")
+        if want != rec.dtype:
+            if want != np.complex64:
+                raise NotImplementedError("dictionary: complex64 records are not widened to complex128")
+            rec = rec.narrowed()
         if rec.keep is None:
             rec.upload(_lib.get_context(device))
         self._rec = rec
-        self.grid, self.natoms, self.nrec, self.device = rec.shape, rec.ncol, rec.nrec, rec.device
+        self.grid, self.natoms, self.nrec, self.device, self.dtype = rec.shape, rec.ncol, rec.nrec, rec.device, rec.dtype
         self.basis = None          # the `Basis` of a dictionary that `compress` made
-        self._norms = _lib.signal_norms(rec.ctx, rec.ptr, rec.row_stride, rec.nrec, rec.ncol)
+        self._norms = _lib.signal_norms(rec.ctx, rec.ptr, rec.row_stride, rec.nrec, rec.ncol, c64=self.dtype == np.complex64)
 
     @property
     def norms(self):
@@ -128,8 +176,32 @@ class Dictionary:
     def records(self):
         """the records as a DeviceSignal `[nrec, *grid]` (np.asarray downloads them)"""
         from . import functions, _lib
+        if self.dtype != np.complex128:
+            raise NotImplementedError("records: a DeviceSignal holds complex128; download() returns the complex64 records")
         keep = self._rec.keep
         return functions.DeviceSignal(keep, self.nrec, self.grid, 0, 1) if isinstance(keep, _lib.DeviceBuffer) else keep
+
+    def download(self):
+        """the records as a NumPy array `[nrec, *grid]` of the dictionary's dtype"""
+        if self.dtype == np.complex128:
+            return np.asarray(self.records).reshape((self.nrec,) + self.grid)
+        from . import _lib
+        keep = self._rec.keep
+        if not keep.ptr:
+            raise _lib.EpgxError("download: the dictionary's buffer was freed")
+        return keep.download(np.complex64, (self.nrec, self.natoms)).reshape((self.nrec,) + self.grid)
+
+    def astype(self, dtype):
+        """complex64 of a complex128 dictionary: a new `Dictionary` that owns the records rounded once on the device (`.basis` is
+        carried along); the dictionary's own dtype: `self`; complex128 of a complex64 one: NotImplementedError"""
+        want = _dtype(dtype, "astype")
+        if want == self.dtype:
+            return self
+        if want == np.complex128:
+            raise NotImplementedError("astype: a complex64 dictionary is not widened; build it from the complex128 records")
+        out = Dictionary(self._rec.narrowed())
+        out.basis = self.basis
+        return out
 
 
 class MatchResult:
@@ -158,7 +230,11 @@ def match(dictionary, signals, *, nsplit=0):
     `match(Dictionary(U^H D), U^H S)`: signals with `basis.nrec` records are projected on the device first (`basis.project`),
     signals with `basis.rank` records are taken as projected already, any other record count raises ValueError (where rank =
     nrec both counts coincide and the signals count as not yet projected).  `score` is then relative to the energy of the
-    PROJECTED signal, sum_r |Sc[r,m]|^2 -- the part of the signal outside the basis does not lower it."""
+    PROJECTED signal, sum_r |Sc[r,m]|^2 -- the part of the signal outside the basis does not lower it.
+
+    With a complex64 dictionary the signals are rounded once to complex64 (a host array by `astype`, a DeviceSignal on the
+    device into a temporary) and matched in single precision (module docstring); signals that a compressed complex64 dictionary
+    projects are projected in float64 first and rounded then.  Anything that is not a `Dictionary` is matched in complex128."""
     from . import _lib
     sig = _Records(signals, "signals")
     basis = dictionary.basis if isinstance(dictionary, Dictionary) else None
@@ -193,9 +269,12 @@ def _match_records(dictionary, sig, nsplit):
     rec = dictionary._rec
     if sig.device is not None and (sig.device != rec.device or sig.ctx is not rec.ctx):
         raise ValueError(f"signals: on device {sig.device}, the dictionary on device {rec.device}; both must be on one GPU (and context)")
+    c64 = dictionary.dtype == np.complex64
+    if c64:
+        sig = sig.narrowed()       # host records by astype; a handle on the device, into a temporary that is freed below
     sig.upload(rec.ctx)
     index, scale, score = _lib.signal_match(rec.ctx, rec.ptr, rec.row_stride, dictionary._norms.ptr.value if dictionary._norms.ptr else None,
-                                            dictionary.natoms, sig.ptr, sig.row_stride, sig.nrec, sig.ncol, nsplit=nsplit)
+                                            dictionary.natoms, sig.ptr, sig.row_stride, sig.nrec, sig.ncol, nsplit=nsplit, c64=c64)
     if isinstance(sig.keep, _lib.DeviceBuffer):
         sig.keep.free()        # (stream-ordered: the block is recycled behind the kernels that read it)
     return MatchResult(index.reshape(sig.shape), scale.reshape(sig.shape), score.reshape(sig.shape), dictionary.grid)
@@ -309,7 +388,7 @@ class Basis:
         return self._project(rec, ctx)
 
 
-def compress(dictionary, rank=None, energy=None, *, nsplit=0, device=None):
+def compress(dictionary, rank=None, energy=None, *, nsplit=0, device=None, dtype=None):
     """SVD compression of a dictionary in HBM (module docstring): returns the `Basis`; `basis.dictionary` is the compressed
     `Dictionary` [rank, *grid] that `match` takes.
 
@@ -319,8 +398,15 @@ def compress(dictionary, rank=None, energy=None, *, nsplit=0, device=None):
     natoms alone, so that the same dictionary gives the same basis on every machine).
     ValueError: rank above 64 or nrec, an energy that needs more than 64, a rank that reaches unresolved eigenvalues
     (lambda_r <= nrec 2^-52 lambda_0), a dictionary without a valid atom.
+    dtype=np.complex64: `basis.dictionary` is the projected dictionary rounded once to complex64 (the complex128 intermediate is
+    freed); Gram matrix, eigenvectors and projection stay float64, `basis.U`, `basis.s`, `basis.energy` keep their bits.  A
+    complex64 INPUT dictionary raises NotImplementedError (no single-precision Gram matrix).
     Only G (16 nrec^2 bytes) comes down and U (16 nrec rank bytes) goes up; the dictionary does not move."""
     from . import _lib, functions
+    want = _dtype(dtype, "compress")
+    if isinstance(dictionary, Dictionary) and dictionary.dtype != np.complex128:
+        raise NotImplementedError("compress: a complex64 dictionary; the Gram matrix is taken in float64 -- compress the complex128 "
+                                  "dictionary with dtype=np.complex64")
     if (rank is None) == (energy is None):
         raise ValueError("compress: exactly one of rank= and energy= must be given")
     if energy is not None and not 0.0 < energy <= 1.0:
@@ -345,5 +431,9 @@ def compress(dictionary, rank=None, energy=None, *, nsplit=0, device=None):
     ubuf = basis._device(ctx)
     out = _lib.signal_project(ctx, ubuf.ptr.value, basis.rank, rec.ptr, rec.row_stride, dictionary.nrec, dictionary.natoms)
     cdic = Dictionary(functions.DeviceSignal(out, basis.rank, dictionary.grid, 0, 1))
+    if want == np.complex64:
+        wide, cdic = cdic, cdic.astype(np.complex64)
+        wide._norms.free()          # (stream-ordered: the blocks are recycled behind the kernel that narrowed them)
+        out.free()
     cdic.basis, basis.dictionary = basis, cdic
     return basis

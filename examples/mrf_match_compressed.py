@@ -10,7 +10,11 @@ their norms there, and `match.match` returns per voxel the best grid point, the 
 The train: an inversion, then `ntr` excitations with a slowly varying flip angle and a gradient spoiler per TR (FISP-like).
 The phantom: voxels at OFF-grid (T1, T2) with a complex density and seeded Gaussian noise.
 
-    python examples/mrf_match_compressed.py [n_T1] [n_T2] [ntr] [nvoxel] [energy]      # defaults 64, 64, 200, 1000, 0.99999
+    python examples/mrf_match_compressed.py [n_T1] [n_T2] [ntr] [nvoxel] [energy] [dtype]  # defaults 64, 64, 200, 1000, 0.99999, complex128
+
+With dtype `complex64` the compressed dictionary is kept in single precision (`compress(..., dtype=np.complex64)`: the projected
+dictionary rounded once, half the bytes) and matched on the fp32 matrix cores; one more line then compares it with the
+complex128 match.
 """
 import os
 import sys
@@ -25,6 +29,7 @@ n2 = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 ntr = int(sys.argv[3]) if len(sys.argv) > 3 else 200
 nvox = int(sys.argv[4]) if len(sys.argv) > 4 else 1000
 energy = float(sys.argv[5]) if len(sys.argv) > 5 else 0.99999
+dtype = np.dtype(sys.argv[6]) if len(sys.argv) > 6 else np.dtype(np.complex128)
 
 TR, TE = 12.0, 3.0                                                       # ms
 angles = 10.0 + 50.0 * np.abs(np.sin(np.pi * np.arange(ntr) / 100.0))    # degrees
@@ -63,3 +68,7 @@ print(f"    T2: grid spacing {step2:.1f} %, matched within median {np.median(err
 print(f"    rank {basis.rank} of {basis.nrec} records keeps {basis.energy:.8f} of the energy; "
       f"{np.mean(res.index == full.index) * 100:.1f} % of the voxels get the atom of the uncompressed match")
 print(f"    density: median |scale / true - 1| = {np.median(np.abs(res.scale / density - 1)):.3f};  score: median {np.median(res.score):.5f}")
+if dtype == np.complex64:
+    single = match.match(match.compress(dictionary, energy=energy, dtype=np.complex64).dictionary, signals)
+    print(f"    complex64 compressed dictionary ({8 * basis.rank * n1 * n2} bytes): {np.mean(single.index == res.index) * 100:.1f} % of the voxels "
+          f"get the atom of the complex128 match; largest |scale - scale128| = {np.max(np.abs(single.scale - res.scale)):.2e}")

@@ -650,6 +650,26 @@ int epgx_signal_gram(epgx_ctx *ctx, const void *dict, int64_t dict_row_stride, c
 int epgx_signal_project(epgx_ctx *ctx, const void *basis, int32_t rank, const void *src, int64_t src_row_stride, int32_t nrec,
                         int64_t ncol, void *out, int64_t out_row_stride);
 
+/* Single-precision matching (csrc/epgx_match32.hip): the calls above on complex64 records, elements of 8 bytes (float re, im),
+ * pointers aligned to 8 bytes, strides in elements of 8 bytes.  A complex64 dictionary is DEFINED as the complex128 one rounded
+ * once, per component, to nearest even, subnormals kept, overflow to +-Inf (NumPy's astype(complex64)), and matching on the
+ * rounded operands D32, S32 as
+ *   n_a      = sum_t |D32[t,a]|^2, accumulated in fp64 in record order           (epgx_signal_norms_c64: out[a] float64)
+ *   c[a,m]   = sum_t conj(D32[t,a]) S32[t,m], accumulated in fp32 (v_mfma_f32_16x16x4_f32: an exact k-ordered fmaf chain)
+ *   q[a,m]   = (Re c^2 + Im c^2) * (1 / n_a), evaluated in fp64 from the fp32 c
+ * with the rule, the invalid atoms, out_index / out_scale / out_score (int64, complex128, float64; scale = c / n and score =
+ * sqrt(q / sum_t |S32[t,m]|^2) in fp64), nsplit and the scratch of epgx_signal_match.  The records of a pair are consumed in
+ * steps of 4 from t = 0, the tail padded with zeros: the bits of c[a,m] depend on column a, column m and nrec alone.
+ * The rounding itself is epgx_signal_narrow above (rows of any stride on both sides; the source is only read).
+ * Both calls are stream-ordered; nothing is uploaded or synchronised.
+ * Errors (nothing is launched): EPGX_ERR_INVALID for a NULL or misaligned pointer (16 bytes: out_scale; 8: the others),
+ * nrec < 1, natoms < 1, nmeas < 0, nsplit < 0 or > natoms, dict_row_stride (row_stride) < natoms, sig_row_stride < nmeas, an
+ * extent (nrec - 1) * stride + columns or a launch nsplit * ceil(nmeas / 64) that overflows.  nmeas = 0: nothing to do. */
+int epgx_signal_norms_c64(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int64_t natoms, void *out);
+int epgx_signal_match_c64(epgx_ctx *ctx, const void *dict, int64_t dict_row_stride, const void *norms, int64_t natoms,
+                          const void *sig, int64_t sig_row_stride, int32_t nrec, int64_t nmeas, int32_t nsplit,
+                          void *out_index, void *out_scale, void *out_score);
+
 /* Convenience for bindings that only have host arrays (what a ctypes/NumPy binding inside
  * the reference would call once per simulate()): builds the plan, runs the whole sequence
  * state-resident over the full grid, copies signal (and optionally the final state) back. */
