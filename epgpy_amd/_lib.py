@@ -21,6 +21,10 @@ RESIDENT_ONLY_K = 2048   # state-resident launches from equilibrium only: four w
 # a halo of TILED_H orders on either side, interiors of TILED_W orders; the state in HBM at a multiple of 64 orders
 TILED_M, TILED_H = 8, 32
 TILED_W = 64 * TILED_M - 2 * TILED_H
+# derivative plans above MAX_DERIV_K on the same tiles (tiled_deriv_kernel<TILED_M, TILED_H, NSP, V>): a wavefront keeps 1 + V
+# windows of 96 registers each; TILED_DERIV_V derivative states fit the 512 registers of a wavefront without scratch
+# (V = 1: 256 VGPRs + 48 AGPRs, V = 2: 256 + 152; a third window spills 136 bytes per lane)
+TILED_DERIV_V = 2
 PACKED_K = (16, 32)  # state-resident only: four / two voxels per wavefront (csrc/epgx_packed_kernels.hip.h)
 MAX_DERIV_K = 1024  # derivative plans: the state and its derivative states of a voxel live in registers (one wavefront per voxel)
 
@@ -148,6 +152,9 @@ SYMBOLS = {
     "epgx_run_tiled": (_i, [_p, _p, _i64, _i64, _p, _i32, _p, _i64, _i64, _i64]),
     "epgx_tiled_info": (_i, [_p, _p, _i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i64),
                              ctypes.POINTER(_i32), ctypes.c_char_p, _i64]),
+    "epgx_run_tiled_deriv": (_i, [_p, _p, _i64, _i64, _p, _i32, _p, _i64, _i64, _i64]),
+    "epgx_tiled_deriv_info": (_i, [_p, _p, _i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i64),
+                                   ctypes.POINTER(_i32), ctypes.c_char_p, _i64]),
     "epgx_signal_reduce": (_i, [_p, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _i64, _i64]),
     "epgx_signal_crlb": (_i, [_p, _p, _i64, _i64, _i32, _i32, _i32, _p, _i64, _i64, _p, _d, _i32, _p]),
     "epgx_signal_crlb_grad": (_i, [_p, _p, _i64, _i64, _i32, _i32, _i32, _p, _i64, _i64, _p, _i64, _i32, _p, _p, _p, _d, _i32, _p, _p]),
@@ -948,4 +955,21 @@ def tiled_info(ctx, plan, Kbuf, top0=0):
     buf = ctypes.create_string_buffer(160)
     check(ctx.lib.epgx_tiled_info(ctx.handle, plan.handle, int(Kbuf), int(top0), ctypes.byref(blocks), ctypes.byref(shifts),
                                   ctypes.byref(tiles), ctypes.byref(peak), buf, len(buf)), "epgx_tiled_info")
+    return dict(blocks=blocks.value, shifts=shifts.value, tile_launches=tiles.value, peak=peak.value, names=buf.value.decode())
+
+
+def run_tiled_deriv(ctx, plan, vox0, nvox, state_in, Kbuf, signal_ptr, signal_ld, signal_col0, slab_voxels=0):
+    """a first-order derivative plan on the tiled path (include/epgx.h epgx_run_tiled_deriv): 1 + n_vars rows per ADC"""
+    check(ctx.lib.epgx_run_tiled_deriv(ctx.handle, plan.handle, int(vox0), int(nvox), state_in.handle if state_in is not None else None,
+                                       int(Kbuf), ctypes.c_void_p(signal_ptr) if signal_ptr else None, int(signal_ld),
+                                       int(signal_col0), int(slab_voxels)), "epgx_run_tiled_deriv")
+
+
+def tiled_deriv_info(ctx, plan, Kbuf, top0=0):
+    """the schedule epgx_run_tiled_deriv follows: dict(blocks, shifts, tile_launches, peak, names)"""
+    blocks, shifts, peak = _i32(), _i32(), _i32()
+    tiles = _i64()
+    buf = ctypes.create_string_buffer(160)
+    check(ctx.lib.epgx_tiled_deriv_info(ctx.handle, plan.handle, int(Kbuf), int(top0), ctypes.byref(blocks), ctypes.byref(shifts),
+                                        ctypes.byref(tiles), ctypes.byref(peak), buf, len(buf)), "epgx_tiled_deriv_info")
     return dict(blocks=blocks.value, shifts=shifts.value, tile_launches=tiles.value, peak=peak.value, names=buf.value.decode())

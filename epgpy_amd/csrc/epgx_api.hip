@@ -2014,11 +2014,20 @@ static void tiled_knobs(int &M, int &H) {   // EPGX_TILED_M=16: 16 orders per la
 }
 
 
-static int tiled_check(epgx_ctx *ctx, const epgx_plan *pl, int32_t Kbuf, const char *who) {
+static constexpr int TILED_DERIV_V = 2;      // derivative states one launch of tiled_deriv_kernel<8, 32, NSP, V> carries (_lib.py TILED_DERIV_V)
+
+static int tiled_check(epgx_ctx *ctx, const epgx_plan *pl, int32_t Kbuf, const char *who, bool deriv = false) {
     if (!ctx || !pl) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
     if (pl->ctx != ctx) return fail(EPGX_ERR_INVALID, "%s: plan belongs to another context", who);
     if (Kbuf < 64 || Kbuf % 64 != 0 || Kbuf > (1 << 24)) return fail(EPGX_ERR_INVALID, "%s: Kbuf=%d is not a multiple of 64 in [64, 2^24]", who, Kbuf);
-    if (pl->host.n_vars > 0) return fail(EPGX_ERR_UNSUPPORTED, "%s: plans with derivative states run at K <= 1024 (epgx_run)", who);
+    if (!deriv && pl->host.n_vars > 0)
+        return fail(EPGX_ERR_UNSUPPORTED, "%s: plans with derivative states run at K <= 1024 (epgx_run)", who);
+    if (deriv) {
+        if (pl->host.second)
+            return fail(EPGX_ERR_UNSUPPORTED, "%s: second-order plans (EPGX_DERIV_SECOND) run at K <= 512 (epgx_run)", who);
+        if (pl->host.n_vars < 1 || pl->host.n_vars > TILED_DERIV_V)
+            return fail(EPGX_ERR_UNSUPPORTED, "%s: the plan has %d derivative states, a launch carries 1 .. %d", who, pl->host.n_vars, TILED_DERIV_V);
+    }
     for (size_t i = 0; i < pl->host.ops.size(); ++i) {
         const int oc = pl->host.ops[i].opcode;
         if (oc == EPGX_OP_X || oc == EPGX_OP_GS || oc == EPGX_OP_D)
@@ -2027,12 +2036,13 @@ static int tiled_check(epgx_ctx *ctx, const epgx_plan *pl, int32_t Kbuf, const c
     return EPGX_OK;
 }
 
-extern "C" int epgx_tiled_info(epgx_ctx *ctx, const epgx_plan *plan, int32_t Kbuf, int32_t top0, int32_t *blocks, int32_t *shifts,
-                               int64_t *tile_launches, int32_t *peak, char *names, int64_t name_bytes) {
-    if (int rc = tiled_check(ctx, plan, Kbuf, "epgx_tiled_info")) return rc;
-    if (top0 < 0 || top0 >= Kbuf) return fail(EPGX_ERR_INVALID, "epgx_tiled_info: top0=%d outside [0, Kbuf)", top0);
+static int tiled_info(const char *who, bool deriv, epgx_ctx *ctx, const epgx_plan *plan, int32_t Kbuf, int32_t top0, int32_t *blocks,
+                      int32_t *shifts, int64_t *tile_launches, int32_t *peak, char *names, int64_t name_bytes) {
+    if (int rc = tiled_check(ctx, plan, Kbuf, who, deriv)) return rc;
+    if (top0 < 0 || top0 >= Kbuf) return fail(EPGX_ERR_INVALID, "%s: top0=%d outside [0, Kbuf)", who, top0);
     int M, H;
     tiled_knobs(M, H);
+    if (deriv) M = 8, H = 32;      // (the derivative kernel exists at 8 orders per lane only)
     TiledSchedule ts;
     if (int rc = tiled_schedule(plan->host, Kbuf, top0, M, H, knobs(), ts)) return rc;
     const int nb = (int)ts.steps.size() - ts.n_shift;
@@ -2041,36 +2051,53 @@ extern "C" int epgx_tiled_info(epgx_ctx *ctx, const epgx_plan *plan, int32_t Kbu
     if (tile_launches) *tile_launches = ts.tile_launches;
     if (peak) *peak = ts.peak;
     if (names && name_bytes > 1) {
-        std::string n = nb ? "tiled_kernel<" + std::to_string(M) + ", " + std::to_string(H) + ">" : std::string();
+        std::string n = nb ? std::string(deriv ? "tiled_deriv_kernel<" : "tiled_kernel<") + std::to_string(M) + ", " + std::to_string(H) +
+                                 (deriv ? ", " + std::to_string(plan->host.n_vars) : std::string()) + ">"
+                           : std::string();
         if (ts.n_shift) n += std::string(n.empty() ? "" : " + ") + "tiled_shift";
         snprintf(names, (size_t)name_bytes, "%s", n.empty() ? "none" : n.c_str());
     }
     return EPGX_OK;
 }
 
-extern "C" int epgx_run_tiled(epgx_ctx *ctx, const epgx_plan *plan_c, int64_t vox0, int64_t nvox, const epgx_state *in, int32_t Kbuf,
-                              void *signal, int64_t signal_ld, int64_t signal_col0, int64_t slab_voxels) {
-    if (int rc = tiled_check(ctx, plan_c, Kbuf, "epgx_run_tiled")) return rc;
+extern "C" int epgx_tiled_info(epgx_ctx *ctx, const epgx_plan *plan, int32_t Kbuf, int32_t top0, int32_t *blocks, int32_t *shifts,
+                               int64_t *tile_launches, int32_t *peak, char *names, int64_t name_bytes) {
+    return tiled_info("epgx_tiled_info", false, ctx, plan, Kbuf, top0, blocks, shifts, tile_launches, peak, names, name_bytes);
+}
+
+extern "C" int epgx_tiled_deriv_info(epgx_ctx *ctx, const epgx_plan *plan, int32_t Kbuf, int32_t top0, int32_t *blocks, int32_t *shifts,
+                                     int64_t *tile_launches, int32_t *peak, char *names, int64_t name_bytes) {
+    return tiled_info("epgx_tiled_deriv_info", true, ctx, plan, Kbuf, top0, blocks, shifts, tile_launches, peak, names, name_bytes);
+}
+
+// both tiled entry points.  `deriv`: a voxel holds nw = 1 + n_vars state windows [3][Kbuf] per buffer (the state, then its
+// derivative states, which start at zero) and the blocks run on tiled_deriv_kernel; a shift by more than H moves every window
+static int run_tiled(const char *who, bool deriv, epgx_ctx *ctx, const epgx_plan *plan_c, int64_t vox0, int64_t nvox, const epgx_state *in,
+                     int32_t Kbuf, void *signal, int64_t signal_ld, int64_t signal_col0, int64_t slab_voxels) {
+    if (int rc = tiled_check(ctx, plan_c, Kbuf, who, deriv)) return rc;
     epgx_plan *pl = const_cast<epgx_plan *>(plan_c);
+    const int nw = deriv ? 1 + pl->host.n_vars : 1;
     if (nvox < 0 || vox0 < 0 || vox0 + nvox > pl->nvox_total)
-        return fail(EPGX_ERR_INVALID, "epgx_run_tiled: voxel range [%lld,%lld) outside the grid (%lld voxels)", (long long)vox0,
+        return fail(EPGX_ERR_INVALID, "%s: voxel range [%lld,%lld) outside the grid (%lld voxels)", who, (long long)vox0,
                     (long long)(vox0 + nvox), (long long)pl->nvox_total);
-    if (slab_voxels < 0) return fail(EPGX_ERR_INVALID, "epgx_run_tiled: slab_voxels < 0");
+    if (slab_voxels < 0) return fail(EPGX_ERR_INVALID, "%s: slab_voxels < 0", who);
     if (in) {
-        if (in->ctx != ctx) return fail(EPGX_ERR_INVALID, "epgx_run_tiled: `in` belongs to another context");
+        if (in->ctx != ctx) return fail(EPGX_ERR_INVALID, "%s: `in` belongs to another context", who);
         if (in->nvox != nvox)
-            return fail(EPGX_ERR_INVALID, "epgx_run_tiled: `in` holds %lld voxels, range has %lld", (long long)in->nvox, (long long)nvox);
-        if (in->K > 1024) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run_tiled: `in` has %d orders (at most 1024)", in->K);
-        if (in->K > Kbuf) return fail(EPGX_ERR_INVALID, "epgx_run_tiled: `in` has %d orders, Kbuf=%d", in->K, Kbuf);
+            return fail(EPGX_ERR_INVALID, "%s: `in` holds %lld voxels, range has %lld", who, (long long)in->nvox, (long long)nvox);
+        if (in->K > 1024) return fail(EPGX_ERR_UNSUPPORTED, "%s: `in` has %d orders (at most 1024)", who, in->K);
+        if (in->K > Kbuf) return fail(EPGX_ERR_INVALID, "%s: `in` has %d orders, Kbuf=%d", who, in->K, Kbuf);
     }
     int M, H;
     tiled_knobs(M, H);
+    if (deriv) M = 8, H = 32;
     TiledSchedule ts;
     if (int rc = tiled_schedule(pl->host, Kbuf, in ? in->K - 1 : 0, M, H, knobs(), ts)) return rc;
+    if (deriv && ts.drecs.size() != ts.recs.size()) return fail(EPGX_ERR_INVALID, "%s: %zu records, %zu derivative records", who, ts.recs.size(), ts.drecs.size());
     if (ts.has_adc) {
-        if (!signal) return fail(EPGX_ERR_INVALID, "epgx_run_tiled: the plan contains an ADC but signal is NULL");
+        if (!signal) return fail(EPGX_ERR_INVALID, "%s: the plan contains an ADC but signal is NULL", who);
         if (signal_col0 < 0 || signal_col0 + nvox > signal_ld)
-            return fail(EPGX_ERR_INVALID, "epgx_run_tiled: signal columns [%lld,%lld) exceed signal_ld=%lld", (long long)signal_col0,
+            return fail(EPGX_ERR_INVALID, "%s: signal columns [%lld,%lld) exceed signal_ld=%lld", who, (long long)signal_col0,
                         (long long)(signal_col0 + nvox), (long long)signal_ld);
     }
     if (nvox == 0 || ts.steps.empty()) return EPGX_OK;
@@ -2078,46 +2105,59 @@ extern "C" int epgx_run_tiled(epgx_ctx *ctx, const epgx_plan *plan_c, int64_t vo
     std::lock_guard<std::mutex> plan_guard(pl->cache_lock);
     if (int rc = ensure_vidx(pl, vox0, nvox)) return rc;
     // two buffers [slab][3][Kbuf] + the density: at most 8 GiB per slab (as the two legs at 2048 orders)
-    const int64_t per_voxel = (int64_t)2 * 3 * Kbuf * sizeof(d2) + sizeof(double);
+    const int64_t per_voxel = (int64_t)2 * nw * 3 * Kbuf * sizeof(d2) + sizeof(double);
     int64_t slab = std::min<int64_t>((nvox + 3) & ~(int64_t)3, std::max<int64_t>(4, (((int64_t)8 << 30) / per_voxel) & ~(int64_t)3));
     if (knobs().slab_voxels > 0) slab = std::min<int64_t>(slab, (knobs().slab_voxels + 3) & ~3);
     if (slab_voxels > 0) slab = std::min<int64_t>(slab, slab_voxels);
-    const size_t buf_bytes = (size_t)slab * 3 * Kbuf * sizeof(d2);
-    void *mem = nullptr, *d_recs = nullptr;
+    const size_t buf_bytes = (size_t)slab * nw * 3 * Kbuf * sizeof(d2);
+    void *mem = nullptr, *d_recs = nullptr, *d_drecs = nullptr;
     const size_t rec_bytes = (ts.recs.size() + 2) * sizeof(Rec);     // two padding records (the kernel fetches ahead)
+    const size_t drec_bytes = (ts.recs.size() + 2) * sizeof(DRec);
     hipError_t e = dev_alloc(ctx, &d_recs, rec_bytes);
+    if (e == hipSuccess && deriv) e = dev_alloc(ctx, &d_drecs, drec_bytes);
     if (e == hipSuccess) e = dev_alloc(ctx, &mem, 2 * buf_bytes + (size_t)slab * sizeof(double));
     if (e != hipSuccess) {
         dev_free(ctx, d_recs);
-        return fail(EPGX_ERR_NOMEM, "epgx_run_tiled: %lld voxels x 2 x %d orders: %s", (long long)slab, Kbuf, hipGetErrorString(e));
+        dev_free(ctx, d_drecs);
+        return fail(EPGX_ERR_NOMEM, "%s: %lld voxels x 2 x %d x %d orders: %s", who, (long long)slab, nw, Kbuf, hipGetErrorString(e));
     }
     ts.recs.resize(ts.recs.size() + 2);
     memset(&ts.recs[ts.recs.size() - 2], 0, 2 * sizeof(Rec));
     e = hipMemcpyAsync(d_recs, ts.recs.data(), rec_bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);     // (the host vector goes away with this call)
+    if (deriv) {
+        ts.drecs.resize(ts.recs.size());
+        memset(&ts.drecs[ts.drecs.size() - 2], 0, 2 * sizeof(DRec));
+        if (e == hipSuccess) e = hipMemcpyAsync(d_drecs, ts.drecs.data(), drec_bytes, hipMemcpyHostToDevice, ctx->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);     // (the host vectors go away with this call)
     d2 *buf[2] = {(d2 *)mem, (d2 *)((char *)mem + buf_bytes)};
     double *dens = (double *)((char *)mem + 2 * buf_bytes);
     if (tracing())
-        fprintf(stderr, "[epgx] run_tiled: %zu records, %zu steps (%d shifts by more than %d), %lld tile launches, peak order %d, Kbuf %d, "
-                        "slabs of %lld voxels\n", ts.recs.size() - 2, ts.steps.size(), ts.n_shift, H, (long long)ts.tile_launches, ts.peak,
+        fprintf(stderr, "[epgx] %s: %d window(s) per voxel, %zu records, %zu steps (%d shifts by more than %d), %lld tile launches, peak order %d, Kbuf %d, "
+                        "slabs of %lld voxels\n", who + 5, nw, ts.recs.size() - 2, ts.steps.size(), ts.n_shift, H, (long long)ts.tile_launches, ts.peak,
                 Kbuf, (long long)slab);
     const int W = 64 * M - 2 * H;
     for (int64_t c0 = 0; c0 < nvox && e == hipSuccess; c0 += slab) {
         const int64_t nv = std::min(slab, nvox - c0);
-        const size_t used = (size_t)nv * 3 * Kbuf * sizeof(d2);
+        const size_t used = (size_t)nv * nw * 3 * Kbuf * sizeof(d2);
         e = hipMemsetAsync(buf[0], 0, used, ctx->stream);
         if (e == hipSuccess) e = hipMemsetAsync(buf[1], 0, used, ctx->stream);
-        if (e == hipSuccess && in)
+        if (e == hipSuccess && in && !deriv)
             e = hipMemcpy2DAsync(buf[0], (size_t)Kbuf * sizeof(d2), in->data + (size_t)c0 * 3 * in->K, (size_t)in->K * sizeof(d2),
                                  (size_t)in->K * sizeof(d2), (size_t)nv * 3, hipMemcpyDeviceToDevice, ctx->stream);
+        for (int comp = 0; comp < 3 && e == hipSuccess && in && deriv; ++comp)   // (the start state is window 0 of every voxel: one row per voxel and component)
+            e = hipMemcpy2DAsync(buf[0] + (size_t)comp * Kbuf, (size_t)nw * 3 * Kbuf * sizeof(d2),
+                                 in->data + (size_t)c0 * 3 * in->K + (size_t)comp * in->K, (size_t)3 * in->K * sizeof(d2),
+                                 (size_t)in->K * sizeof(d2), (size_t)nv, hipMemcpyDeviceToDevice, ctx->stream);
         if (e == hipSuccess && in) e = hipMemcpyAsync(dens, in->dens + c0, (size_t)nv * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
-        if (e == hipSuccess && !in) e = epgx_launch_tiled_equilibrium(ctx->stream, buf[0], dens, nullptr, nv, Kbuf);
+        if (e == hipSuccess && !in) e = epgx_launch_tiled_equilibrium(ctx->stream, buf[0], dens, nullptr, nv, Kbuf, nw);
         for (size_t j = 0; j < ts.steps.size() && e == hipSuccess; ++j) {
             const TiledStep &st = ts.steps[j];
             const d2 *src = buf[j & 1];
             d2 *dst = buf[(j + 1) & 1];
             if (st.shift) {
-                e = epgx_launch_tiled_shift(ctx->stream, src, dst, nv, Kbuf, (int32_t)std::min<int64_t>(Kbuf, (int64_t)st.tiles * W), st.shift,
+                // (the windows of a voxel follow each other at the stride of a voxel of the plain layout: nv * nw "voxels")
+                e = epgx_launch_tiled_shift(ctx->stream, src, dst, nv * nw, Kbuf, (int32_t)std::min<int64_t>(Kbuf, (int64_t)st.tiles * W), st.shift,
                                             st.kmax);
                 continue;
             }
@@ -2139,13 +2179,33 @@ extern "C" int epgx_run_tiled(epgx_ctx *ctx, const epgx_plan *plan_c, int64_t vo
             a.t.vidx_ld = pl->vidx_nvox;
             a.t.vox0 = vox0 + c0;
             a.t.dense_spaces = pl->dense_spaces;
-            e = epgx_launch_tiled(ctx->stream, a, M, H, pl->host.n_spaces);
+            if (!deriv) {
+                e = epgx_launch_tiled(ctx->stream, a, M, H, pl->host.n_spaces);
+                continue;
+            }
+            TiledDerivArgs da;
+            memset(&da, 0, sizeof(da));
+            da.a = a;
+            da.drecs = (const DRec *)d_drecs;
+            da.through_plain = (pl->deriv_flags & EPGX_DERIV_THROUGH_PLAIN_OPS) ? 1 : 0;
+            e = epgx_launch_tiled_deriv(ctx->stream, da, M, H, pl->host.n_spaces, pl->host.n_vars);
         }
     }
     dev_free(ctx, mem);
     dev_free(ctx, d_recs);
-    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_run_tiled: %s", hipGetErrorString(e));
+    dev_free(ctx, d_drecs);
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return EPGX_OK;
+}
+
+extern "C" int epgx_run_tiled(epgx_ctx *ctx, const epgx_plan *plan, int64_t vox0, int64_t nvox, const epgx_state *in, int32_t Kbuf,
+                              void *signal, int64_t signal_ld, int64_t signal_col0, int64_t slab_voxels) {
+    return run_tiled("epgx_run_tiled", false, ctx, plan, vox0, nvox, in, Kbuf, signal, signal_ld, signal_col0, slab_voxels);
+}
+
+extern "C" int epgx_run_tiled_deriv(epgx_ctx *ctx, const epgx_plan *plan, int64_t vox0, int64_t nvox, const epgx_state *in, int32_t Kbuf,
+                                    void *signal, int64_t signal_ld, int64_t signal_col0, int64_t slab_voxels) {
+    return run_tiled("epgx_run_tiled_deriv", true, ctx, plan, vox0, nvox, in, Kbuf, signal, signal_ld, signal_col0, slab_voxels);
 }
 
 // ------------------------------------------------------------------------------ RCCL (loaded on first use)

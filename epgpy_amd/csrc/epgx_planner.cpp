@@ -929,13 +929,18 @@ int tiled_schedule(const PlanHost &ph, int Kbuf, int top0, int M, int H, const K
     const int n_ops = (int)ph.ops.size();
     pack_records(ph, 0, n_ops, 1 << 30, kn, packed, drecs, use_lds, ts.has_adc, elog);
     const int W = 64 * M - 2 * H;
-    struct Item { Rec r; int big; };    // big: 0, or the shift of a step of its own
+    struct Item { Rec r; int big; DRec d; };    // big: 0, or the shift of a step of its own; d: the record's partials (derivative plans)
     std::vector<Item> items;
     const uint32_t probe = F_ADC | F_ADC_Z;
-    for (const Rec &r : packed) {
+    const bool deriv = !drecs.empty();
+    DRec none;                          // a record made here (unit shift, probe) has no partials
+    memset(&none, 0, sizeof(none));
+    for (size_t ri = 0; ri < packed.size(); ++ri) {
+        const Rec &r = packed[ri];
+        const DRec &d = deriv ? drecs[ri] : none;
         const int n = ((r.flags & F_S) && !(r.flags & F_FOLD)) ? r.shift : 1;
         if (!(r.flags & F_S) || std::abs(n) <= 1) {
-            items.push_back({r, 0});
+            items.push_back({r, 0, d});
             continue;
         }
         Rec head = r;
@@ -943,22 +948,22 @@ int tiled_schedule(const PlanHost &ph, int Kbuf, int top0, int M, int H, const K
         if (std::abs(n) > H) {
             head.flags &= ~F_S;
             head.shift = 0;
-            if (head.flags & 0xffffffu) items.push_back({with_leaf(head), 0});
+            if (head.flags & 0xffffffu) items.push_back({with_leaf(head), 0, d});
             Rec step;
             memset(&step, 0, sizeof(step));
             step.flags = r.flags & F_TRUNC;
             step.kmax = r.kmax;
-            items.push_back({step, n});
+            items.push_back({step, n, none});
         } else {
             head.shift = n > 0 ? 1 : -1;
-            items.push_back({with_leaf(head), 0});
+            items.push_back({with_leaf(head), 0, d});
             for (int j = 1; j < std::abs(n); ++j) {
                 Rec one;
                 memset(&one, 0, sizeof(one));
                 one.flags = F_S | (j + 1 == std::abs(n) ? (r.flags & F_TRUNC) : 0u);
                 one.shift = n > 0 ? 1 : -1;
                 one.kmax = r.kmax;
-                items.push_back({with_leaf(one), 0});
+                items.push_back({with_leaf(one), 0, none});
             }
             if (!(r.flags & probe)) continue;
             Rec &last = items.back().r;
@@ -972,10 +977,11 @@ int tiled_schedule(const PlanHost &ph, int Kbuf, int top0, int M, int H, const K
             memset(&adc, 0, sizeof(adc));
             adc.flags = r.flags & probe;
             adc.slot = r.slot;
-            items.push_back({with_leaf(adc), 0});
+            items.push_back({with_leaf(adc), 0, none});
         }
     }
     ts.recs.clear();
+    ts.drecs.clear();
     ts.steps.clear();
     ts.peak = top0;
     ts.n_shift = 0;
@@ -1024,6 +1030,7 @@ int tiled_schedule(const PlanHost &ph, int Kbuf, int top0, int M, int H, const K
         if (r.flags & F_TRUNC) top = std::min(top, r.kmax);
         ts.peak = std::max(ts.peak, top);
         ts.recs.push_back(r);
+        if (deriv) ts.drecs.push_back(it.d);
         cur.rec1 = (int)ts.recs.size();
     }
     if (cur.rec1 > cur.rec0) close(cur);

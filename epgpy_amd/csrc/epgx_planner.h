@@ -124,7 +124,8 @@ RangeLists build_range(const PlanHost &ph, int begin, int end, int K, const Knob
 //   * a shift by 2 .. H orders becomes |n| records of S(+-1) (the same moves, the truncation and the probe on the last);
 //   * a shift by more than H becomes a step of its own (tiled_shift_kernel): the stages in front of it stay a record, the
 //     probe behind it becomes one;
-// and the list is cut into blocks whose shifts add up to at most H.  `top` = the highest order that can hold anything, as in
+// and the list is cut into blocks whose shifts add up to at most H.  A derivative plan (n_vars > 0) carries a DRec per record,
+// parallel to `recs` (epgx_run_tiled_deriv): the stages keep theirs, the unit shifts and probes made here have no partials.  `top` = the highest order that can hold anything, as in
 // build_range plus truncations and resets; a launch covers the tiles up to the top after its block, and at least the tiles the
 // launch before the previous one wrote into the same buffer (so no tile of the output buffer keeps a stale value).
 struct TiledStep {
@@ -136,6 +137,7 @@ struct TiledStep {
 };
 struct TiledSchedule {
     std::vector<Rec> recs;
+    std::vector<DRec> drecs;   // derivative plans: parallel to recs (present = 0 where a record has no partials); else empty
     std::vector<TiledStep> steps;
     int peak = 0, n_shift = 0;
     int64_t tile_launches = 0;

@@ -269,7 +269,9 @@ def simulate(sequence, *, adc_time=False, init=None, squeeze=False, probe=None, 
     `ShardedDeviceSignal` whose `.parts` are the per-GPU handles) -- for consumers that reduce or match the dictionary
     on the GPU and never need the 16 GB of a 10^6-voxel MRF signal on the host.  A Jacobian probe (at most three
     variables, one GPU) leaves a `DeviceJacobian`: per ADC the probed state and its derivative rows, `.column(var)` a
-    `DeviceSignal` on one of them.
+    `DeviceSignal` on one of them.  A Jacobian of more than 1024 phase states per voxel raises under mode="auto";
+    mode="resident", written out, runs it on the tiled path (state and derivative windows in HBM, two variables per pass:
+    one GPU, integer 1-D shifts, no X / D, from equilibrium or a start state of at most 1023 orders).
 
     A Hessian probe runs operator by operator under mode="auto" / "stepwise"; mode="resident" runs ONE fused launch per variable
     pair (F0 / Z0 probes, at most 512 orders, one GPU, from equilibrium; NotImplementedError names what it does not take) and with
@@ -334,6 +336,7 @@ def simulate(sequence, *, adc_time=False, init=None, squeeze=False, probe=None, 
         mode = "stepwise"
     from .diff import Hessian
     second = any(isinstance(pb or op, Hessian) for op in sequence if isinstance(op, Probe) for pb in (probes or [op]))
+    asked_resident = mode == "resident"      # (written out, not resolved from "auto": Jacobians above 1024 orders go by it)
     if mode == "auto":      # (Hessian probes: the fused passes are taken on request, mode="resident")
         mode = "resident" if (on_device and not callback and not second) else "stepwise"
     if second and mode == "stream":
@@ -362,7 +365,8 @@ def simulate(sequence, *, adc_time=False, init=None, squeeze=False, probe=None, 
         values, times = _simulate_stepwise(sequence, probes, init, shape, callback, device, options, progress)
     else:
         values, times = _simulate_device(sequence, probes, init, mode, devices, options, exact_partials, fuse, packed, progress,
-                                         to_host=(out != "device"), dtype=dtype, shape=shape, collapse=collapse)
+                                         to_host=(out != "device"), dtype=dtype, shape=shape, collapse=collapse,
+                                         asked_resident=asked_resident)
     if progress is not None:
         progress.close()
     return _pack_values(values, times, asarray=asarray, adc_time=adc_time, stacked_as_is=(out == "device"), dtype=dtype)
@@ -677,10 +681,12 @@ def _jacobian_views(sequence, records, raw, chunk, grid):
 
 
 def _simulate_jacobian(sequence, probes, variables, init, devices, options, exact_partials=False, packed=True, fuse=True,
-                       to_host=True, dtype=np.complex128, shape=None, collapse=True):
+                       to_host=True, dtype=np.complex128, shape=None, collapse=True, tiled=False):
     """derivative passes: the state and up to 3 derivative states per launch (diff.py:119-139);
     the derivative states start from zero (an `init` state matrix carries no partials here).
-    `to_host=False` (simulate(out="device")): one pass on one GPU, the rows stay in HBM -- per probe a DeviceJacobian"""
+    `to_host=False` (simulate(out="device")): one pass on one GPU, the rows stay in HBM -- per probe a DeviceJacobian.
+    `tiled`: the caller wrote mode="resident" out -- above 1024 orders the passes run on the tiled path
+    (_simulate_jacobian_tiled) instead of raising"""
     if not to_host and (len(variables) > _lib.MAX_VARS or init is not None or len(devices) > 1):
         raise NotImplementedError(f'out="device" with Jacobian probes: one pass (at most {_lib.MAX_VARS} variables) on one GPU, from equilibrium')
     ctx0 = init._ctx if init is not None else None
@@ -697,17 +703,47 @@ def _simulate_jacobian(sequence, probes, variables, init, devices, options, exac
                                            kspace0=init._kspace if init is not None else None,
                                            dense_start=init is not None, fuse=fuse, collapse=collapse)
         enc.deriv_flags |= _lib.DERIV_THROUGH_PLAIN_OPS if exact_partials else 0
-        K = enc.capacity(at_least=(init.nstate + 1) if init is not None else 0)
+        try:
+            K = enc.capacity(at_least=(init.nstate + 1) if init is not None else 0)
+        except NotImplementedError:
+            K = None                # above the capacity classes
         state_in = None
         if init is not None:
             work = init.copy()      # never mutate the caller's init (functions.py:149)
             work._broadcast_to(enc.grid)
-            work._reserve(max(K, init._state.K))
-            state_in, K = work._state, work._state.K
-        if K > _lib.MAX_DERIV_K:
-            raise NotImplementedError(
-                f"derivatives with {enc.peak + 1} phase states per voxel: the device path keeps at most "
-                f"{_lib.MAX_DERIV_K}; bound the state matrix with max_nstate=...")
+            if K is not None:
+                work._reserve(max(K, init._state.K))
+                K = work._state.K
+            state_in = work._state
+        if K is None or K > _lib.MAX_DERIV_K:
+            # above 1024 orders the derivative states leave the registers: the tiled path (state and derivative windows in
+            # HBM), taken on request -- mode="resident" written out
+            if not tiled:
+                raise NotImplementedError(
+                    f"derivatives with {enc.peak + 1} phase states per voxel: the in-register path keeps at most "
+                    f"{_lib.MAX_DERIV_K}; bound the state matrix with max_nstate=..., or ask for the tiled path with "
+                    "mode='resident' (one GPU, integer 1-D shifts, no X / D)")
+            if len(chunk) > _lib.TILED_DERIV_V:      # fewer derivative states per pass: 1 + V windows per wavefront
+                per_pass = _lib.TILED_DERIV_V
+                continue
+            why = _tiled_jacobian_refusal(enc, init, devices)
+            if why:
+                raise NotImplementedError(f"derivatives with {enc.peak + 1} phase states per voxel, mode='resident': the tiled "
+                                          f"path does not take {why}; bound the state matrix with max_nstate=...")
+            if not to_host and len(chunk) < len(variables):
+                raise NotImplementedError(f'out="device" with Jacobian probes: one pass -- on the tiled path {_lib.TILED_DERIV_V} variable(s)')
+            first += len(chunk)
+            fleet = _simulate_jacobian_tiled(enc, state_in, devices, ctx0)
+            if not to_host:
+                return _Stacked(_jacobian_handles(sequence, records, fleet.sigs[0], chunk, enc)), _probe_times(sequence)
+            raw = fleet.download(_lib.result_empty(fleet.ctxs[0], (enc.n_adc,) + enc.grid, dtype))
+            fleet.free()
+            if len(variables) == len(chunk):
+                views = _jacobian_views(sequence, records, raw, chunk, enc.grid)
+                if views is not None:
+                    return _Stacked(views), _probe_times(sequence)
+            _collect_jacobian(records, raw, chunk, base, partials)
+            continue
         if len(chunk) > _lib.max_vars(K):      # long state matrices: fewer derivative states per pass (1024 orders: one)
             per_pass = _lib.max_vars(K)
             continue
@@ -736,6 +772,27 @@ def _simulate_jacobian(sequence, probes, variables, init, devices, options, exac
                 return _Stacked(views), _probe_times(sequence)
         _collect_jacobian(records, raw, chunk, base, partials)
     return _finish_jacobian(sequence, records, base, partials)
+
+
+def _tiled_jacobian_refusal(enc, init, devices):
+    """what keeps a derivative plan above 1024 orders off the tiled path (epgx_run_tiled_deriv), or None"""
+    if len(devices) > 1:
+        return "ngpu > 1"
+    if init is not None and init.nstate >= _lib.SUPPORTED_K[-1]:
+        return f"a start state of {init.nstate} orders (at most {_lib.SUPPORTED_K[-1] - 1})"
+    if not enc.tiled_ok(derivatives=True):
+        return "n-D shifts, diffusion or exchange"
+    return None
+
+
+def _simulate_jacobian_tiled(enc, state_in, devices, ctx0=None):
+    """one derivative pass of a state matrix longer than 1024 orders (include/epgx.h epgx_run_tiled_deriv): the state and
+    the derivative states of the plan's variables in HBM windows, one GPU.  Returns the fleet whose signal buffer holds
+    the 1 + V rows per ADC"""
+    Kbuf = enc.tiled_capacity(state_in.K - 1 if state_in is not None else None)
+    fleet = _Fleet(enc, None, devices, ctx0)
+    _lib.run_tiled_deriv(fleet.ctxs[0], fleet.plans[0], 0, enc.nvox, state_in, Kbuf, fleet.sigs[0].ptr.value, enc.nvox, 0)
+    return fleet
 
 
 def _jacobian_handles(sequence, records, buf, chunk, enc):
@@ -788,7 +845,7 @@ def _finish_jacobian(sequence, records, base, partials):
 
 
 def _simulate_device(sequence, probes, init, mode, devices, options, exact_partials=False, fuse=True, packed=True,
-                     progress=None, to_host=True, dtype=np.complex128, shape=None, collapse=True):
+                     progress=None, to_host=True, dtype=np.complex128, shape=None, collapse=True, asked_resident=False):
     from .diff import Hessian
     if any(isinstance(pb or op, Hessian) for op in sequence if isinstance(op, Probe) for pb in (probes or [op])):
         return _simulate_hessian(sequence, probes, init, devices, options, exact_partials, to_host, dtype, shape)
@@ -797,7 +854,7 @@ def _simulate_device(sequence, probes, init, mode, devices, options, exact_parti
         if mode == "stream":
             raise NotImplementedError("derivatives run state-resident (no mode='stream')")
         return _simulate_jacobian(sequence, probes, variables, init, devices, options, exact_partials, packed, fuse, to_host, dtype, shape,
-                                  collapse)
+                                  collapse, tiled=asked_resident and mode == "resident")
     grid0 = init.shape if init is not None else shape
     options = dict(options)
     if init is not None:

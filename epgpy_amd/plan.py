@@ -388,11 +388,17 @@ class Encoder:
             f"({_lib.RESIDENT_ONLY_K} for simulate() of rotations / relaxation / shifts by one from equilibrium); "
             "bound the state matrix with max_nstate=...")
 
-    def tiled_ok(self):
+    def tiled_ok(self, derivatives=False):
         """True if the plan can run on the tiled path (state matrices above the capacity classes, include/epgx.h
-        epgx_run_tiled): integer 1-D shifts, no derivative states, no n-D shifts / diffusion / gathers, no X"""
-        return (self.kspace is None and not self.deferred and not self.variables and self.exchange is None
-                and all(rec[0] not in (_lib.OP_D, _lib.OP_GS, _lib.OP_X) for rec in self.records))
+        epgx_run_tiled): integer 1-D shifts, no derivative states, no n-D shifts / diffusion / gathers, no X.
+        `derivatives=True` asks the same of a first-order derivative plan (epgx_run_tiled_deriv): 1 .. TILED_DERIV_V
+        variables, no second-order pass"""
+        shape_ok = (self.kspace is None and not self.deferred and self.exchange is None
+                    and all(rec[0] not in (_lib.OP_D, _lib.OP_GS, _lib.OP_X) for rec in self.records))
+        if derivatives:
+            return (shape_ok and 0 < len(self.variables) <= _lib.TILED_DERIV_V
+                    and not (self.deriv_flags & _lib.DERIV_SECOND))
+        return shape_ok and not self.variables
 
     def tiled_blocks(self, H=None, W=None, top0=None):
         """the tiled path's schedule at operator level: [(op_begin, op_end, tiles_after)].  A block ends before the shift

@@ -508,6 +508,23 @@ int epgx_run_tiled(epgx_ctx *ctx, const epgx_plan *plan, int64_t vox0, int64_t n
 int epgx_tiled_info(epgx_ctx *ctx, const epgx_plan *plan, int32_t Kbuf, int32_t top0, int32_t *blocks, int32_t *shifts,
                     int64_t *tile_launches, int32_t *peak, char *names, int64_t name_bytes);
 
+/* epgx_run_tiled for a FIRST-ORDER DERIVATIVE plan (n_vars = 1 or 2): Jacobians of state matrices of any length.  The state
+ * and its n_vars derivative states live in HBM as two alternating buffers [nvox][1 + n_vars][3][Kbuf] c128 (the derivative
+ * states start at zero; a start state carries no partials); one wavefront keeps the 1 + n_vars windows of its (voxel, tile)
+ * in registers (tiled_deriv_kernel<8, 32, NSP, n_vars>) and walks the block with the record semantics of epgx_run's
+ * derivative kernels: derivative states carry no equilibrium term, SPOILER acts on them only under
+ * EPGX_DERIV_THROUGH_PLAIN_OPS, RESET and PD-with-reset always clear them.  Blocks, halos and tiles are those of
+ * epgx_run_tiled.  Arguments as for epgx_run_tiled; the signal takes 1 + n_vars rows per ADC (the layout epgx_run writes for a
+ * derivative plan).  Slabs: 8 GiB for the two buffers, (1 + n_vars) times the bytes per voxel.
+ * Errors as for epgx_run_tiled; EPGX_ERR_UNSUPPORTED also for n_vars = 0 or > 2 and for second-order plans (EPGX_DERIV_SECOND). */
+int epgx_run_tiled_deriv(epgx_ctx *ctx, const epgx_plan *plan, int64_t vox0, int64_t nvox, const epgx_state *in, int32_t Kbuf,
+                         void *signal, int64_t signal_ld, int64_t signal_col0, int64_t slab_voxels);
+
+/* epgx_tiled_info for epgx_run_tiled_deriv: the same schedule, names e.g. "tiled_deriv_kernel<8, 32, 1> + tiled_shift" (orders
+ * per lane, halo, derivative states per launch). */
+int epgx_tiled_deriv_info(epgx_ctx *ctx, const epgx_plan *plan, int32_t Kbuf, int32_t top0, int32_t *blocks, int32_t *shifts,
+                          int64_t *tile_launches, int32_t *peak, char *names, int64_t name_bytes);
+
 /* The whole plan, state-resident, over voxels [vox0, vox0 + nvox) in SLABS whose signal columns travel to the host while
  * the next slab computes (second stream + events): what a caller with host buffers waits for is then the PCIe copy
  * alone.
