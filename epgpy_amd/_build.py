@@ -30,6 +30,7 @@ UNITS = [("epgx_api.o", "epgx_api.hip", []), ("epgx_planner.o", "epgx_planner.cp
         [(f"epgx_dfold_v{v}.o", "epgx_dfold.hip", [f"-DEPGX_V={v}"]) for v in (3, 2, 1)] + \
         [(f"epgx_pdfold_v{v}_k{k}.o", "epgx_pdfold.hip", [f"-DEPGX_V={v}", f"-DEPGX_KP={k}"]) for v in (3, 2, 1) for k in (32, 16)] + \
         [(f"epgx_xrun_nc{nc}.o", "epgx_xrun.hip", [f"-DEPGX_NC={nc}"]) for nc in (2, 3, 4)] + \
+        [(f"epgx_dxrun_nc{nc}.o", "epgx_dxrun.hip", [f"-DEPGX_NC={nc}"]) for nc in (2, 3, 4)] + \
         [("epgx_hess.o", "epgx_hess.hip", []), ("epgx_tiled.o", "epgx_tiled.hip", []), ("epgx_chain.o", "epgx_chain.hip", []),
          ("epgx_dft.o", "epgx_dft.hip", []), ("epgx_stats.o", "epgx_stats.hip", []),
          ("epgx_merge.o", "epgx_merge.hip", []), ("epgx_match.o", "epgx_match.hip", []),

@@ -33,6 +33,16 @@ def max_vars(K):
     """derivative states one launch carries at capacity K: 3 up to 512 orders (at 512 the registers of a whole SIMD), 1 at 1024"""
     return MAX_VARS if K <= 512 else 1
 
+
+def max_vars_exchange(ncomp, K):
+    """derivative states one launch carries through an exchange (X) between `ncomp` compartments at capacity K: the state and
+    the derivative states of a compartment group live in the registers of one wavefront (dxrun_kernel<NC, K / 64, V>,
+    NC * (K / 64) * (1 + V) <= 8): 8 // (ncomp * K / 64) - 1, none above 4 compartments"""
+    if not 2 <= int(ncomp) <= 4:
+        return 0
+    return max(0, min(MAX_VARS, 8 // (int(ncomp) * (int(K) // 64)) - 1))
+
+
 OP_NOP, OP_T, OP_MAT, OP_E, OP_S, OP_ADC, OP_SPOIL, OP_RESET, OP_PD, OP_D, OP_GS, OP_MAT0, OP_T0, OP_X = range(14)
 NCOEF = {OP_T: 8, OP_MAT: 10, OP_E: 4, OP_PD: 1, OP_MAT0: 14, OP_T0: 12}   # OP_D: 3*K, OP_GS: 3*K/2 (depend on the capacity), OP_X: 3*N*N
 GS_ZERO, GS_CONJ = -1, 1 << 30

@@ -37,6 +37,7 @@
 #include "epgx_small_kernels.hip.h"
 #include "epgx_exchange_kernels.hip.h"
 #include "epgx_xrun_kernels.hip.h"
+#include "epgx_dxrun_kernels.hip.h"
 #include "epgx_deriv_kernels.hip.h"
 #include "epgx_launch.h"
 #include "epgx_launch_hess.h"
@@ -226,6 +227,7 @@ struct epgx_plan : PlanGeometry {   // ndim, shape, strides, nvox_total, dense_s
     int64_t n_coef = 0;
     int32_t n_adc = 0;
     epgx_op *d_ops = nullptr;   // device copy of `ops` (xrun_kernel walks the primitive list), made on first use
+    epgx_dop *d_dops = nullptr; // device copy of `dops` (dxrun_kernel), made on first use
     // `cache_lock` guards `packed` and the vidx cache (two host threads running ranges of one plan)
     std::mutex cache_lock;
     // cached table indices for one voxel range
@@ -762,6 +764,7 @@ extern "C" int epgx_plan_destroy(epgx_plan *pl) {
     dev_free(pl->ctx, pl->d_coef);
     dev_free(pl->ctx, pl->d_vidx);
     dev_free(pl->ctx, pl->d_ops);
+    dev_free(pl->ctx, pl->d_dops);
     delete pl;
     return EPGX_OK;
 }
@@ -1569,6 +1572,10 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
 hipError_t epgx_launch_xrun_nc2(hipStream_t stream, const epgx::XRunArgs &a, int64_t ngroups, int M);
 hipError_t epgx_launch_xrun_nc3(hipStream_t stream, const epgx::XRunArgs &a, int64_t ngroups, int M);
 hipError_t epgx_launch_xrun_nc4(hipStream_t stream, const epgx::XRunArgs &a, int64_t ngroups, int M);
+// dxrun_kernel launchers (epgx_dxrun.hip, likewise): V = derivative states
+hipError_t epgx_launch_dxrun_nc2(hipStream_t stream, const epgx::DXRunArgs &a, int64_t ngroups, int M, int V);
+hipError_t epgx_launch_dxrun_nc3(hipStream_t stream, const epgx::DXRunArgs &a, int64_t ngroups, int M, int V);
+hipError_t epgx_launch_dxrun_nc4(hipStream_t stream, const epgx::DXRunArgs &a, int64_t ngroups, int M, int V);
 
 // one EPGX_OP_X over the groups of voxels [vox0, vox0 + st->nvox) of the grid, state in place
 static int launch_exchange(epgx_ctx *ctx, const epgx_plan *pl, const epgx_op &op, int64_t vox0, epgx_state *st) {
@@ -1605,12 +1612,81 @@ static int launch_exchange(epgx_ctx *ctx, const epgx_plan *pl, const epgx_op &op
     return EPGX_OK;
 }
 
+// A range that holds EPGX_OP_X in a plan with derivative states: ONE launch of dxrun_kernel<NC, M, V>, state and derivative
+// states in registers, from equilibrium.  There is no split path for derivatives (the per-timestep derivative kernels keep no
+// derivative states in HBM): what the kernel does not cover is EPGX_ERR_UNSUPPORTED.
+static int run_exchange_deriv(epgx_ctx *ctx, epgx_plan *pl, int32_t op_begin, int32_t op_end, int64_t vox0, int64_t nvox,
+                              const epgx_state *in, epgx_state *out, int32_t K, void *signal, int64_t signal_ld, int64_t signal_col0,
+                              char *name_out, int64_t name_bytes) {
+    const int NC = pl->x_ncomp, V = pl->host.n_vars, M = K / 64;
+    static const char *rule = "derivative states through an exchange (EPGX_OP_X) run on dxrun_kernel<N, K / 64, V>: N = 2 .. 4 compartments with "
+                              "N * (K / 64) * (1 + V) <= 8, first order, from equilibrium (in = out = NULL), no D / gather shifts";
+    if (pl->host.second) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: EPGX_DERIV_SECOND: %s", rule);
+    if (in || out) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: a state in HBM: %s", rule);
+    if (!xrun_deriv_fits(NC, K, V)) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: N = %d, K = %d, V = %d: %s", NC, K, V, rule);
+    if (vox0 % pl->x_span || nvox % pl->x_span)
+        return fail(EPGX_ERR_INVALID, "epgx_run: voxel range [%lld,%lld) cuts compartment groups (blocks of %lld voxels)", (long long)vox0,
+                    (long long)(vox0 + nvox), (long long)pl->x_span);
+    bool has_adc = false;
+    for (int i = op_begin; i < op_end; ++i) {
+        const int oc = pl->host.ops[i].opcode;
+        if (oc == EPGX_OP_D || oc == EPGX_OP_GS) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: operator %d (opcode %d): %s", i, oc, rule);
+        has_adc = has_adc || oc == EPGX_OP_ADC;
+    }
+    if (name_out) {
+        snprintf(name_out, (size_t)name_bytes, "dxrun_kernel<%d, %d, %d>", NC, M, V);
+        return EPGX_OK;
+    }
+    if (has_adc && (!signal || signal_col0 < 0 || signal_col0 + nvox > signal_ld))
+        return fail(EPGX_ERR_INVALID, "epgx_run: range contains an ADC but the signal buffer is NULL or too narrow");
+    if (int rc = set_device(ctx)) return rc;
+    if (tracing()) fprintf(stderr, "[epgx] run: dxrun_kernel<%d, %d, %d> -- compartment groups and derivative states in registers\n", NC, M, V);
+    {
+        std::lock_guard<std::mutex> plan_guard(pl->cache_lock);
+        if (!pl->d_ops) {
+            HIP_TRY(dev_alloc(ctx, (void **)&pl->d_ops, sizeof(epgx_op) * pl->host.ops.size()));
+            HIP_TRY(hipMemcpyAsync(pl->d_ops, pl->host.ops.data(), sizeof(epgx_op) * pl->host.ops.size(), hipMemcpyHostToDevice, ctx->stream));
+        }
+        if (!pl->d_dops) {
+            HIP_TRY(dev_alloc(ctx, (void **)&pl->d_dops, sizeof(epgx_dop) * pl->host.dops.size()));
+            HIP_TRY(hipMemcpyAsync(pl->d_dops, pl->host.dops.data(), sizeof(epgx_dop) * pl->host.dops.size(), hipMemcpyHostToDevice, ctx->stream));
+        }
+    }
+    DXRunArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x.ops = pl->d_ops;
+    a.x.op_begin = op_begin;
+    a.x.op_end = op_end;
+    a.x.coef = pl->d_coef;
+    a.x.signal = signal ? (d2 *)signal + signal_col0 : nullptr;
+    a.x.signal_ld = signal_ld;
+    a.x.vox0 = vox0;
+    a.x.stride = pl->x_span / NC;
+    a.x.ndim = pl->ndim;
+    a.x.n_spaces = pl->host.n_spaces;
+    memcpy(a.x.shape, pl->shape, sizeof(a.x.shape));
+    memcpy(a.x.strides, pl->strides, sizeof(a.x.strides));
+    a.dops = pl->d_dops;
+    a.through_plain = (pl->deriv_flags & EPGX_DERIV_THROUGH_PLAIN_OPS) ? 1 : 0;
+    const int64_t ngroups = nvox / NC;
+    if (ngroups > 0x7fffffff) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: more than 2^31 compartment groups in one launch");
+    hipError_t e = hipErrorInvalidValue;
+    switch (NC) {
+    case 2: e = epgx_launch_dxrun_nc2(ctx->stream, a, ngroups, M, V); break;
+    case 3: e = epgx_launch_dxrun_nc3(ctx->stream, a, ngroups, M, V); break;
+    default: e = epgx_launch_dxrun_nc4(ctx->stream, a, ngroups, M, V); break;
+    }
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_run: dxrun_kernel launch failed: %s", hipGetErrorString(e));
+    return EPGX_OK;
+}
+
 // A range that holds EPGX_OP_X: the records between two X run as pieces with the state in HBM (`out`, or a temporary state
 // when out is NULL), each X on exchange_kernel in between.  The voxel range must hold whole compartment groups.
 static int run_exchange_split(epgx_ctx *ctx, epgx_plan *pl, int32_t op_begin, int32_t op_end, int64_t vox0, int64_t nvox,
                               const epgx_state *in, epgx_state *out, int32_t K, void *signal, int64_t signal_ld, int64_t signal_col0,
                               char *name_out, int64_t name_bytes) {
-    if (pl->host.n_vars > 0) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: exchange (EPGX_OP_X) in a plan with derivative states");
+    if (pl->host.n_vars > 0)
+        return run_exchange_deriv(ctx, pl, op_begin, op_end, vox0, nvox, in, out, K, signal, signal_ld, signal_col0, name_out, name_bytes);
     if (!supported_K(K))
         return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: ranges with an exchange (EPGX_OP_X) keep the state in HBM: K = 64 .. 1024, not %d", K);
     if (vox0 % pl->x_span || nvox % pl->x_span)

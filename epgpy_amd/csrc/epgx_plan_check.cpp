@@ -365,7 +365,8 @@ const char *Analysis::check_partial(const epgx_op &op, const epgx_dop &dp, int v
     if (v >= d.n_vars) return "partial for a variable beyond n_vars";
     else if (op.opcode == EPGX_OP_T || op.opcode == EPGX_OP_MAT || op.opcode == EPGX_OP_MAT0 || op.opcode == EPGX_OP_T0) nc = 10;
     else if (op.opcode == EPGX_OP_E) nc = 4;
-    else return "only T / MAT / E operators can carry partial derivatives";
+    else if (op.opcode == EPGX_OP_X) nc = op.ncoef;   // d mT, d mL in the layout of X's own table (3 N^2 per group)
+    else return "only T / MAT / E operators can carry partial derivatives";   // (and X, above)
     const int sp = dp.space[v];
     if (!space_ok(sp)) return "index space of a partial out of range";
     if (op.opcode == EPGX_OP_T0 && off >= d.n_coef) {   // generated next to the table itself (epgx_fuse_partial)
@@ -394,6 +395,16 @@ int Analysis::check_derivatives() {
         if (op.opcode == EPGX_OP_ADC && op.ia + d.n_vars >= d.n_adc)
             return fail(EPGX_ERR_INVALID, "epgx_plan_create: operator %d: ADC rows [%d,%d] exceed n_adc=%d", i,
                         op.ia, op.ia + d.n_vars, d.n_adc);
+        // dxrun_kernel<N, K / 64, V> keeps N K / 64 (1 + V) <= 8 state matrices of 64 orders in registers: at K = 64 already ...
+        if (op.opcode == EPGX_OP_X && !xrun_deriv_fits(op.ia, 64, d.n_vars))
+            return fail(EPGX_ERR_UNSUPPORTED, "epgx_plan_create: operator %d: exchange (EPGX_OP_X) between %d compartments with %d derivative "
+                        "state(s): the fused kernel holds N * (K / 64) * (1 + n_vars) <= 8 with N <= 4 (no split path for derivatives)", i, op.ia, d.n_vars);
+        // ... and the constant term of a generated EPGX_OP_T0 partial (14 per entry) is not read there
+        if (geo.x_span && op.opcode == EPGX_OP_T0)
+            for (int v = 0; v < d.n_vars; ++v)
+                if (host.dops[i].coef_off[v] >= d.n_coef)
+                    return fail(EPGX_ERR_UNSUPPORTED, "epgx_plan_create: operator %d: a generated partial (epgx_fuse_partial) in a plan with exchange "
+                                "(EPGX_OP_X): keep the relaxations stages of their own", i);
     }
     return EPGX_OK;
 }
@@ -557,7 +568,7 @@ int Analysis::partial_patterns() {
     for (int i = 0; i < d.n_ops; ++i)
         for (int v = 0; v < d.n_vars; ++v) {
             const int64_t off = host.dops[i].coef_off[v];
-            if (off < 0) continue;
+            if (off < 0 || host.ops[i].opcode == EPGX_OP_X) continue;   // (X: no zero pattern is used)
             if (off >= d.n_coef && host.ops[i].opcode == EPGX_OP_T0) {   // a generated partial (checked above): pattern known from its sources
                 const auto g = generated_dpattern.find(off);
                 if (g == generated_dpattern.end())

@@ -39,6 +39,13 @@ struct PlanGeometry {
     }
 };
 
+// exchange with derivative states: dxrun_kernel<N, K / 64, V> holds the state and V derivative states of the N compartments of
+// a group in registers -- N (K / 64) (1 + V) <= 8 state matrices of 64 orders, N = 2 .. 4.  There is no split path for
+// derivatives, so what does not fit is refused (plan analysis at K = 64, epgx_run at the capacity it is asked for)
+inline bool xrun_deriv_fits(int ncomp, int K, int n_vars) {
+    return ncomp >= 2 && ncomp <= 4 && n_vars >= 1 && K >= 64 && K % 64 == 0 && ncomp * (K / 64) * (1 + n_vars) <= 8;
+}
+
 // rounding residues to clear in the device copy of a table (snap_kernel): bit c of mask = column c of every entry
 struct Snap { int64_t off, entries; int nc; uint32_t mask; };
 // one table of logarithmic partials to generate (logtab_kernel): PlanHost::logtabs[j] is written from log_jobs[j]

@@ -214,6 +214,10 @@ def compile_sequence(sequence, probes=None, *, shape=None, options=None, nstate0
     if hessian is not None:
         enc.hessian = tuple(hessian)
         enc.deriv_flags |= _lib.DERIV_SECOND | _lib.PLAN_NO_FOLD
+    if variables and has_exchange(sequence):
+        # derivative states through X (dxrun_kernel walks the primitive operators): every relaxation stays a stage of its own,
+        # with its own partial -- no host-side E.T.E tables (their generated partials are not read there), no run-time fold
+        fuse = False
     if not fuse:     # operator-by-operator arithmetic: no host-side E.T.E tables, no run-time fold in the library either
         enc.deriv_flags |= _lib.PLAN_NO_FOLD
     records, bounds = [], []
@@ -322,7 +326,7 @@ def simulate(sequence, *, adc_time=False, init=None, squeeze=False, probe=None, 
         options = {**init.options, **options}
 
     if has_exchange(sequence):
-        _check_exchange(sequence, probes, init, out, devices)
+        _check_exchange(sequence, probes, init, out, devices, mode, callback)
     float_shift = has_float_shift(sequence, init)
     if float_shift:
         _check_float_shift(sequence, probes, {**(init.options if init is not None else {}), **options})
@@ -402,18 +406,40 @@ def _check_float_shift(sequence, probes, options):
         raise NotImplementedError("X (exchange) in a sequence with float shifts (shift-merge)")
 
 
-def _check_exchange(sequence, probes, init, out, devices):
-    """what simulate() does not carry through an exchange (X) yet: NotImplementedError that names X"""
+def exchange_derivatives(sequence, probes=()):
+    """True if a (flat) sequence with X asks for derivative states: a Jacobian probe, or an operator with order1"""
+    from .diff import Jacobian
+    return (any(isinstance(pb, Jacobian) for pb in list(probes) + list(sequence))
+            or any(getattr(part, "order1", None) for op in sequence for part in op._parts()))
+
+
+def _check_exchange(sequence, probes, init, out, devices, mode=None, callback=None):
+    """what simulate() does not carry through an exchange (X): NotImplementedError that names X.  First-order derivatives
+    (Jacobian probes, order1) run on the fused kernel dxrun_kernel: state-resident from equilibrium, on one GPU, to the host"""
     from .diff import Jacobian, Hessian
-    if any(isinstance(pb, (Jacobian, Hessian)) for pb in probes) or any(
-            getattr(part, "order1", None) or getattr(part, "order2", None) for op in sequence for part in op._parts()):
-        raise NotImplementedError("X (exchange) has no derivatives: no Jacobian / Hessian / order1 in a sequence with X")
+    everything = list(probes) + list(sequence)
+    if any(isinstance(pb, Hessian) for pb in everything) or any(
+            getattr(part, "order2", None) for op in sequence for part in op._parts()):
+        raise NotImplementedError("X (exchange) has first-order derivatives only: no Hessian / order2 in a sequence with X")
     if out == "device":
         raise NotImplementedError('X (exchange): out="device" is not supported')
     if len(devices) > 1:
         raise NotImplementedError("X (exchange) runs on one GPU (no ngpu > 1)")
     if init is not None and getattr(init, "_eq", None) is not None:
         raise NotImplementedError("X (exchange) with a general equilibrium: only [0, 0, density] is supported")
+    if not exchange_derivatives(sequence, probes):
+        return
+    known = {var for op in sequence for part in op._parts() for var in (getattr(part, "order1", None) or {})}
+    for pb in everything:
+        unknown = [var for var in pb._device_variables() if var not in known] if isinstance(pb, Jacobian) else []
+        if unknown:
+            raise NotImplementedError(f"X (exchange): Jacobian variable(s) {unknown} that no operator of the sequence declares (order1=)")
+    if init is not None:
+        raise NotImplementedError("X (exchange) with derivative states starts from equilibrium: no init= (the fused kernel "
+                                  "keeps the state and its derivative states in registers)")
+    if callback is not None or mode not in (None, "auto", "resident"):
+        raise NotImplementedError(f"X (exchange) with derivative states runs in one fused launch (mode='auto' / 'resident'): no "
+                                  f"mode={mode!r}, no callback, no operator-by-operator path")
 
 
 def _pack_values(values, times, *, asarray=True, adc_time=False, stacked_as_is=False, dtype=None):
@@ -695,6 +721,7 @@ def _simulate_jacobian(sequence, probes, variables, init, devices, options, exac
         options.setdefault("kvalue", init.kvalue)
     base, partials = {}, {}      # (probe index in the sequence, probe index) -> arrays
     first, per_pass = 0, _lib.MAX_VARS
+    finish_rows = False      # X plans: weights / reduce of the sequence's Adc act on every row of a Jacobian (the compartment sum)
     while first < len(variables):
         chunk = variables[first:first + per_pass]
         enc, records, _ = compile_sequence(sequence, probes, options=options, variables=chunk,
@@ -715,6 +742,33 @@ def _simulate_jacobian(sequence, probes, variables, init, devices, options, exac
                 work._reserve(max(K, init._state.K))
                 K = work._state.K
             state_in = work._state
+        if enc.exchange is not None:
+            # X: state and derivative states of a compartment group in the registers of ONE wavefront (dxrun_kernel)
+            ncomp, K_x = enc.exchange[1], (K if K is not None else (enc.peak + 64) // 64 * 64)
+            fit = _lib.max_vars_exchange(ncomp, K_x)
+            if fit == 0:
+                raise NotImplementedError(
+                    f"X (exchange) with derivative states: {ncomp} compartments at {enc.peak + 1} phase states per voxel ({K_x} orders) "
+                    f"leave room for 8 // (N * orders / 64) - 1 = 0 derivative states (at most 4 compartments; N * orders / 64 * "
+                    "(1 + variables) <= 8); bound the state matrix with max_nstate=...")
+            if any(rec[0] in (_lib.OP_D, _lib.OP_GS) for rec in enc.records) or enc.deferred or enc.kspace is not None:
+                raise NotImplementedError("X (exchange) with derivative states: no diffusion (D) or n-D shifts in the sequence")
+            if len(chunk) > fit:
+                per_pass = fit
+                continue
+            first += len(chunk)
+            fleet = _Fleet(enc, K, devices, ctx0)
+            raw = _lib.result_empty(fleet.ctxs[0], (enc.n_adc,) + enc.grid, dtype)
+            fleet.run(K, None)
+            fleet.download(raw)
+            fleet.free()
+            if len(variables) == len(chunk):
+                views = _jacobian_views(sequence, records, raw, chunk, enc.grid)
+                if views is not None:
+                    return _Stacked(views), _probe_times(sequence)
+            _collect_jacobian(records, raw, chunk, base, partials)
+            finish_rows = True
+            continue
         if K is None or K > _lib.MAX_DERIV_K:
             # above 1024 orders the derivative states leave the registers: the tiled path (state and derivative windows in
             # HBM), taken on request -- mode="resident" written out
@@ -771,7 +825,7 @@ def _simulate_jacobian(sequence, probes, variables, init, devices, options, exac
             if views is not None:
                 return _Stacked(views), _probe_times(sequence)
         _collect_jacobian(records, raw, chunk, base, partials)
-    return _finish_jacobian(sequence, records, base, partials)
+    return _finish_jacobian(sequence, records, base, partials, finish_rows)
 
 
 def _tiled_jacobian_refusal(enc, init, devices):
@@ -829,13 +883,19 @@ def _collect_jacobian(records, raw, chunk, base, partials):
             partials.setdefault((i, j), {}).update({var: raw[slot + 1 + v] for v, var in enumerate(chunk)})
 
 
-def _finish_jacobian(sequence, records, base, partials):
+def _finish_jacobian(sequence, records, base, partials, finish_rows=False):
+    """`finish_rows` (plans with X): the weights / reduce of the sequence's own Adc are applied to the state row and to every
+    derivative row before a Jacobian probe assembles them -- they are linear, and the sum over the compartment axis is what
+    an exchange experiment measures.  Other derivative plans hand a Jacobian the rows as they are (the reference's way)"""
     values, i = [], 0
     for op in sequence:
         if isinstance(op, Probe):
             row = []
             for j, (pb, _) in enumerate(records[i][1]):
-                if hasattr(pb, "_assemble"):
+                if hasattr(pb, "_assemble") and finish_rows and pb is not op and hasattr(op, "_finish"):
+                    row.append(op.post(pb._assemble(np.asarray(op._finish(base[i, j])),
+                                                    {var: np.asarray(op._finish(arr)) for var, arr in partials[i, j].items()})))
+                elif hasattr(pb, "_assemble"):
                     row.append(op.post(pb._assemble(base[i, j], partials[i, j])))
                 else:
                     row.append(op.post(np.array(pb._finish(base[i, j]))))

@@ -111,7 +111,18 @@ enum epgx_opcode {
                           (or with EPGX_XRUN=0 in the environment) as pieces: the records between two X on the per-timestep
                           kernels with the state in HBM (a temporary state from equilibrium when `in` is NULL),
                           exchange_kernel in between.  epgx_kernel_for names the first "xrun_kernel<2, 2, false>" (etc.),
-                          the second "split<exchange_kernel>".  Voxel ranges must hold whole groups. */
+                          the second "split<exchange_kernel>".  Voxel ranges must hold whole groups.
+                          With derivative states (n_vars > 0) X is a DIFFERENTIABLE operator, not a plain one: it always acts on
+                          the derivative states, independent of EPGX_DERIV_THROUGH_PLAIN_OPS, and may carry partials (epgx_dop).
+                          At every order k, the partial terms reading the state BEFORE its update:
+                            dA_v,c <- sum_c' mT[c][c'] dA_v,c'       + sum_c' dmT_v[c][c'] A_c'
+                            dB_v,c <- sum_c' conj(mT[c][c']) dB_v,c' + sum_c' conj(dmT_v[c][c']) B_c'
+                            dZ_v,c <- sum_c' mL[c][c'] dZ_v,c'       + sum_c' dmL_v[c][c'] (Z_c' - d_k0 rho_c')
+                          (no equilibrium term in the derivative states; the densities depend on no variable).  Such a range runs in
+                          ONE launch of dxrun_kernel<NC, M, V> (V = n_vars): NC = 2 .. 4 with NC M (1 + V) <= 8, state-resident
+                          from equilibrium (in = out = NULL), no D / gather shifts, first order; everything else is
+                          EPGX_ERR_UNSUPPORTED -- there is no split path for derivatives.  A plan that holds X and variables keeps
+                          every relaxation a stage of its own: a generated EPGX_OP_T0 partial (epgx_fuse_partial) is refused. */
     EPGX_OP__COUNT
 };
 
@@ -128,7 +139,8 @@ typedef struct epgx_op {
 /* First-order partial derivatives of operator i w.r.t. up to EPGX_MAX_VARS variables
  * (DiffOperator order1, epgpy/diff.py:264-288).  coef_off[v] < 0: operator i does not depend on
  * variable v.  Table entry: EPGX_OP_T / MAT / MAT0 -> the 10 coefficients of EPGX_OP_MAT for
- * d(mat)/dv;  EPGX_OP_E -> 4 coefficients (Re/Im d e0, d e2, d r0) for d(arr, arr0)/dv; already
+ * d(mat)/dv;  EPGX_OP_E -> 4 coefficients (Re/Im d e0, d e2, d r0) for d(arr, arr0)/dv;  EPGX_OP_X -> a table in the
+ * layout of X's own, one entry per compartment group of 3 N^2 doubles (Re/Im of d mT / dv row-major, then d mL / dv, real); already
  * combined over the operator's parameters (sum_p coeff[v][p] * dOp/dp).  An EPGX_OP_T0 whose table the library
  * generated (epgx_fuse) takes its partials from tables the library generates as well (epgx_fuse_partial: coef_off in
  * the generated part of the pool, 14 per entry -- the 10 of d(mat)/dv, then Re/Im d o0, d o2, pad).  A partial table may
