@@ -80,7 +80,7 @@ const Knobs &knobs() {
                             env_int("EPGX_GROW_MIN", 1),    env_int("EPGX_FOLD", 1) != 0,
                             getenv("EPGX_GROW_SHARE") ? atof(getenv("EPGX_GROW_SHARE")) : 0.1, env_int("EPGX_LEAD_FORWARD", 1) != 0,
                             env_int("EPGX_SLAB_VOXELS", 0), env_int("EPGX_SPLIT_GROW", 1) != 0, env_int("EPGX_XRUN", 1) != 0,
-                            env_int("EPGX_REACH", 1) != 0,  env_int("EPGX_CGROW", 1)};
+                            env_int("EPGX_REACH", 1) != 0,  env_int("EPGX_CGROW", 1),           env_int("EPGX_LANES", 1)};
     return k;
 }
 
@@ -1987,12 +1987,8 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
         if (tracing())
             fprintf(stderr, "[epgx] run: %d records: [0, %d) at %d orders per voxel, [%d, %d) at %d, the rest at %d\n", rl.n_grow, rl.grow1,
                     rl.grow_cap[0], rl.grow1, rl.grow2, rl.grow_cap[1], rl.grow_cap[2]);
-        switch (pl->host.n_spaces) {
-        case 0: e = epgx_launch_rows_grow_nsp0(ctx->stream, a, rl.grow1, rl.grow2, rl.grow_cap); break;
-        case 1: e = epgx_launch_rows_grow_nsp1(ctx->stream, a, rl.grow1, rl.grow2, rl.grow_cap); break;
-        case 2: e = epgx_launch_rows_grow_nsp2(ctx->stream, a, rl.grow1, rl.grow2, rl.grow_cap); break;
-        default: e = epgx_launch_rows_grow_nsp4(ctx->stream, a, rl.grow1, rl.grow2, rl.grow_cap); break;
-        }
+        // (rows layout or one voxel per lane: epgx_launch_grow.h)
+        e = epgx_launch_rows_grow(ctx->stream, a, pl->host.n_spaces, rl.grow, rl.grow1, rl.grow2, rl.grow_cap, knobs());
         break;
     case FAM_ROWS:
         switch (K / 16) {

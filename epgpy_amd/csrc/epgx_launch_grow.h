@@ -1,7 +1,50 @@
 // epgx_launch_grow.h -- launchers of the growing long-state-matrix kernels (epgx_cgrow.hip); included by epgx_api.hip and the
 // units that define them only, so that work on these kernels does not rebuild every translation unit.  Not part of the public ABI.
 #pragma once
+#include <cstdio>
+#include <vector>
+
 #include "epgx_launch.h"
+#include "epgx_planner.h"
+
+// The growing launch at K = 64 (FAM_ROWS_GROW) has two variants: the rows layout (rows_grow_kernel, epgx_grow.hip: four voxels
+// per wave) and one voxel per lane (rows_grow_lanes_kernel, epgx_grow_lanes.hip) for lists that lanes_plan accepts and launches
+// big enough to fill the chip with waves of 64 voxels.  choose_kernel does not know of the second: it names the family, the
+// launcher picks the variant from the list, the knob EPGX_LANES and the number of voxels.
+hipError_t epgx_launch_rows_grow_lanes_nsp0(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L);
+hipError_t epgx_launch_rows_grow_lanes_nsp1(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L);
+hipError_t epgx_launch_rows_grow_lanes_nsp2(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L);
+hipError_t epgx_launch_rows_grow_lanes_nsp4(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L);
+int epgx_lanes_deck();   // orders of a lane that live in VGPRs (EPGX_LANES_DECK); the rest, up to L, in LDS
+inline size_t epgx_lanes_lds_bytes(int L, int deck) { return L > deck ? (size_t)48 * 64 * (size_t)(L - deck) : 0; }
+// `grow`: the host copy of the list `a.recs` holds; n1, n2, cap: the ranges of the rows variant
+inline hipError_t epgx_launch_rows_grow(hipStream_t stream, const epgx::RunArgs &a, int n_spaces, const std::vector<epgx::Rec> &grow, int n1, int n2,
+                                        const int cap[3], const epgx::Knobs &kn) {
+    const epgx::LanesPlan lp = epgx::lanes_plan(grow, a.in != nullptr, a.out != nullptr, kn);
+    const bool lanes = epgx::lanes_selected(lp, a.nvox, kn);
+    if (epgx::tracing()) {
+        if (lanes)
+            fprintf(stderr, "[epgx] run: variant lanes (one voxel per lane): L = %d, %zu bytes of LDS per wave, %d shifts before the last probe\n", lp.L,
+                    epgx_lanes_lds_bytes(lp.L, epgx_lanes_deck()), lp.rem0);
+        else
+            fprintf(stderr, "[epgx] run: variant rows (four voxels per wave): %s\n",
+                    lp.eligible ? "fewer voxels than the one-voxel-per-lane variant is taken for" : lp.why);
+    }
+    if (lanes) {
+        switch (n_spaces) {
+        case 0: return epgx_launch_rows_grow_lanes_nsp0(stream, a, lp.rem0, lp.L);
+        case 1: return epgx_launch_rows_grow_lanes_nsp1(stream, a, lp.rem0, lp.L);
+        case 2: return epgx_launch_rows_grow_lanes_nsp2(stream, a, lp.rem0, lp.L);
+        default: return epgx_launch_rows_grow_lanes_nsp4(stream, a, lp.rem0, lp.L);
+        }
+    }
+    switch (n_spaces) {
+    case 0: return epgx_launch_rows_grow_nsp0(stream, a, n1, n2, cap);
+    case 1: return epgx_launch_rows_grow_nsp1(stream, a, n1, n2, cap);
+    case 2: return epgx_launch_rows_grow_nsp2(stream, a, n1, n2, cap);
+    default: return epgx_launch_rows_grow_nsp4(stream, a, n1, n2, cap);
+    }
+}
 
 // K = 128 / 256 / 512 / 1024 FROM EQUILIBRIUM while the state matrix grows: the contiguous layout walked in phases of 1, 2, 4, 8, 16
 // orders per lane (epgx_cgrow.hip, one translation unit per capacity): records [0, g[0]) while at most 64 orders can hold

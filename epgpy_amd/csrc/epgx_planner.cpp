@@ -361,6 +361,64 @@ void grow_reach(const std::vector<Rec> &list, int n1, int n2, int cap[3]) {
     for (int p = 0; p < 3; ++p) cap[p] = !probed ? today[p] : std::min(today[p], need[p] <= 16 ? 16 : (need[p] <= 32 ? 32 : 64));
 }
 
+// see epgx_planner.h.  `top` and `rem` are counted exactly as the kernel counts them (every S(+1) of a record, leading or
+// trailing; resets and truncations cannot occur), so L is the largest window the kernel will ever open.
+LanesPlan lanes_plan(const std::vector<Rec> &grow, bool has_in, bool has_out, const Knobs &kn) {
+    LanesPlan lp;
+    auto refuse = [&](const char *why) {
+        lp.eligible = false;
+        lp.why = why;
+        return lp;
+    };
+    if (kn.lanes <= 0) return refuse("EPGX_LANES=0");
+    if (has_in || has_out) return refuse("a state input or output");
+    if (grow.empty()) return refuse("no growing record list");
+    struct Exec { int d, rep; bool adc; };
+    std::vector<Exec> ex;
+    size_t members = 0;
+    for (const Rec &r : grow) {
+        const uint32_t f = r.flags, head = f >> 24;
+        const int count = (int)((uint32_t)r.kmax >> 16);
+        if (!members && (head == LEAF_PAIR || head == LEAF_SINGLE)) {   // (a header's low flag bits are a shape code, not flags)
+            members = (size_t)(head == LEAF_PAIR ? 2 : 1) * (size_t)count;
+            continue;
+        }
+        const int rep = members ? 1 : std::max(count, 1);
+        if (members) --members;
+        if (f & F_TRUNC) return refuse("a truncation below the capacity");
+        if (f & (F_SPOIL | F_FOLD_SPOIL)) return refuse("a spoiler");
+        if (f & F_RESET) return refuse("a reset");
+        if (f & (F_PD | F_PD_RESET)) return refuse("a density stage");
+        if (f & F_GS) return refuse("an n-D shift");
+        if (f & F_D) return refuse("diffusion");
+        if (f & (F_MAT | F_MAT0)) return refuse("a general matrix");
+        if (f & F_ADC_Z) return refuse("a Z0 probe");
+        if ((f & F_S) && !(f & F_FOLD) && r.shift != 1) return refuse(r.shift == -1 ? "S(-1)" : "a shift by more than one order");
+        if ((f & F_T0) && !(f & F_T)) return refuse("a constant term without a rotation");
+        ex.push_back({((f & F_S0) ? 1 : 0) + ((f & F_S) ? 1 : 0), rep, (f & F_ADC) != 0});
+    }
+    // the shifts up to the last probe (a record shifts before it probes), then shift by shift: between two shifts the state
+    // holds 1 + min(top, rem) live orders
+    size_t last = ex.size();
+    for (size_t q = 0; q < ex.size(); ++q)
+        if (ex[q].adc) last = q;
+    if (last == ex.size()) return refuse("no probe");
+    long rem = 0;
+    for (size_t q = 0; q <= last; ++q) rem += (long)ex[q].d * ex[q].rep;
+    lp.rem0 = (int)std::min<long>(rem, 1 << 30);
+    long top = 0, need = 1;
+    for (size_t q = 0; q <= last; ++q)
+        for (long s = (long)ex[q].d * ex[q].rep; s > 0; --s) {
+            ++top;
+            --rem;
+            need = std::max(need, 1 + std::min(top, rem));
+        }
+    lp.L = (int)std::min<long>(need, 1 << 30);
+    if (need > LANES_MAX_ORDERS) return refuse("more than 24 live orders");
+    lp.eligible = true;
+    return lp;
+}
+
 // what a launch needs to know about the packed records of a range
 static void range_facts(RangeLists &pr) {
     const std::vector<Rec> &recs = pr.recs;

@@ -31,6 +31,7 @@ struct Knobs {
     bool xrun;      // EPGX_XRUN (default 1): ranges with exchange (EPGX_OP_X) on xrun_kernel where it covers them; 0: always the split path
     bool reach;     // EPGX_REACH (default 1): a range of rows_grow_kernel runs at the orders that can still reach a probe (grow_reach); 0: at 16 / 32 / 64
     int cgrow;      // EPGX_CGROW: 0 off, 1 (default): growing launches at K = 256 .. 1024, at K = 128 when 60 % of the records run below 64 orders; 2: at K = 128 whenever the other capacities would
+    int lanes;      // EPGX_LANES: the one-voxel-per-lane variant of a FAM_ROWS_GROW launch (lanes_plan) -- 0 never, 1 from LANES_MIN_VOXELS voxels on, 2 whenever the list is eligible (tests)
 };
 // EPGX_TRACE is read per call (tests switch it on and off)
 inline bool tracing() { return getenv("EPGX_TRACE") != nullptr; }
@@ -113,6 +114,30 @@ void pack_records(const PlanHost &ph, int begin, int end, int K, const Knobs &kn
                   bool &use_lds, bool &has_adc, std::vector<ELog> &elog);
 void grow_split(const std::vector<Rec> &runs, std::vector<Rec> &out, int &n1, int &n2, double work[3]);
 void grow_reach(const std::vector<Rec> &list, int n1, int n2, int cap[3]);
+
+// The one-voxel-per-lane variant of a FAM_ROWS_GROW launch (rows_grow_lanes_kernel, epgx_grow_lanes_kernels.hip.h): whether the
+// cut list `grow` can run there, and what the launch needs.  A pure function of the list and the knob.
+//   eligible  the launch starts from equilibrium and writes no state; every record is made of rotation / relaxation / S(+1)
+//             leading or trailing / F0 probe stages (members of pair and folded runs included); no truncation, no S(-1) or
+//             shift by |n| >= 2, no gather shift, no diffusion, no spoiler (folded ones included), no reset, no density stage,
+//             no general matrix, no Z0 probe; the list has a probe; L <= LANES_MAX_ORDERS
+//   L         the largest number of live orders between two shifts: 1 + min(top, rem), top = the shifts so far (grow_split's
+//             highest populated order), rem = the shifts left up to the last probe -- grow_reach's rule shift by shift
+//             instead of record by record, without the rounding to 16 / 32 / 64.  An n-echo train (two shifts each): n + 1
+//   rem0      the shifts of the whole list up to its last probe (what the kernel starts `rem` from)
+//   why       "" or the first reason the list was refused for
+constexpr int LANES_MAX_ORDERS = 24;
+constexpr int64_t LANES_MIN_VOXELS = 1 << 19;   // EPGX_LANES=1: the variant from this many voxels on (the crossover)
+struct LanesPlan {
+    bool eligible = false;
+    int L = 0, rem0 = 0;
+    const char *why = "";
+};
+LanesPlan lanes_plan(const std::vector<Rec> &grow, bool has_in, bool has_out, const Knobs &kn);
+// the launcher's choice: the knob, the list and the size of the launch
+inline bool lanes_selected(const LanesPlan &lp, int64_t nvox, const Knobs &kn) {
+    return lp.eligible && (kn.lanes >= 2 || (kn.lanes == 1 && nvox >= LANES_MIN_VOXELS));
+}
 
 // pack_records, then in this order: run folding, the phases of rows_grow_kernel, the phases of run_contig_grow_kernel, the runs of
 // derivative plans
