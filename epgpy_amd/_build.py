@@ -35,7 +35,9 @@ UNITS = [("epgx_api.o", "epgx_api.hip", []), ("epgx_planner.o", "epgx_planner.cp
         [("epgx_hess.o", "epgx_hess.hip", []), ("epgx_tiled.o", "epgx_tiled.hip", []), ("epgx_chain.o", "epgx_chain.hip", []),
          ("epgx_dft.o", "epgx_dft.hip", []), ("epgx_stats.o", "epgx_stats.hip", []),
          ("epgx_merge.o", "epgx_merge.hip", []), ("epgx_match.o", "epgx_match.hip", []),
-         ("epgx_compress.o", "epgx_compress.hip", []), ("epgx_match32.o", "epgx_match32.hip", [])]
+         ("epgx_compress.o", "epgx_compress.hip", []), ("epgx_match32.o", "epgx_match32.hip", []),
+         # (the per-voxel shift restates NumPy arithmetic operation by operation: no fused multiply-add anywhere in the unit)
+         ("epgx_prune.o", "epgx_prune.hip", ["-ffp-contract=off"])]
 ARCH = "gfx950"
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
          # every branch of run_kernel is wave-uniform (scalar compares on record flags); without this

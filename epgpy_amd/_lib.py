@@ -157,6 +157,14 @@ SYMBOLS = {
     "epgx_state_dft": (_i, [_p, _p, _i64, _i64, _i32, _p, _p, _i32, _p, _i64, _d, _d, _p]),
     "epgx_state_row_stats": (_i, [_p, _p, _i32, _p, _p]),
     "epgx_state_merge": (_i, [_p, _p, _p, _i32, _p, _p]),
+    "epgx_coords_create": (_i, [_p, _i64, _i32, c_void_pp]),
+    "epgx_coords_destroy": (_i, [_p]),
+    "epgx_coords_info": (_i, [_p, ctypes.POINTER(_i64), ctypes.POINTER(_i32)]),
+    "epgx_coords_upload": (_i, [_p, _p, _p, _i64]),
+    "epgx_coords_download": (_i, [_p, _p, _p]),
+    "epgx_coords_widen": (_i, [_p, _p]),
+    "epgx_state_prune_shift": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p, _p, _i32, _i32, _d, ctypes.POINTER(_i32)]),
+    "epgx_state_prune_read": (_i, [_p, _p, _p, _d, _p]),
     "epgx_run": (_i, [_p, _p, _i32, _i32, _i64, _i64, _p, _p, _i32, _p, _i64, _i64]),
     "epgx_kernel_for": (_i, [_p, _p, _i32, _i32, _i32, _p, _p, ctypes.c_char_p, _i64]),
     "epgx_run_tiled": (_i, [_p, _p, _i64, _i64, _p, _i32, _p, _i64, _i64, _i64]),
@@ -931,6 +939,77 @@ def state_merge(ctx, dst, src, nrow_dst, offsets, sources):
         raise NotImplementedError(f"{ctx.lib.epgx_last_error().decode(errors='replace')}: a coarser `kgrid` or a larger `prune` "
                                   "tolerance keeps the state matrix under the limit")
     check(rc, "epgx_state_merge")
+
+
+PRUNE_K = 64                                              # stored orders of a voxel through the per-voxel shift (epgx_prune.h)
+PRUNE_MAX_DIMS = 8                                        # grid axes of its shift table
+
+
+class DeviceCoords:
+    """epgx_coords handle: per-voxel coordinates [nvox][kdim][64] float64 + live stored rows [nvox] int32 in HBM"""
+
+    def __init__(self, ctx, nvox, kdim):
+        self.ctx, self.nvox, self.kdim = ctx, int(nvox), int(kdim)
+        handle = ctypes.c_void_p()
+        check(ctx.lib.epgx_coords_create(ctx.handle, self.nvox, self.kdim, ctypes.byref(handle)), "epgx_coords_create")
+        self.handle = handle
+
+    def upload(self, k, nlive):
+        """k [nsrc, kdim, 64], nlive [nsrc]; nsrc = nvox, or 1: one set for every voxel (repeated on the device)"""
+        k = np.ascontiguousarray(k, dtype=np.float64)
+        nlive = np.ascontiguousarray(nlive, dtype=np.int32).reshape(-1)
+        if k.ndim != 3 or k.shape[1:] != (self.kdim, PRUNE_K) or k.shape[0] != nlive.size:
+            raise ValueError(f"coords upload: k {k.shape}, nlive {nlive.shape} for kdim={self.kdim}")
+        check(self.ctx.lib.epgx_coords_upload(self.handle, k.ctypes.data, nlive.ctypes.data, k.shape[0]), "epgx_coords_upload")
+
+    def download(self):
+        k = np.empty((self.nvox, self.kdim, PRUNE_K), dtype=np.float64)
+        nlive = np.empty(self.nvox, dtype=np.int32)
+        check(self.ctx.lib.epgx_coords_download(self.handle, k.ctypes.data, nlive.ctypes.data), "epgx_coords_download")
+        return k, nlive
+
+    def widen(self, kdim):
+        """the same coordinates with further zero columns"""
+        new = DeviceCoords(self.ctx, self.nvox, kdim)
+        check(self.ctx.lib.epgx_coords_widen(new.handle, self.handle), "epgx_coords_widen")
+        return new
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None) and _alive() and self.ctx.handle:
+                self.ctx.lib.epgx_coords_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+def state_prune_shift(ctx, dst, cdst, src, csrc, table, shape, sstride, ktvalue, grid, nmax, prune, tol):
+    """epgx_state_prune_shift: the per-voxel float shift of (src, csrc) into (dst, cdst); table [ntable, kdim] (wavenumbers),
+    shape / sstride: the grid and the table's stride along each axis.  Returns the largest live count of a voxel.  A voxel that
+    keeps more than PRUNE_K stored orders: NotImplementedError (the sources are untouched)"""
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    shape = np.ascontiguousarray(shape, dtype=np.int64)
+    sstride = np.ascontiguousarray(sstride, dtype=np.int64)
+    ktvalue = np.ascontiguousarray(ktvalue, dtype=np.float64)
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    if table.ndim != 2 or table.shape[1] != csrc.kdim or shape.shape != sstride.shape or ktvalue.size != csrc.kdim or grid.size != csrc.kdim:
+        raise ValueError(f"state_prune_shift: table {table.shape}, ktvalue {ktvalue.shape}, grid {grid.shape} for kdim={csrc.kdim}")
+    out = ctypes.c_int32(0)
+    rc = ctx.lib.epgx_state_prune_shift(ctx.handle, dst.handle, cdst.handle, src.handle, csrc.handle, table.ctypes.data, table.shape[0],
+                                        shape.size, shape.ctypes.data, sstride.ctypes.data, ktvalue.ctypes.data, grid.ctypes.data,
+                                        -1 if nmax is None else int(nmax), 1 if prune else 0, float(tol), ctypes.byref(out))
+    if rc == ERR_UNSUPPORTED:
+        raise NotImplementedError(f"{ctx.lib.epgx_last_error().decode(errors='replace')}: a coarser `kgrid`, a `max_nstate` or a larger "
+                                  "`prune` tolerance keeps every voxel under the limit")
+    check(rc, "epgx_state_prune_shift")
+    return int(out.value)
+
+
+def state_prune_read(ctx, state, coords, tvalue, out_ptr):
+    """epgx_state_prune_read: F0 with a time coordinate and per-voxel coordinates into the device memory at `out_ptr`
+    ([nvox] complex128)"""
+    check(ctx.lib.epgx_state_prune_read(ctx.handle, state.handle, coords.handle, float(tvalue), ctypes.c_void_p(out_ptr)),
+          "epgx_state_prune_read")
 
 
 def kernel_for(ctx, plan, K, op_begin=0, op_end=None, state_in=None, state_out=None):

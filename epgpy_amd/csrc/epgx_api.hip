@@ -50,6 +50,7 @@
 #include "epgx_match32.h"
 #include "epgx_compress.h"
 #include "epgx_merge.h"
+#include "epgx_prune.h"
 #include "epgx_launch_grow.h"
 #include "epgx_launch_tiled.h"
 
@@ -241,6 +242,14 @@ struct epgx_state {
     int32_t K = 0;
     d2 *data = nullptr;
     double *dens = nullptr;
+};
+
+struct epgx_coords {   // per-voxel coordinates next to a state of 64 stored orders (epgx_prune.hip)
+    epgx_ctx *ctx = nullptr;
+    int64_t nvox = 0;
+    int32_t kdim = 0;
+    double *k = nullptr;        // [nvox][kdim][64]
+    int32_t *nlive = nullptr;   // [nvox]
 };
 
 static int set_device(const epgx_ctx *ctx) {
@@ -1510,6 +1519,209 @@ extern "C" int epgx_state_merge(epgx_ctx *ctx, epgx_state *dst, const epgx_state
     }
     dev_free(ctx, d_tab);   // (recycled in stream order, behind the kernel that reads it)
     if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_state_merge: %s", hipGetErrorString(e));
+    return EPGX_OK;
+}
+
+// ------------------------------------------------------------------------------ per-voxel float shift (epgx_prune.hip)
+extern "C" int epgx_coords_create(epgx_ctx *ctx, int64_t nvox, int32_t kdim, epgx_coords **out) {
+    if (!ctx || !out) return fail(EPGX_ERR_INVALID, "epgx_coords_create: NULL argument");
+    *out = nullptr;
+    if (nvox < 1) return fail(EPGX_ERR_INVALID, "epgx_coords_create: nvox < 1");
+    if (kdim < 1 || kdim > 4) return fail(EPGX_ERR_INVALID, "epgx_coords_create: kdim = %d, expected 1 .. 4", kdim);
+    if (int rc = set_device(ctx)) return rc;
+    epgx_coords *c = new (std::nothrow) epgx_coords();
+    if (!c) return fail(EPGX_ERR_NOMEM, "epgx_coords_create: host allocation failed");
+    c->ctx = ctx;
+    c->nvox = nvox;
+    c->kdim = kdim;
+    const size_t kbytes = sizeof(double) * (size_t)nvox * (size_t)kdim * PRUNE_K;
+    hipError_t e = dev_alloc(ctx, (void **)&c->k, kbytes);
+    if (e == hipSuccess) e = dev_alloc(ctx, (void **)&c->nlive, sizeof(int32_t) * (size_t)nvox);
+    if (e == hipSuccess) e = hipMemsetAsync(c->k, 0, kbytes, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->nlive, 0, sizeof(int32_t) * (size_t)nvox, ctx->stream);
+    if (e != hipSuccess) {
+        epgx_coords_destroy(c);
+        return fail(e == hipErrorOutOfMemory ? EPGX_ERR_NOMEM : EPGX_ERR_HIP, "epgx_coords_create: %s", hipGetErrorString(e));
+    }
+    *out = c;
+    return EPGX_OK;
+}
+
+extern "C" int epgx_coords_destroy(epgx_coords *c) {
+    if (!c) return EPGX_OK;
+    (void)hipSetDevice(c->ctx->device);
+    dev_free(c->ctx, c->k);
+    dev_free(c->ctx, c->nlive);
+    delete c;
+    return EPGX_OK;
+}
+
+extern "C" int epgx_coords_info(const epgx_coords *c, int64_t *nvox, int32_t *kdim) {
+    if (!c) return fail(EPGX_ERR_INVALID, "epgx_coords_info: NULL argument");
+    if (nvox) *nvox = c->nvox;
+    if (kdim) *kdim = c->kdim;
+    return EPGX_OK;
+}
+
+static int coords_widen(epgx_coords *dst, const double *d_k, const int32_t *d_n, int32_t ks, int broadcast) {
+    CoordsWidenArgs a;
+    a.dst = dst->k;
+    a.src = d_k;
+    a.ndst = dst->nlive;
+    a.nsrc_rows = d_n;
+    a.nvox = dst->nvox;
+    a.kd = dst->kdim;
+    a.ks = ks;
+    a.broadcast = broadcast;
+    HIP_TRY(epgx_launch_coords_widen(dst->ctx->stream, a));
+    return EPGX_OK;
+}
+
+extern "C" int epgx_coords_upload(epgx_coords *c, const double *k, const int32_t *nlive, int64_t nsrc) {
+    if (!c || !k || !nlive) return fail(EPGX_ERR_INVALID, "epgx_coords_upload: NULL argument");
+    if (nsrc != 1 && nsrc != c->nvox)
+        return fail(EPGX_ERR_INVALID, "epgx_coords_upload: %lld coordinate sets for %lld voxels (one for all, or one each)", (long long)nsrc,
+                    (long long)c->nvox);
+    for (int64_t v = 0; v < nsrc; ++v)
+        if (nlive[v] < 1 || nlive[v] > PRUNE_K)
+            return fail(EPGX_ERR_INVALID, "epgx_coords_upload: nlive[%lld] = %d not in [1, %d]", (long long)v, nlive[v], PRUNE_K);
+    epgx_ctx *ctx = c->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    const size_t kbytes = sizeof(double) * (size_t)nsrc * (size_t)c->kdim * PRUNE_K, nbytes = sizeof(int32_t) * (size_t)nsrc;
+    if (nsrc == c->nvox) {
+        if (int rc = epgx_memcpy_h2d(ctx, c->k, k, (int64_t)kbytes)) return rc;
+        return epgx_memcpy_h2d(ctx, c->nlive, nlive, (int64_t)nbytes);
+    }
+    char *block = nullptr;      // one set for all voxels: uploaded once, repeated on the device
+    HIP_TRY(dev_alloc(ctx, (void **)&block, kbytes + nbytes));
+    int rc = epgx_memcpy_h2d(ctx, block, k, (int64_t)kbytes);
+    if (!rc) rc = epgx_memcpy_h2d(ctx, block + kbytes, nlive, (int64_t)nbytes);
+    if (!rc) rc = coords_widen(c, (const double *)block, (const int32_t *)(block + kbytes), c->kdim, 1);
+    dev_free(ctx, block);   // (recycled in stream order, behind the kernel that reads it)
+    return rc;
+}
+
+extern "C" int epgx_coords_download(const epgx_coords *c, double *k, int32_t *nlive) {
+    if (!c || !k || !nlive) return fail(EPGX_ERR_INVALID, "epgx_coords_download: NULL argument");
+    if (int rc = epgx_memcpy_d2h(c->ctx, k, c->k, (int64_t)(sizeof(double) * (size_t)c->nvox * (size_t)c->kdim * PRUNE_K))) return rc;
+    return epgx_memcpy_d2h(c->ctx, nlive, c->nlive, (int64_t)(sizeof(int32_t) * (size_t)c->nvox));
+}
+
+extern "C" int epgx_coords_widen(epgx_coords *dst, const epgx_coords *src) {
+    if (!dst || !src) return fail(EPGX_ERR_INVALID, "epgx_coords_widen: NULL argument");
+    if (dst == src || dst->k == src->k) return fail(EPGX_ERR_INVALID, "epgx_coords_widen: dst and src must differ");
+    if (dst->ctx != src->ctx) return fail(EPGX_ERR_INVALID, "epgx_coords_widen: different contexts");
+    if (dst->nvox != src->nvox || dst->kdim < src->kdim)
+        return fail(EPGX_ERR_INVALID, "epgx_coords_widen: %lld voxels x %d columns into %lld x %d", (long long)src->nvox, src->kdim,
+                    (long long)dst->nvox, dst->kdim);
+    if (int rc = set_device(dst->ctx)) return rc;
+    return coords_widen(dst, src->k, src->nlive, src->kdim, 0);
+}
+
+extern "C" int epgx_state_prune_shift(epgx_ctx *ctx, epgx_state *dst, epgx_coords *cdst, const epgx_state *src, const epgx_coords *csrc,
+                                      const double *table, int64_t ntable, int32_t ndim, const int64_t *shape, const int64_t *sstride,
+                                      const double *ktvalue, const double *grid, int32_t nmax, int32_t prune, double tol,
+                                      int32_t *max_live) {
+    if (!ctx || !dst || !cdst || !src || !csrc || !table || !shape || !sstride || !ktvalue || !grid || !max_live)
+        return fail(EPGX_ERR_INVALID, "epgx_state_prune_shift: NULL argument");
+    if (dst->ctx != ctx || src->ctx != ctx || cdst->ctx != ctx || csrc->ctx != ctx)
+        return fail(EPGX_ERR_INVALID, "epgx_state_prune_shift: a state or a coordinate buffer belongs to another context");
+    if (dst == src || dst->data == src->data || cdst == csrc || cdst->k == csrc->k)
+        return fail(EPGX_ERR_INVALID, "epgx_state_prune_shift: dst and src must differ");
+    const int64_t nvox = src->nvox;
+    if (dst->nvox != nvox || cdst->nvox != nvox || csrc->nvox != nvox)
+        return fail(EPGX_ERR_INVALID, "epgx_state_prune_shift: nvox mismatch (%lld, %lld, %lld, %lld)", (long long)dst->nvox,
+                    (long long)cdst->nvox, (long long)src->nvox, (long long)csrc->nvox);
+    const int32_t kdim = csrc->kdim;
+    if (kdim < 1 || kdim > 4 || cdst->kdim != kdim)
+        return fail(EPGX_ERR_INVALID, "epgx_state_prune_shift: kdim = %d / %d, expected equal and 1 .. 4", csrc->kdim, cdst->kdim);
+    if (dst->K != PRUNE_K || src->K != PRUNE_K)
+        return fail(EPGX_ERR_UNSUPPORTED, "epgx_state_prune_shift: states of %d / %d stored orders, the per-voxel shift covers %d", src->K,
+                    dst->K, PRUNE_K);
+    if (ndim < 1 || ndim > PRUNE_MAX_DIMS) return fail(EPGX_ERR_INVALID, "epgx_state_prune_shift: ndim = %d not in [1, %d]", ndim, PRUNE_MAX_DIMS);
+    if (ntable < 1) return fail(EPGX_ERR_INVALID, "epgx_state_prune_shift: ntable < 1");
+    int64_t total = 1, last = 0;
+    for (int d = 0; d < ndim; ++d) {
+        if (shape[d] < 1 || sstride[d] < 0 || total > nvox)
+            return fail(EPGX_ERR_INVALID, "epgx_state_prune_shift: grid axis %d: extent %lld, table stride %lld", d, (long long)shape[d],
+                        (long long)sstride[d]);
+        total *= shape[d];
+        last += (shape[d] - 1) * sstride[d];
+    }
+    if (total != nvox) return fail(EPGX_ERR_INVALID, "epgx_state_prune_shift: a grid of %lld voxels for states of %lld", (long long)total, (long long)nvox);
+    if (last >= ntable) return fail(EPGX_ERR_INVALID, "epgx_state_prune_shift: the grid reaches entry %lld of a table of %lld", (long long)last, (long long)ntable);
+    for (int c = 0; c < kdim; ++c) {
+        if (!(grid[c] > 0.0) || !std::isfinite(grid[c])) return fail(EPGX_ERR_INVALID, "epgx_state_prune_shift: grid[%d] = %g, expected positive", c, grid[c]);
+        if (ktvalue[c] == 0.0 || !std::isfinite(ktvalue[c])) return fail(EPGX_ERR_INVALID, "epgx_state_prune_shift: ktvalue[%d] = %g", c, ktvalue[c]);
+    }
+    for (int64_t i = 0; i < ntable * kdim; ++i)
+        if (!std::isfinite(table[i])) return fail(EPGX_ERR_INVALID, "epgx_state_prune_shift: table[%lld] is not finite", (long long)i);
+    if (!(tol >= 0.0)) return fail(EPGX_ERR_INVALID, "epgx_state_prune_shift: tol = %g", tol);
+    if (int rc = set_device(ctx)) return rc;
+
+    PruneArgs a;
+    a.dst = dst->data;
+    a.src = src->data;
+    a.kdst = cdst->k;
+    a.ksrc = csrc->k;
+    a.ndst = cdst->nlive;
+    a.nsrc = csrc->nlive;
+    a.nvox = nvox;
+    a.kdim = kdim;
+    a.ndim = ndim;
+    int64_t stride = nvox;
+    for (int d = 0; d < PRUNE_MAX_DIMS; ++d) {
+        a.shape[d] = d < ndim ? shape[d] : 1;
+        stride /= a.shape[d];
+        a.vstride[d] = d < ndim ? stride : 1;
+        a.sstride[d] = d < ndim ? sstride[d] : 0;
+    }
+    for (int c = 0; c < 4; ++c) {
+        a.scale_in[c] = a.scale_out[c] = c < kdim ? ktvalue[c] : 1.0;
+        a.grid[c] = c < kdim ? grid[c] : 1.0;
+    }
+    a.nmax = nmax < 0 ? -1 : nmax;
+    a.prune = prune ? 1 : 0;
+    a.tol = tol;
+    a.nblocks = (int32_t)(nvox < PRUNE_MAX_BLOCKS ? nvox : PRUNE_MAX_BLOCKS);
+    const size_t tbytes = (sizeof(double) * (size_t)ntable * (size_t)kdim + 15) & ~(size_t)15;
+    char *block = nullptr;
+    HIP_TRY(dev_alloc(ctx, (void **)&block, tbytes + sizeof(int32_t) * (2 * (size_t)a.nblocks + 2)));
+    a.table = (const double *)block;
+    a.result = (int32_t *)(block + tbytes);
+    a.partial = a.result + 2;
+    int32_t result[2] = {0, 0};
+    hipError_t e = hipMemcpyAsync(block, table, sizeof(double) * (size_t)ntable * (size_t)kdim, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (`table` is the caller's)
+    if (e == hipSuccess) e = epgx_launch_prune_shift(ctx->stream, a);
+    if (e == hipSuccess) e = hipMemcpyAsync(dst->dens, src->dens, sizeof(double) * (size_t)nvox, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(result, a.result, sizeof(result), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    dev_free(ctx, block);
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_state_prune_shift: %s", hipGetErrorString(e));
+    if (result[1])
+        return fail(EPGX_ERR_UNSUPPORTED, "epgx_state_prune_shift: a voxel keeps more than %d stored orders after trim and prune", PRUNE_K);
+    *max_live = result[0];
+    return EPGX_OK;
+}
+
+extern "C" int epgx_state_prune_read(epgx_ctx *ctx, const epgx_state *st, const epgx_coords *c, double tvalue, void *out) {
+    if (!ctx || !st || !c || !out) return fail(EPGX_ERR_INVALID, "epgx_state_prune_read: NULL argument");
+    if (st->ctx != ctx || c->ctx != ctx) return fail(EPGX_ERR_INVALID, "epgx_state_prune_read: the state or the coordinates belong to another context");
+    if (st->nvox != c->nvox) return fail(EPGX_ERR_INVALID, "epgx_state_prune_read: nvox mismatch (%lld vs %lld)", (long long)st->nvox, (long long)c->nvox);
+    if (c->kdim != 4) return fail(EPGX_ERR_INVALID, "epgx_state_prune_read: kdim = %d, the read-out weighs a time coordinate (kdim 4)", c->kdim);
+    if (st->K != PRUNE_K) return fail(EPGX_ERR_UNSUPPORTED, "epgx_state_prune_read: a state of %d stored orders, expected %d", st->K, PRUNE_K);
+    if (!std::isfinite(tvalue)) return fail(EPGX_ERR_INVALID, "epgx_state_prune_read: tvalue = %g", tvalue);
+    if (((uintptr_t)out & 15) != 0) return fail(EPGX_ERR_INVALID, "epgx_state_prune_read: out is not aligned to 16 bytes");
+    if (int rc = set_device(ctx)) return rc;
+    PruneReadArgs a;
+    a.state = st->data;
+    a.k = c->k;
+    a.nlive = c->nlive;
+    a.nvox = st->nvox;
+    a.tscale = tvalue;
+    a.out = (d2 *)out;
+    HIP_TRY(epgx_launch_prune_read(ctx->stream, a));
     return EPGX_OK;
 }
 

@@ -593,6 +593,9 @@ def simulate_sharded(sequence, *, group=None, dst=0, probe=None, adc_time=False,
     if dtype != np.complex128 and out == "device":
         raise NotImplementedError('out="device" keeps complex128 records')
     flat = functions.flatten_sequence(sequence)
+    if options.get("voxel_coords"):
+        raise NotImplementedError("simulate_sharded with per-voxel float shifts (shift-prune, voxel_coords): they run operator by "
+                                  "operator on one GPU (simulate)")
     from .diff import Hessian
     if any(isinstance(pb, Hessian) for pb in (list(probe) if isinstance(probe, (tuple, list)) else [probe]) + flat):
         # (the fused second-order passes run on one GPU; the same refusal sits in compile_sequence for ShardedPlan)

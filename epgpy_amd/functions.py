@@ -329,7 +329,7 @@ def simulate(sequence, *, adc_time=False, init=None, squeeze=False, probe=None, 
         _check_exchange(sequence, probes, init, out, devices, mode, callback)
     float_shift = has_float_shift(sequence, init)
     if float_shift:
-        _check_float_shift(sequence, probes, {**(init.options if init is not None else {}), **options})
+        _check_float_shift(sequence, probes, {**(init.options if init is not None else {}), **options}, init, mode, out, devices)
     on_device = not float_shift and all((pb or op)._device_kind() is not None
                     for op in sequence if isinstance(op, Probe) for pb in (probes or [op]))
     on_device = on_device and not any(part._on_host() for op in sequence for part in op._parts())   # (user-written operators)
@@ -387,13 +387,40 @@ def has_float_shift(sequence, init=None):
     k, G, C), or any shift once the start state has float coordinates.  Such a shift needs reductions of the state as it stands
     (kmerge.py): the sequence runs operator by operator -- device modes, out="device" and ngpu > 1 raise what they raise for
     probes the kernel cannot record"""
-    floating = init is not None and getattr(getattr(init, "_kspace", None), "points", np.zeros(0, int)).dtype.kind == "f"
+    from . import kmerge
+    floating = init is not None and kmerge.is_float(getattr(init, "_kspace", None))
     return any(isinstance(part, _shift.S) and (floating or part._float_k()) for op in sequence for part in op._parts())
 
 
-def _check_float_shift(sequence, probes, options):
+def _check_float_shift(sequence, probes, options, init=None, mode="auto", out="host", devices=(0,)):
     """what a sequence with a float shift does not carry: NotImplementedError that names the thing"""
     from .diff import Jacobian, Hessian
+    from . import kmerge
+    ks = getattr(init, "_kspace", None)
+    if options.get("voxel_coords") and (isinstance(ks, kmerge.VoxelKSpace) or any(
+            isinstance(part, _shift.S) and kmerge.per_voxel(part, ks) for op in sequence for part in op._parts())):
+        # per-voxel coordinates (shift-prune) run operator by operator on one GPU, records to the host
+        if mode in ("resident", "stream"):
+            raise NotImplementedError(f"mode={mode!r} with per-voxel float shifts (shift-prune, voxel_coords): they run operator by operator")
+        if out == "device":
+            raise NotImplementedError('out="device" with per-voxel float shifts (shift-prune, voxel_coords)')
+        if len(devices) > 1:
+            raise NotImplementedError("ngpu > 1 with per-voxel float shifts (shift-prune, voxel_coords): one GPU")
+        from .diffusion import D
+        if any(isinstance(part, D) for op in sequence for part in op._parts()):
+            raise NotImplementedError("D (diffusion) on per-voxel coordinates (shift-prune, voxel_coords)")
+        from .probe import DFT, Imaging
+        from .operator import System
+        for cls in (DFT, Imaging, System):
+            if any(isinstance(x, cls) for x in list(probes or ()) + list(sequence) + [part for op in sequence for part in op._parts()]):
+                raise NotImplementedError(f"{cls.__name__} on per-voxel coordinates (shift-prune, voxel_coords): the spatial read-out "
+                                          "takes coordinates shared by all voxels")
+        if init is not None and getattr(init, "_eq", None) is not None:
+            raise NotImplementedError("a general equilibrium with per-voxel float shifts (shift-prune, voxel_coords)")
+        if np.ndim(options.get("kgrid")) > 1:
+            raise NotImplementedError("a different kgrid per voxel: the grid is a scalar or one value per coordinate column")
+        if options.get("kgrid") is None and not any(getattr(part, "kgrid", None) is not None for op in sequence for part in op._parts()):
+            raise AttributeError("kgrid not set")
     if not options.get("kgrid") and any(getattr(part, "kgrid", None) is not None for op in sequence for part in op._parts()):
         # one run, one grid: the coordinate set of a run is ordered by the cells of ONE grid (kmerge.FloatKSpace), which
         # simulate() takes as the state-matrix option.  A grid that only single operators carry is honoured by op(sm)

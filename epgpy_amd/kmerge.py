@@ -19,6 +19,7 @@ import numpy as np
 from . import _lib, kspace
 
 NAX = np.newaxis
+VOXEL_HINT = "; the option voxel_coords=True (StateMatrix / simulate) runs it per voxel on the device"
 
 
 class FloatKSpace(kspace.KSpace):
@@ -29,7 +30,7 @@ class FloatKSpace(kspace.KSpace):
     def __init__(self, coords, nz_f=None, nz_z=None, lead=()):
         pts = np.array(coords, dtype=np.float64)
         if lead:
-            raise NotImplementedError("float coordinates that differ between voxels (shift-prune, shift.py:478-542)")
+            raise NotImplementedError("float coordinates that differ between voxels (shift-prune, shift.py:478-542)" + VOXEL_HINT)
         self.lead = ()
         self.points = pts.reshape(pts.shape[0], 1, pts.shape[-1])
         self.nz_f = self.nz_z = np.ones(len(pts), dtype=bool)
@@ -47,7 +48,7 @@ class FloatKSpace(kspace.KSpace):
         if coords.ndim < 2 or coords.shape[-2] % 2 != 1:
             raise ValueError("coords: expected [..., 2n+1, kdim]")
         if any(d != 1 for d in coords.shape[:-2]):
-            raise NotImplementedError("float coordinates that differ between voxels (shift-prune, shift.py:478-542)")
+            raise NotImplementedError("float coordinates that differ between voxels (shift-prune, shift.py:478-542)" + VOXEL_HINT)
         pts = coords.reshape(coords.shape[-2:])
         if not np.allclose(pts, -pts[::-1], rtol=1e-9, atol=1e-12 * max(1.0, float(np.abs(pts).max(initial=0.0)))):
             raise ValueError("coords: rows must be symmetric about the centre row")
@@ -68,7 +69,7 @@ class FloatKSpace(kspace.KSpace):
 
     def with_lead(self, lead):
         if tuple(lead):
-            raise NotImplementedError("float coordinates that differ between voxels (shift-prune, shift.py:478-542)")
+            raise NotImplementedError("float coordinates that differ between voxels (shift-prune, shift.py:478-542)" + VOXEL_HINT)
         return self
 
     def _like(self, nz_f, nz_z):
@@ -82,6 +83,93 @@ class FloatKSpace(kspace.KSpace):
         if self.kdim <= 3:
             return super().bmatrices(kvalue, shift)
         return FloatKSpace(self.points[:, 0, :3]).bmatrices(kvalue, None if shift is None else np.asarray(shift).reshape(-1)[:3])
+
+
+class VoxelKSpace(FloatKSpace):
+    """float coordinates that differ between voxels, after a per-voxel shift (`shift_prune`): a device buffer [nvox][kdim][64]
+    with the live stored rows per voxel (_lib.DeviceCoords) next to the state.  `nstate + 1` is the largest live count; a
+    voxel's live rows are its stored orders 0 .. live - 1 in lexicographic order of their grid cells, the rest exact zeros.
+    Row-local operators pass it on unchanged; whatever reads shared coordinates on the host (D, DFT / Imaging / System, the
+    planned shifts) does not run on it."""
+
+    def __init__(self, dev, grid, nstate):
+        self.dev, self.grid, self._n = dev, tuple(int(d) for d in grid), int(nstate)
+        self.lead = self.grid
+        self.nz_f = self.nz_z = np.ones(2 * self._n + 1, dtype=bool)
+
+    @classmethod
+    def equilibrium(cls, kdim):
+        """RESET: one row at the origin in every voxel -- shared coordinates again"""
+        return FloatKSpace.equilibrium(kdim)
+
+    @classmethod
+    def from_coords(cls, ctx, coords, grid):
+        """coordinates [*grid', 2n+1, kdim] as `StateMatrix.coords` exports them (grid' broadcasts to `grid`): per voxel the
+        live rows centred and symmetric, zero rows at both ends"""
+        coords = np.asarray(coords, dtype=np.float64)
+        if coords.ndim < 2 or coords.shape[-2] % 2 != 1 or not 1 <= coords.shape[-1] <= 4:
+            raise ValueError("coords: expected [..., 2n+1, kdim] with kdim 1 .. 4")
+        n, kdim = (coords.shape[-2] - 1) // 2, coords.shape[-1]
+        if n + 1 > _lib.PRUNE_K:
+            raise NotImplementedError(f"per-voxel coordinates with more than {_lib.PRUNE_K} stored orders (kgrid / max_nstate / prune)")
+        if not np.allclose(coords, -coords[..., ::-1, :], rtol=1e-9, atol=1e-12 * max(1.0, float(np.abs(coords).max(initial=0.0)))):
+            raise ValueError("coords: rows must be symmetric about the centre row")
+        lead = coords.shape[:-2]
+        full = np.broadcast_to(coords.reshape(lead + (1,) * (len(grid) - len(lead)) + coords.shape[-2:]), tuple(grid) + coords.shape[-2:])
+        half = full.reshape(-1, 2 * n + 1, kdim)[:, n:, :]
+        used = np.any(half != 0, axis=-1)                       # (rows past the live ones are exact zeros)
+        nlive = np.where(used.any(axis=1), n + 1 - np.argmax(used[:, ::-1], axis=1), 1).astype(np.int32)
+        k = np.zeros((half.shape[0], kdim, _lib.PRUNE_K))
+        k[:, :, : n + 1] = np.moveaxis(half, -1, -2)
+        dev = _lib.DeviceCoords(ctx, half.shape[0], kdim)
+        dev.upload(k, nlive)
+        return cls(dev, grid, n)
+
+    @property
+    def points(self):
+        raise NotImplementedError("per-voxel coordinates (voxel_coords) live on the device: D, DFT / Imaging / System and planned "
+                                  "shifts read coordinates shared by all voxels and do not run on them")
+
+    @property
+    def kdim(self):
+        return self.dev.kdim
+
+    @property
+    def nrow(self):
+        return 2 * self._n + 1
+
+    @property
+    def coords(self):
+        """[*grid, 2n+1, kdim]: downloaded and mirrored"""
+        k, _ = self.dev.download()
+        pos = np.moveaxis(k[:, :, : self._n + 1], -2, -1)
+        return np.concatenate([0.0 - pos[:, :0:-1, :], pos], axis=1).reshape(self.grid + (self.nrow, self.kdim))
+
+    def live(self):
+        """live stored rows per voxel [*grid]"""
+        return self.dev.download()[1].reshape(self.grid)
+
+    def with_kdim(self, kdim):
+        if kdim == self.kdim:
+            return self
+        if kdim < self.kdim:
+            raise RuntimeError("Cannot remove existing k-dimension")
+        return VoxelKSpace(self.dev.widen(kdim), self.grid, self._n)
+
+    def with_lead(self, lead):
+        if tuple(lead) != self.grid:
+            raise NotImplementedError(f"widening the grid of a state matrix that holds per-voxel coordinates (voxel_coords): "
+                                      f"{self.grid} -> {tuple(lead)}; give the state matrix its full shape before the first shift")
+        return self
+
+    def bmatrices(self, kvalue, shift=None):
+        raise NotImplementedError("D (diffusion) on per-voxel coordinates (voxel_coords): the b-matrices are planned on the host "
+                                  "from coordinates shared by all voxels")
+
+
+def is_float(ks):
+    """True for a coordinate set with float coordinates (after a float shift)"""
+    return isinstance(ks, FloatKSpace)
 
 
 def ktvalue(kvalue, tvalue, kdim):
@@ -206,6 +294,12 @@ def merges(shift_op, ks):
     return isinstance(ks, FloatKSpace) or shift_op._float_k()
 
 
+def per_voxel(shift_op, ks):
+    """True if a merging shift gives (or meets) coordinates that differ between voxels: the reference's 'shift-prune'
+    (shift.py:247-249), and -- a deliberate deviation, DESIGN 4.14 -- every shift once the coordinates are per voxel"""
+    return isinstance(ks, VoxelKSpace) or (merges(shift_op, ks) and np.sum(np.shape(shift_op.k)[:-1]) > 1)
+
+
 def has_merge(ks, ops):
     from .shift import S
     return any(isinstance(op, S) and merges(op, ks) for op in ops)
@@ -225,7 +319,10 @@ def apply(sm, ops):
             if batch:
                 sm = apply_operators(sm, batch)
                 batch = []
-            sm = shift_merge(sm, op)
+            if sm.options.get("voxel_coords") and per_voxel(op, sm._kspace):
+                sm = shift_prune(sm, op)
+            else:
+                sm = shift_merge(sm, op)
         else:
             batch.append(op)
     return apply_operators(sm, batch) if batch else sm
@@ -243,7 +340,7 @@ def shift_merge(sm, op):
         shift = np.asarray(k)
     if np.sum(np.shape(shift)[:-1]) > 1:
         raise NotImplementedError("a float wavenumber that varies along a grid axis (shift-prune, shift.py:247-249, :478-542): "
-                                  "the coordinate sets would differ per voxel")
+                                  "the coordinate sets would differ per voxel" + VOXEL_HINT)
     kgrid = sm.options.get("kgrid") or op.kgrid
     if kgrid is None:
         raise AttributeError("kgrid not set")
@@ -256,7 +353,7 @@ def shift_merge(sm, op):
     if ks is None:
         ks = kspace.KSpace.from_orders(sm.nstate, kdim)
     if ks.lead:
-        raise NotImplementedError("a float shift of coordinates that differ between voxels (shift-prune, shift.py:478-542)")
+        raise NotImplementedError("a float shift of coordinates that differ between voxels (shift-prune, shift.py:478-542)" + VOXEL_HINT)
     if ks.kdim < kdim:
         ks = ks.with_kdim(kdim)
     elif kdim < ks.kdim:
@@ -278,6 +375,74 @@ def shift_merge(sm, op):
         compact(ctx, dst, keep, sm.shape)
     sm._state, sm._nstate = dst, len(keep) - 1
     sm._kspace = FloatKSpace(wavenums / ktv)
+    return sm
+
+
+def shift_prune(sm, op):
+    """S._apply, branch 'shift-prune' (shift.py:120-148, :478-629), on the device-resident state of `sm`: every voxel sorts,
+    merges, weighs, trims and prunes its own rows (epgx_state_prune_shift); two words come back per shift.  Every check of
+    the arguments stands before the first change of `sm`; a voxel that overflows on the device raises after `sm` was broadcast
+    to the shift's grid (its values unchanged)"""
+    from . import common
+    if getattr(sm, "order1", None) or getattr(sm, "order2", None):
+        raise NotImplementedError("derivative states (order1 / order2, Jacobian / Hessian) through a per-voxel float shift (shift-prune)")
+    ks = sm._kspace
+    if isinstance(op.k, int):       # onto existing coordinates: [k, 0, ...] (shift.py:243-244)
+        shift = np.zeros((1, ks.kdim if ks is not None else 1))
+        shift[0, 0] = op.k
+    else:
+        shift = np.asarray(op.k, dtype=np.float64)
+    kgrid = sm.options.get("kgrid") or op.kgrid
+    if kgrid is None:
+        raise AttributeError("kgrid not set")
+    if np.ndim(kgrid) > 1:
+        raise NotImplementedError("a different kgrid per voxel: the grid is a scalar or one value per coordinate column")
+    nmax = sm.options.get("max_nstate") or op.nmax or None
+    prune = sm.options.get("prune") or op.prune
+    tol = 1e-8 if prune in (True, False) else float(prune)
+    prune = bool(prune)
+
+    grid = tuple(common.broadcast_shapes(sm.shape, shift.shape[:-1], append=True))
+    if len(grid) > _lib.PRUNE_MAX_DIMS:
+        raise NotImplementedError(f"a per-voxel shift on a grid of more than {_lib.PRUNE_MAX_DIMS} axes")
+    # every check that can raise stands before the first change of `sm`
+    if isinstance(ks, VoxelKSpace) and (grid != sm.shape or ks.grid != sm.shape):
+        raise NotImplementedError(f"widening the grid of a state matrix that holds per-voxel coordinates (voxel_coords): {ks.grid} -> "
+                                  f"{grid}; give the state matrix its full shape before the first per-voxel shift")
+    if sm.nstate + 1 > _lib.PRUNE_K or (ks is not None and ks.nstate != sm.nstate):
+        raise NotImplementedError(f"a per-voxel float shift (shift-prune) of more than {_lib.PRUNE_K} stored orders: a coarser "
+                                  "`kgrid`, a `max_nstate` or a larger `prune` tolerance keeps the state matrix under the limit")
+    if ks is not None and not isinstance(ks, VoxelKSpace) and ks.lead:
+        raise NotImplementedError("a per-voxel float shift of integer coordinates that differ along a leading grid axis")
+    if grid != sm.shape:
+        if len(grid) > sm.ndim:
+            sm.expand(len(grid))
+        sm._broadcast_to(grid)
+    kdim = max(shift.shape[-1], ks.kdim if ks is not None else 1)
+    if shift.shape[-1] < kdim:
+        shift = np.pad(shift, [(0, 0)] * (shift.ndim - 1) + [(0, kdim - shift.shape[-1])])
+    ctx = sm._ctx
+    if isinstance(ks, VoxelKSpace):
+        csrc = ks.with_kdim(kdim).dev
+    else:       # coordinates shared by all voxels: one upload, repeated on the device
+        if ks is None:
+            ks = kspace.KSpace.from_orders(sm.nstate, kdim)
+        half = np.asarray(ks.with_kdim(kdim).coords, dtype=np.float64)[ks.centre:]
+        k = np.zeros((1, kdim, _lib.PRUNE_K))
+        k[0, :, : len(half)] = half.T
+        csrc = _lib.DeviceCoords(ctx, sm.size, kdim)
+        csrc.upload(k, [len(half)])
+    src = sm._state if sm._state.K == _lib.PRUNE_K else sm._state.copy(_lib.PRUNE_K)
+
+    ktv = ktvalue(sm.kvalue, sm.tvalue, kdim).astype(np.float64)
+    kshape = shift.shape[:-1]
+    strides = [int(np.prod(kshape[d + 1:], dtype=np.int64)) if kshape[d] > 1 else 0 for d in range(len(kshape))]
+    sstride = strides + [0] * (len(grid) - len(kshape))
+    dst, cdst = _lib.DeviceState(ctx, sm.size, _lib.PRUNE_K), _lib.DeviceCoords(ctx, sm.size, kdim)
+    live = _lib.state_prune_shift(ctx, dst, cdst, src, csrc, shift.reshape(-1, kdim) * ktv, grid, sstride, ktv,
+                                  kgrid * np.ones(kdim), nmax, prune, tol)
+    sm._state, sm._nstate = dst, live - 1
+    sm._kspace = VoxelKSpace(cdst, grid, live - 1)
     return sm
 
 

@@ -257,6 +257,10 @@ def read_out(sm, positions, *, phase=None, weights=None, modulation=None, voxel_
     `acctime=sm.t` and `modulation` (decay rate and frequency of the accumulated time, utils.imaging); while kdim < 4
     `modulation` has no effect, as in the reference.  State matrices live at the library's capacities (up to 1024 orders),
     all of which the kernel covers."""
+    from . import kmerge
+    if isinstance(sm._kspace, kmerge.VoxelKSpace):
+        raise NotImplementedError("DFT / Imaging on per-voxel coordinates (shift-prune, voxel_coords): the spatial read-out takes "
+                                  "coordinates shared by all voxels")
     pos = np.asarray(positions)
     pos = pos if pos.ndim > 1 else pos[..., np.newaxis]
     wts = None if weights is None else np.asarray(weights)

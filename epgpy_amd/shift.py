@@ -8,11 +8,19 @@ Integer vectors -- one for all voxels, or one per point of the leading grid axes
 gather shift (kspace.py).  Float wavenumbers -- `S(1.5)`, the gradient `G(tau, gradient)`, the time accumulation `C(tau, R2)`,
 or any shift of coordinates that already are float -- take the shift-merge (kmerge.py): rows that fall into one cell of the
 grid `kgrid` merge, on the device, between two reductions of the resident state.  Such a shift is a barrier of the
-operator-by-operator path; shift-prune (a float wavenumber that varies along a grid axis) is not supported.
+operator-by-operator path.  A float wavenumber that varies along a grid axis (shift-prune: `S([[1.5], [0.5]])`, `G` with an
+array of gradients, `C` with an array `R2`) gives every voxel its own coordinate set: with the option `voxel_coords=True` of
+the state matrix / of simulate() the device sorts, merges, trims and prunes per voxel (kmerge.shift_prune); without it the
+shift raises as before.
 """
 import numpy as np
 
 from . import common, operator, utils, _lib
+
+
+def _is_float(ks):
+    from . import kmerge
+    return kmerge.is_float(ks)
 
 
 class S(operator.Operator):
@@ -48,7 +56,7 @@ class S(operator.Operator):
         """S has no parameters but is a DiffOperator in the reference (shift.py:14): derivative states
         attached to `sm` are shifted with it"""
         order1, order2 = getattr(sm, "order1", None), getattr(sm, "order2", None)
-        if (order1 or order2) and (self._float_k() or getattr(sm._kspace, "points", np.zeros(0, int)).dtype.kind == "f"):
+        if (order1 or order2) and (self._float_k() or _is_float(sm._kspace)):
             raise NotImplementedError("derivative states (order1 / order2, Jacobian / Hessian) through a float shift (shift-merge)")
         sm = super().__call__(sm, inplace=inplace)
         if order1 or order2:
@@ -64,12 +72,13 @@ class S(operator.Operator):
     def _encode(self, enc):
         # shift.py:86: the state-matrix option wins over the operator's own nmax
         nmax = enc.options.get("max_nstate") or self.nmax or None
-        if self._float_k() or (enc.kspace is not None and enc.kspace.points.dtype.kind == "f"):
+        if self._float_k() or _is_float(enc.kspace):
             if (enc.options.get("kgrid") or self.kgrid) is None:
                 raise AttributeError("kgrid not set")        # the reference's own error (shift.py:131-132)
             if np.sum(np.shape(self.k)[:-1]) > 1:
                 raise NotImplementedError("a float wavenumber that varies along a grid axis (shift-prune, shift.py:247-249, "
-                                          ":478-542): the coordinate sets would differ per voxel")
+                                          ":478-542): the coordinate sets would differ per voxel; the option voxel_coords=True "
+                                          "runs it per voxel, operator by operator (simulate / op(sm)), not in a compiled plan")
             raise NotImplementedError("a float shift (shift-merge, shift.py:367-449) cannot be compiled into a plan: it runs "
                                       "operator by operator (simulate(mode='stepwise') or op(sm))")
         if isinstance(self.k, int):

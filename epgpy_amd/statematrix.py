@@ -178,6 +178,15 @@ class StateMatrix:
             ks = kspace.KSpace.from_coords(coords)
         else:       # float coordinates: what `sm.coords` returns after a shift-merge (kmerge.py)
             coords = np.asarray(coords, dtype=np.float64)
+            if self.options.get("voxel_coords") and any(d != 1 for d in coords.shape[:-2]):
+                # one coordinate set per voxel: what `sm.coords` returns after a per-voxel shift (kmerge.shift_prune)
+                if not common.broadcastable(self._shape, coords.shape[:-2], append=True) or tuple(
+                        common.broadcast_shapes(self._shape, coords.shape[:-2], append=True)) != self._shape:
+                    raise ValueError(f"coords: leading shape {coords.shape[:-2]} does not fit the state matrix {self._shape}")
+                ks = kmerge.VoxelKSpace.from_coords(self._ctx, coords, self._shape)
+                if ks.nstate != self._nstate:
+                    raise ValueError(f"coords: {ks.nrow} rows for a state matrix with nstate={self._nstate}")
+                return ks
             ks = kmerge.FloatKSpace.from_coords(coords, self.options.get("kgrid"),
                                                 kmerge.ktvalue(self.kvalue, self.tvalue, coords.shape[-1]))
         if ks.nstate != self._nstate:
@@ -299,6 +308,9 @@ class StateMatrix:
         if self._kspace is None:
             return None
         ks = self._kspace
+        from . import kmerge
+        if isinstance(ks, kmerge.VoxelKSpace):      # per-voxel coordinates: [*grid, 2n+1, kdim], live rows centred
+            return ks.coords
         return ks.coords.reshape(ks.lead + (1,) * (self.ndim - len(ks.lead)) + (ks.nrow, ks.kdim))
 
     @property
@@ -362,6 +374,16 @@ class StateMatrix:
         -j carries the weight of row +j, so this is the spatial read-out (epgx_state_dft) at ONE position, the origin, with
         the voxel factor w_j = i0_j exp(-|t_j|) of stored order j: only [nvox] values cross PCIe"""
         n = self._nstate
+        from . import kmerge
+        if isinstance(self._kspace, kmerge.VoxelKSpace):      # per-voxel coordinates: i0 and exp(-|t|) per voxel, on the device
+            if self._state.K != _lib.PRUNE_K:
+                raise NotImplementedError("F0 of per-voxel coordinates on a state matrix that was widened past 64 stored orders")
+            buf = _lib.DeviceBuffer(self._ctx, 16 * self.size)
+            try:
+                _lib.state_prune_read(self._ctx, self._state, self._kspace.dev, self.tvalue, buf.ptr.value)
+                return buf.download(np.complex128, (self.size,)).reshape(self._shape)
+            finally:
+                buf.free()
         w = (self.i0 * np.exp(-np.abs(self.t))).reshape(-1)[n:]
         if n + 1 > self._state.K:
             raise NotImplementedError("F0 of a state matrix with a time coordinate that was truncated at its capacity")

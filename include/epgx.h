@@ -461,6 +461,49 @@ int epgx_state_row_stats(epgx_ctx *ctx, const epgx_state *st, int32_t nrow, doub
 int epgx_state_merge(epgx_ctx *ctx, epgx_state *dst, const epgx_state *src, int32_t nrow_dst, const int32_t *offsets,
                      const int32_t *sources);
 
+/* The per-voxel float shift (epgpy/shift.py:478-629 `shiftprune`; csrc/epgx_prune.hip): a float wavenumber that varies along
+ * a grid axis gives every voxel its own coordinate set.  An epgx_coords buffer holds, next to a state of 64 stored orders,
+ * the coordinates [nvox][kdim][64] (float64, stored order j of voxel v in column c at k[(v * kdim + c) * 64 + j]) and the
+ * number of live stored rows per voxel; rows from the live count on are exact zeros in state and coordinates.
+ *
+ * epgx_coords_create: all coordinates zero, live counts zero (to be filled by upload, widen or a shift).
+ * epgx_coords_upload: host k [nsrc][kdim][64] and nlive [nsrc] (each in [1, 64]); nsrc = nvox, or 1: the one set is repeated
+ *   for every voxel on the device.  epgx_coords_download: the reverse, always [nvox].
+ * epgx_coords_widen: dst (kdim >= that of src, same nvox) takes the coordinates of src, further columns zero.
+ * Errors: EPGX_ERR_INVALID for a NULL argument, nvox < 1, kdim outside 1 .. 4, nsrc other than 1 or nvox, a live count outside
+ * [1, 64], buffers of different contexts or sizes.  (`struct epgx_coords` is opaque like the other handles.) */
+int epgx_coords_create(epgx_ctx *ctx, int64_t nvox, int32_t kdim, struct epgx_coords **out);
+int epgx_coords_destroy(struct epgx_coords *c);
+int epgx_coords_info(const struct epgx_coords *c, int64_t *nvox, int32_t *kdim);
+int epgx_coords_upload(struct epgx_coords *c, const double *k, const int32_t *nlive, int64_t nsrc);
+int epgx_coords_download(const struct epgx_coords *c, double *k, int32_t *nlive);
+int epgx_coords_widen(struct epgx_coords *dst, const struct epgx_coords *src);
+
+/* epgx_state_prune_shift: (dst, cdst) = the shift of (src, csrc), per voxel v by
+ *   s(v) = table[sum_d i_d(v) * sstride[d]][kdim],  i_d(v) the index of v along axis d of the C-ordered grid shape[ndim]
+ * (an axis the shift does not vary along has sstride 0; table is host [ntable][kdim], already multiplied by ktvalue).
+ * Wavenumbers are coordinates * ktvalue[c] on the way in and divided by it on the way out.  Per voxel: Z of row i stays at
+ * k_i, F goes to k_i + s, column 1 mirrors it; cells are rnd(k / grid[c]) with rnd(x) = trunc(x - 0.5 + (x > 0)); candidates
+ * that share a cell merge (sums in ascending row from +0; merged coordinate sum w k / (sum w + (sum w < 1e-12)), w the modulus
+ * of the source in this voxel); with nmax >= 0 and more than nmax positive rows the centre row and the nmax rows of largest
+ * sum_c |.|^2 stay; with prune != 0 the rows with sqrt(sum_c |.|^2) <= tol leave (never the centre row).  The live rows are
+ * stored in lexicographic order of their cells.  *max_live = the largest live count of a voxel.  dst takes the densities of
+ * src.  Deterministic, no atomics: a voxel's bits depend on the voxel alone.  The call synchronises the context's stream.
+ * Errors (nothing is launched): EPGX_ERR_INVALID for a NULL argument, objects of another context, dst == src, different
+ * nvox or kdim, ndim outside 1 .. 8, a grid that does not hold nvox voxels, a table index outside the table, a non-positive
+ * grid, a zero ktvalue, a value that is not finite; EPGX_ERR_UNSUPPORTED for states of another capacity than 64.
+ * After the launch: EPGX_ERR_UNSUPPORTED if some voxel keeps more than 64 stored orders after trim and prune; src and csrc
+ * are untouched, dst and cdst are to be dropped. */
+int epgx_state_prune_shift(epgx_ctx *ctx, epgx_state *dst, struct epgx_coords *cdst, const epgx_state *src, const struct epgx_coords *csrc,
+                           const double *table, int64_t ntable, int32_t ndim, const int64_t *shape, const int64_t *sstride,
+                           const double *ktvalue /*[kdim]*/, const double *grid /*[kdim]*/, int32_t nmax, int32_t prune, double tol,
+                           int32_t *max_live);
+
+/* epgx_state_prune_read: F0 with a time coordinate (kdim 4; statematrix.py:149-155) and per-voxel coordinates,
+ *   out[v] = sum over the rows of v whose three wavenumber coordinates are within 1e-8 of zero of F exp(-|t tvalue|),
+ * out: DEVICE complex128 [nvox], 16-byte aligned.  Stream-ordered, not synchronised. */
+int epgx_state_prune_read(epgx_ctx *ctx, const epgx_state *st, const struct epgx_coords *c, double tvalue, void *out);
+
 /* ---- run ------------------------------------------------------------------------------ */
 /* Apply operators [op_begin, op_end) of `plan` to voxels [vox0, vox0+nvox) of the plan's grid.
  *   in  : state to start from (its voxel j is grid voxel vox0+j), or NULL = equilibrium
