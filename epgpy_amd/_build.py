@@ -16,7 +16,7 @@ OBJDIR = os.path.join(CSRC, "build")
 LIBPATH = os.path.join(CSRC, "libepgx.so")
 # (object name, source, extra flags)
 UNITS = [("epgx_api.o", "epgx_api.hip", []), ("epgx_planner.o", "epgx_planner.cpp", []),
-         ("epgx_plan_check.o", "epgx_plan_check.cpp", [])] + \
+         ("epgx_plan_check.o", "epgx_plan_check.cpp", []), ("epgx_run_check.o", "epgx_run_check.cpp", [])] + \
         [(f"epgx_split_p{part}.o", "epgx_split.hip", [f"-DEPGX_PART={part}"]) for part in (16, 0, 8, 4, 2)] + \
         [(f"epgx_cgrow_m{m}.o", "epgx_cgrow.hip", [f"-DEPGX_M={m}"]) for m in (16, 8, 4, 2)] + \
         [(f"epgx_packed_v{v}_k{k}.o", "epgx_packed.hip", [f"-DEPGX_V={v}", f"-DEPGX_KP={k}"]) for v in (3, 2, 1) for k in (32, 16)] + \
@@ -46,7 +46,8 @@ FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
          "-mllvm", "-structurizecfg-skip-uniform-regions=1",
          # the first 16 dwords of run_kernel's arguments are preloaded into SGPRs at wave launch
          "-mllvm", "-amdgpu-kernarg-preload-count=16"]
-# epgx_planner.cpp and epgx_plan_check.cpp are plain C++ (launch planning and plan analysis, no HIP): the host compiler alone
+# epgx_planner.cpp, epgx_plan_check.cpp and epgx_run_check.cpp are plain C++ (launch planning, plan and run analysis, no HIP):
+# the host compiler alone
 HOST_FLAGS = ["-x", "c++", "-O3", "-std=c++17", "-fPIC"]
 
 

@@ -43,6 +43,7 @@
 #include "epgx_launch_hess.h"
 #include "epgx_planner.h"
 #include "epgx_plan_check.h"
+#include "epgx_run_check.h"
 #include "epgx_chain.h"
 #include "epgx_dft.h"
 #include "epgx_stats.h"
@@ -255,10 +256,6 @@ struct epgx_coords {   // per-voxel coordinates next to a state of 64 stored ord
 static int set_device(const epgx_ctx *ctx) {
     HIP_TRY(hipSetDevice(ctx->device));
     return EPGX_OK;
-}
-
-static bool supported_K(int K) {
-    return K == 64 || K == 128 || K == 256 || K == 512 || K == 1024;
 }
 
 // ------------------------------------------------------------------------------ library
@@ -1774,11 +1771,36 @@ static int get_packed(epgx_plan *pl, int begin, int end, int K, const PackedRang
     return EPGX_OK;
 }
 
+// one call of epgx_run / epgx_kernel_for: the request as run analysis reads it (epgx_run_check.h) and the handles behind it
+struct RunCall {
+    RunRequest rq;
+    const epgx_state *in;
+    epgx_state *out;
+    void *signal;
+    d2 *signal_col() const { return signal ? (d2 *)signal + rq.signal_col0 : nullptr; }
+};
 
+static StateFacts facts_of(const epgx_state *st, const epgx_ctx *ctx) {
+    StateFacts f;
+    if (st) f.present = true, f.K = st->K, f.nvox = st->nvox, f.foreign = st->ctx != ctx;
+    return f;
+}
 
-static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin, int32_t op_end, int64_t vox0, int64_t nvox,
-                       const epgx_state *in, epgx_state *out, int32_t K, void *signal, int64_t signal_ld, int64_t signal_col0,
-                       char *name_out, int64_t name_bytes);
+static RunCall run_call(const epgx_ctx *ctx, int32_t op_begin, int32_t op_end, int64_t vox0, int64_t nvox, const epgx_state *in, epgx_state *out,
+                        int32_t K, void *signal, int64_t signal_ld, int64_t signal_col0, bool naming) {
+    RunCall call = {{}, in, out, signal};
+    call.rq.op_begin = op_begin, call.rq.op_end = op_end, call.rq.vox0 = vox0, call.rq.nvox = nvox, call.rq.K = K;
+    call.rq.in = facts_of(in, ctx), call.rq.out = facts_of(out, ctx);
+    call.rq.has_signal = signal != nullptr, call.rq.signal_ld = signal_ld, call.rq.signal_col0 = signal_col0, call.rq.naming = naming;
+    return call;
+}
+
+// what epgx_run and epgx_kernel_for do first, both through here: the handles, then everything that needs no record list
+static int analyse_call(const epgx_ctx *ctx, const epgx_plan *pl, const RunCall &call, RunDecision *d) {
+    if (!ctx || !pl) return fail(EPGX_ERR_INVALID, "epgx_run: NULL argument");
+    if (pl->ctx != ctx) return fail(EPGX_ERR_INVALID, "epgx_run: plan belongs to another context");
+    return analyse_run(pl->host, *pl, call.rq, knobs(), d);
+}
 
 // xrun_kernel launchers (epgx_xrun.hip, one translation unit per number of compartments): M = K / 64
 hipError_t epgx_launch_xrun_nc2(hipStream_t stream, const epgx::XRunArgs &a, int64_t ngroups, int M);
@@ -1824,140 +1846,79 @@ static int launch_exchange(epgx_ctx *ctx, const epgx_plan *pl, const epgx_op &op
     return EPGX_OK;
 }
 
-// A range that holds EPGX_OP_X in a plan with derivative states: ONE launch of dxrun_kernel<NC, M, V>, state and derivative
-// states in registers, from equilibrium.  There is no split path for derivatives (the per-timestep derivative kernels keep no
-// derivative states in HBM): what the kernel does not cover is EPGX_ERR_UNSUPPORTED.
-static int run_exchange_deriv(epgx_ctx *ctx, epgx_plan *pl, int32_t op_begin, int32_t op_end, int64_t vox0, int64_t nvox,
-                              const epgx_state *in, epgx_state *out, int32_t K, void *signal, int64_t signal_ld, int64_t signal_col0,
-                              char *name_out, int64_t name_bytes) {
-    const int NC = pl->x_ncomp, V = pl->host.n_vars, M = K / 64;
-    static const char *rule = "derivative states through an exchange (EPGX_OP_X) run on dxrun_kernel<N, K / 64, V>: N = 2 .. 4 compartments with "
-                              "N * (K / 64) * (1 + V) <= 8, first order, from equilibrium (in = out = NULL), no D / gather shifts";
-    if (pl->host.second) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: EPGX_DERIV_SECOND: %s", rule);
-    if (in || out) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: a state in HBM: %s", rule);
-    if (!xrun_deriv_fits(NC, K, V)) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: N = %d, K = %d, V = %d: %s", NC, K, V, rule);
-    if (vox0 % pl->x_span || nvox % pl->x_span)
-        return fail(EPGX_ERR_INVALID, "epgx_run: voxel range [%lld,%lld) cuts compartment groups (blocks of %lld voxels)", (long long)vox0,
-                    (long long)(vox0 + nvox), (long long)pl->x_span);
-    bool has_adc = false;
-    for (int i = op_begin; i < op_end; ++i) {
-        const int oc = pl->host.ops[i].opcode;
-        if (oc == EPGX_OP_D || oc == EPGX_OP_GS) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: operator %d (opcode %d): %s", i, oc, rule);
-        has_adc = has_adc || oc == EPGX_OP_ADC;
+// the device copy of `ops` (and, for dxrun_kernel, of `dops`), made on first use
+static int ensure_dev_ops(epgx_ctx *ctx, epgx_plan *pl, bool with_dops) {
+    std::lock_guard<std::mutex> plan_guard(pl->cache_lock);
+    if (!pl->d_ops) {
+        HIP_TRY(dev_alloc(ctx, (void **)&pl->d_ops, sizeof(epgx_op) * pl->host.ops.size()));
+        HIP_TRY(hipMemcpyAsync(pl->d_ops, pl->host.ops.data(), sizeof(epgx_op) * pl->host.ops.size(), hipMemcpyHostToDevice, ctx->stream));
     }
-    if (name_out) {
-        snprintf(name_out, (size_t)name_bytes, "dxrun_kernel<%d, %d, %d>", NC, M, V);
-        return EPGX_OK;
+    if (with_dops && !pl->d_dops) {
+        HIP_TRY(dev_alloc(ctx, (void **)&pl->d_dops, sizeof(epgx_dop) * pl->host.dops.size()));
+        HIP_TRY(hipMemcpyAsync(pl->d_dops, pl->host.dops.data(), sizeof(epgx_dop) * pl->host.dops.size(), hipMemcpyHostToDevice, ctx->stream));
     }
-    if (has_adc && (!signal || signal_col0 < 0 || signal_col0 + nvox > signal_ld))
-        return fail(EPGX_ERR_INVALID, "epgx_run: range contains an ADC but the signal buffer is NULL or too narrow");
-    if (int rc = set_device(ctx)) return rc;
-    if (tracing()) fprintf(stderr, "[epgx] run: dxrun_kernel<%d, %d, %d> -- compartment groups and derivative states in registers\n", NC, M, V);
-    {
-        std::lock_guard<std::mutex> plan_guard(pl->cache_lock);
-        if (!pl->d_ops) {
-            HIP_TRY(dev_alloc(ctx, (void **)&pl->d_ops, sizeof(epgx_op) * pl->host.ops.size()));
-            HIP_TRY(hipMemcpyAsync(pl->d_ops, pl->host.ops.data(), sizeof(epgx_op) * pl->host.ops.size(), hipMemcpyHostToDevice, ctx->stream));
-        }
-        if (!pl->d_dops) {
-            HIP_TRY(dev_alloc(ctx, (void **)&pl->d_dops, sizeof(epgx_dop) * pl->host.dops.size()));
-            HIP_TRY(hipMemcpyAsync(pl->d_dops, pl->host.dops.data(), sizeof(epgx_dop) * pl->host.dops.size(), hipMemcpyHostToDevice, ctx->stream));
-        }
-    }
-    DXRunArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x.ops = pl->d_ops;
-    a.x.op_begin = op_begin;
-    a.x.op_end = op_end;
-    a.x.coef = pl->d_coef;
-    a.x.signal = signal ? (d2 *)signal + signal_col0 : nullptr;
-    a.x.signal_ld = signal_ld;
-    a.x.vox0 = vox0;
-    a.x.stride = pl->x_span / NC;
-    a.x.ndim = pl->ndim;
-    a.x.n_spaces = pl->host.n_spaces;
-    memcpy(a.x.shape, pl->shape, sizeof(a.x.shape));
-    memcpy(a.x.strides, pl->strides, sizeof(a.x.strides));
-    a.dops = pl->d_dops;
-    a.through_plain = (pl->deriv_flags & EPGX_DERIV_THROUGH_PLAIN_OPS) ? 1 : 0;
-    const int64_t ngroups = nvox / NC;
-    if (ngroups > 0x7fffffff) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: more than 2^31 compartment groups in one launch");
-    hipError_t e = hipErrorInvalidValue;
-    switch (NC) {
-    case 2: e = epgx_launch_dxrun_nc2(ctx->stream, a, ngroups, M, V); break;
-    case 3: e = epgx_launch_dxrun_nc3(ctx->stream, a, ngroups, M, V); break;
-    default: e = epgx_launch_dxrun_nc4(ctx->stream, a, ngroups, M, V); break;
-    }
-    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_run: dxrun_kernel launch failed: %s", hipGetErrorString(e));
     return EPGX_OK;
 }
 
-// A range that holds EPGX_OP_X: the records between two X run as pieces with the state in HBM (`out`, or a temporary state
-// when out is NULL), each X on exchange_kernel in between.  The voxel range must hold whole compartment groups.
-static int run_exchange_split(epgx_ctx *ctx, epgx_plan *pl, int32_t op_begin, int32_t op_end, int64_t vox0, int64_t nvox,
-                              const epgx_state *in, epgx_state *out, int32_t K, void *signal, int64_t signal_ld, int64_t signal_col0,
-                              char *name_out, int64_t name_bytes) {
-    if (pl->host.n_vars > 0)
-        return run_exchange_deriv(ctx, pl, op_begin, op_end, vox0, nvox, in, out, K, signal, signal_ld, signal_col0, name_out, name_bytes);
-    if (!supported_K(K))
-        return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: ranges with an exchange (EPGX_OP_X) keep the state in HBM: K = 64 .. 1024, not %d", K);
-    if (vox0 % pl->x_span || nvox % pl->x_span)
-        return fail(EPGX_ERR_INVALID, "epgx_run: voxel range [%lld,%lld) cuts compartment groups (blocks of %lld voxels)", (long long)vox0,
-                    (long long)(vox0 + nvox), (long long)pl->x_span);
-    // xrun_kernel: one wavefront per group, NC = 2 .. 4 compartments, K = 64 NC .. 256 with NC * K / 64 <= 8, no D / gather shifts
-    const int M = K / 64, NC = pl->x_ncomp;
-    bool fused = knobs().xrun && NC >= 2 && NC <= 4 && K <= 256 && NC * M <= 8;
-    bool has_adc = false;
-    for (int i = op_begin; i < op_end && fused; ++i) {
-        fused = pl->host.ops[i].opcode != EPGX_OP_D && pl->host.ops[i].opcode != EPGX_OP_GS;
-        has_adc = has_adc || pl->host.ops[i].opcode == EPGX_OP_ADC;
-    }
-    if (name_out) {
-        if (fused) snprintf(name_out, (size_t)name_bytes, "xrun_kernel<%d, %d, %s>", NC, M, in ? "true" : "false");
-        else snprintf(name_out, (size_t)name_bytes, "split<exchange_kernel>");
-        return EPGX_OK;
-    }
-    if (has_adc && (!signal || signal_col0 < 0 || signal_col0 + nvox > signal_ld))
-        return fail(EPGX_ERR_INVALID, "epgx_run: range contains an ADC but the signal buffer is NULL or too narrow");
-    if (int rc = set_device(ctx)) return rc;
-    if (fused) {
-        if (tracing()) fprintf(stderr, "[epgx] run: xrun_kernel<%d, %d, %s> -- compartment groups in registers\n", NC, M, in ? "true" : "false");
-        {
-            std::lock_guard<std::mutex> plan_guard(pl->cache_lock);
-            if (!pl->d_ops) {
-                HIP_TRY(dev_alloc(ctx, (void **)&pl->d_ops, sizeof(epgx_op) * pl->host.ops.size()));
-                HIP_TRY(hipMemcpyAsync(pl->d_ops, pl->host.ops.data(), sizeof(epgx_op) * pl->host.ops.size(), hipMemcpyHostToDevice, ctx->stream));
-            }
+static void fill_xrun(XRunArgs &a, const epgx_plan *pl, const RunCall &call, int NC) {
+    const epgx_state *in = call.in, *out = call.out;
+    a.ops = pl->d_ops;
+    a.op_begin = call.rq.op_begin;
+    a.op_end = call.rq.op_end;
+    a.coef = pl->d_coef;
+    a.in = in ? in->data : nullptr;
+    a.dens_in = in ? in->dens : nullptr;
+    a.out = out ? out->data : nullptr;
+    a.dens_out = out ? out->dens : nullptr;
+    a.signal = call.signal_col();
+    a.signal_ld = call.rq.signal_ld;
+    a.vox0 = call.rq.vox0;
+    a.stride = pl->x_span / NC;
+    a.ndim = pl->ndim;
+    a.n_spaces = pl->host.n_spaces;
+    memcpy(a.shape, pl->shape, sizeof(a.shape));
+    memcpy(a.strides, pl->strides, sizeof(a.strides));
+}
+
+// ROUTE_XRUN / ROUTE_DXRUN: ONE launch of xrun_kernel<NC, M, HAS_IN> or -- a plan with derivative states, from equilibrium --
+// dxrun_kernel<NC, M, V>, the compartment groups (and derivative states) in registers
+static int run_exchange_fused(epgx_ctx *ctx, epgx_plan *pl, const RunCall &call, const RunDecision &d) {
+    const bool deriv = d.route == ROUTE_DXRUN;
+    const int NC = d.NC, M = d.M, V = d.V;
+    if (tracing())
+        fprintf(stderr, "[epgx] run: %s -- compartment groups %sin registers\n", d.name, deriv ? "and derivative states " : "");
+    if (int rc = ensure_dev_ops(ctx, pl, deriv)) return rc;
+    DXRunArgs a;
+    memset(&a, 0, sizeof(a));
+    fill_xrun(a.x, pl, call, NC);
+    a.dops = pl->d_dops;
+    a.through_plain = (pl->deriv_flags & EPGX_DERIV_THROUGH_PLAIN_OPS) ? 1 : 0;
+    const int64_t ngroups = call.rq.nvox / NC;
+    if (ngroups > 0x7fffffff) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: more than 2^31 compartment groups in one launch");
+    hipError_t e = hipErrorInvalidValue;
+    if (deriv) switch (NC) {
+        case 2: e = epgx_launch_dxrun_nc2(ctx->stream, a, ngroups, M, V); break;
+        case 3: e = epgx_launch_dxrun_nc3(ctx->stream, a, ngroups, M, V); break;
+        default: e = epgx_launch_dxrun_nc4(ctx->stream, a, ngroups, M, V); break;
         }
-        XRunArgs a;
-        memset(&a, 0, sizeof(a));
-        a.ops = pl->d_ops;
-        a.op_begin = op_begin;
-        a.op_end = op_end;
-        a.coef = pl->d_coef;
-        a.in = in ? in->data : nullptr;
-        a.dens_in = in ? in->dens : nullptr;
-        a.out = out ? out->data : nullptr;
-        a.dens_out = out ? out->dens : nullptr;
-        a.signal = signal ? (d2 *)signal + signal_col0 : nullptr;
-        a.signal_ld = signal_ld;
-        a.vox0 = vox0;
-        a.stride = pl->x_span / NC;
-        a.ndim = pl->ndim;
-        a.n_spaces = pl->host.n_spaces;
-        memcpy(a.shape, pl->shape, sizeof(a.shape));
-        memcpy(a.strides, pl->strides, sizeof(a.strides));
-        const int64_t ngroups = nvox / NC;
-        if (ngroups > 0x7fffffff) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: more than 2^31 compartment groups in one launch");
-        hipError_t e = hipErrorInvalidValue;
-        switch (NC) {
-        case 2: e = epgx_launch_xrun_nc2(ctx->stream, a, ngroups, M); break;
-        case 3: e = epgx_launch_xrun_nc3(ctx->stream, a, ngroups, M); break;
-        default: e = epgx_launch_xrun_nc4(ctx->stream, a, ngroups, M); break;
+    else switch (NC) {
+        case 2: e = epgx_launch_xrun_nc2(ctx->stream, a.x, ngroups, M); break;
+        case 3: e = epgx_launch_xrun_nc3(ctx->stream, a.x, ngroups, M); break;
+        default: e = epgx_launch_xrun_nc4(ctx->stream, a.x, ngroups, M); break;
         }
-        if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_run: xrun_kernel launch failed: %s", hipGetErrorString(e));
-        return EPGX_OK;
-    }
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_run: %s launch failed: %s", deriv ? "dxrun_kernel" : "xrun_kernel", hipGetErrorString(e));
+    return EPGX_OK;
+}
+
+static int run_records(epgx_ctx *ctx, epgx_plan *pl, const RunCall &call, int K);
+
+// ROUTE_XSPLIT: the records between two X run as pieces with the state in HBM (`out`, or a temporary state when out is NULL),
+// each X on exchange_kernel in between.  (A piece is a part of a range run analysis has accepted: it goes to its records.)
+static int run_exchange_split(epgx_ctx *ctx, epgx_plan *pl, const RunCall &call, int K) {
+    const int32_t op_begin = call.rq.op_begin, op_end = call.rq.op_end;
+    const int64_t vox0 = call.rq.vox0, nvox = call.rq.nvox;
+    const epgx_state *in = call.in;
+    epgx_state *out = call.out;
     if (tracing()) fprintf(stderr, "[epgx] run: split<exchange_kernel> -- records between exchanges on the per-timestep kernels\n");
     epgx_state *tmp = nullptr;
     epgx_state *work = out;
@@ -1971,7 +1932,10 @@ static int run_exchange_split(epgx_ctx *ctx, epgx_plan *pl, int32_t op_begin, in
     for (int i = op_begin; i <= op_end && !rc; ++i) {
         if (i < op_end && pl->host.ops[i].opcode != EPGX_OP_X) continue;
         if (i > begin) {
-            rc = run_or_name(ctx, pl, begin, i, vox0, nvox, src, work, K, signal, signal_ld, signal_col0, nullptr, 0);
+            RunCall piece = call;
+            piece.rq.op_begin = begin, piece.rq.op_end = i;
+            piece.in = src, piece.out = work;
+            rc = run_records(ctx, pl, piece, K);
             src = work;
         }
         if (rc || i == op_end) break;
@@ -1995,173 +1959,125 @@ static int run_exchange_split(epgx_ctx *ctx, epgx_plan *pl, int32_t op_begin, in
 
 // The kernel instantiations live in separate translation units (epgx_inst.hip compiled once per
 // M, epgx_deriv.hip ...) so that they build in parallel; see epgx_launch.h.
-// epgx_run, and (name_out != NULL) epgx_kernel_for: the same checks and the same decision, no launch
-static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin, int32_t op_end, int64_t vox0, int64_t nvox,
-                       const epgx_state *in, epgx_state *out, int32_t K, void *signal, int64_t signal_ld, int64_t signal_col0,
-                       char *name_out, int64_t name_bytes) {
-    epgx_plan *pl = const_cast<epgx_plan *>(plan_c);
-    if (!ctx || !pl) return fail(EPGX_ERR_INVALID, "epgx_run: NULL argument");
-    if (pl->ctx != ctx) return fail(EPGX_ERR_INVALID, "epgx_run: plan belongs to another context");
-    const int n_ops = (int)pl->host.ops.size();
-    if (op_begin < 0 || op_end > n_ops || op_begin > op_end)
-        return fail(EPGX_ERR_INVALID, "epgx_run: operator range [%d,%d) outside [0,%d)", op_begin, op_end, n_ops);
-    if (nvox > (int64_t)4 * 0x7fffffff) return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: more than 2^33 voxels in one launch");
-    if (nvox < 0 || vox0 < 0 || vox0 + nvox > pl->nvox_total)
-        return fail(EPGX_ERR_INVALID, "epgx_run: voxel range [%lld,%lld) outside the grid (%lld voxels)",
-                    (long long)vox0, (long long)(vox0 + nvox), (long long)pl->nvox_total);
-    if (in && in->ctx != ctx) return fail(EPGX_ERR_INVALID, "epgx_run: `in` belongs to another context");
-    if (out && out->ctx != ctx) return fail(EPGX_ERR_INVALID, "epgx_run: `out` belongs to another context");
-    if (in) K = in->K;
-    if (out) {
-        if (in && out->K != in->K)
-            return fail(EPGX_ERR_INVALID, "epgx_run: in/out capacities differ (%d vs %d)", in->K, out->K);
-        K = out->K;
-    }
-    // K = 16: four voxels per wavefront (epgx_packed_kernels.hip.h), state-resident launches only
-    const bool packed16 = (K == 16 || K == 32);
-    if (packed16 && (in || out))
-        return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: K = 16 / 32 keep no state in HBM: in and out must be NULL");
-    // K = 2048: state-resident from equilibrium only (four wavefronts per voxel; a state matrix of that size has no HBM form)
-    const bool wide = K == 2048 && !in && !out;
-    if (!packed16 && !wide && !supported_K(K))
-        return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: K=%d not one of 16, 32, 2048 (state-resident only), 64, 128, 256, 512, 1024", K);
-    if (in && in->nvox != nvox)
-        return fail(EPGX_ERR_INVALID, "epgx_run: `in` holds %lld voxels, range has %lld", (long long)in->nvox,
-                    (long long)nvox);
-    if (out && out->nvox != nvox)
-        return fail(EPGX_ERR_INVALID, "epgx_run: `out` holds %lld voxels, range has %lld", (long long)out->nvox,
-                    (long long)nvox);
-    if (nvox == 0 || op_begin == op_end) {
-        if (name_out) snprintf(name_out, (size_t)name_bytes, "none");
-        return EPGX_OK;
-    }
 
-    for (int i = op_begin; i < op_end; ++i) {
-        const epgx_op &op = pl->host.ops[i];
-        if (op.opcode == EPGX_OP_S && std::abs(op.ia) >= K)
-            return fail(EPGX_ERR_INVALID, "epgx_run: operator %d shifts by %d, capacity K=%d", i, op.ia, K);
-        if (packed16 && (op.opcode == EPGX_OP_MAT || op.opcode == EPGX_OP_MAT0))
-            return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: K = 16 / 32 do not handle general matrices (operator %d)", i);
-        if (K == 32 && (op.opcode == EPGX_OP_D || op.opcode == EPGX_OP_GS))
-            return fail(EPGX_ERR_UNSUPPORTED, "epgx_run: diffusion and gather shifts run with K = 16 or K >= 64 (operator %d)", i);
-        if (op.opcode == EPGX_OP_D && op.ncoef != 3 * K)
-            return fail(EPGX_ERR_INVALID, "epgx_run: operator %d: D table has %d doubles per entry, need 3*K=%d", i,
-                        op.ncoef, 3 * K);
-        if (op.opcode == EPGX_OP_GS) {
-            if (2 * op.ncoef != 3 * K)
-                return fail(EPGX_ERR_INVALID, "epgx_run: operator %d: gather table has %d entries, need 3*K=%d", i,
-                            2 * op.ncoef, 3 * K);
-            for (int32_t v : pl->host.gather_tables[i])
-                if (v != -1 && ((v & ~(1 << 30)) < 0 || (v & ~(1 << 30)) >= K))
-                    return fail(EPGX_ERR_INVALID, "epgx_run: operator %d: gather index %d outside [0,%d)", i, v, K);
-        }
-    }
-    for (int i = op_begin; i < op_end; ++i)
-        if (pl->host.ops[i].opcode == EPGX_OP_X)
-            return run_exchange_split(ctx, pl, op_begin, op_end, vox0, nvox, in, out, K, signal, signal_ld, signal_col0, name_out,
-                                      name_bytes);
-    if (int rc = set_device(ctx)) return rc;
-    // from here to the launch the plan's caches (packed records, table indices of the voxel range) are read and
-    // possibly rebuilt: one host thread at a time per plan (the launch itself is asynchronous)
-    std::lock_guard<std::mutex> plan_guard(pl->cache_lock);
-    const PackedRange *pr = nullptr;
-    if (int rc = get_packed(pl, op_begin, op_end, K, &pr)) return rc;
-    if (pr->lists.has_adc && !name_out) {
-        if (!signal) return fail(EPGX_ERR_INVALID, "epgx_run: range contains an ADC but signal is NULL");
-        if (signal_col0 < 0 || signal_col0 + nvox > signal_ld)
-            return fail(EPGX_ERR_INVALID, "epgx_run: signal columns [%lld,%lld) exceed signal_ld=%lld",
-                        (long long)signal_col0, (long long)(signal_col0 + nvox), (long long)signal_ld);
-    }
-    if (pr->lists.n_rec == 0) {  // nothing but NOPs: only a state copy may be needed
-        if (name_out) {
-            snprintf(name_out, (size_t)name_bytes, "none");
-            return EPGX_OK;
-        }
-        if (out && in && out != in) return epgx_state_copy(out, in);
-        return EPGX_OK;
-    }
+// the records route of a derivative plan: DerivArgs and the launch of the family `c` names
+static hipError_t launch_deriv(epgx_ctx *ctx, const epgx_plan *pl, const RunCall &call, int K, const PackedRange *pr, const Choice &c) {
     const RangeLists &rl = pr->lists;
-    Choice c;
-    if (int rc = choose_kernel(pl->host, rl, op_begin, op_end, K, in != nullptr, out != nullptr, knobs(), &c)) return rc;
-    if (name_out) {   // epgx_kernel_for: the decision, no launch
-        snprintf(name_out, (size_t)name_bytes, "%s", c.name);
-        return EPGX_OK;
-    }
-    if (tracing()) fprintf(stderr, "[epgx] run: %s -- %s\n", c.name, c.why);
-    if (int rc = ensure_vidx(pl, vox0, nvox)) return rc;
-
+    const epgx_state *in = call.in;
     hipError_t e = hipSuccess;
-    if (pl->host.n_vars > 0) {
-        DerivArgs da;
-        memset(&da, 0, sizeof(da));
-        da.nvox = nvox;
-        da.in = in ? in->data : nullptr;
-        da.dens_in = in ? in->dens : nullptr;
-        da.recs = pr->recs(DEV_RECS);
-        da.drecs = (const DRec *)pr->dev[DEV_DRECS];
-        da.coef = pl->d_coef;
-        da.signal = signal ? (d2 *)signal + signal_col0 : nullptr;
-        da.signal_ld = signal_ld;
-        da.t.vidx = pl->d_vidx;
-        da.t.vidx_ld = pl->vidx_nvox;
-        da.t.vox0 = vox0;
-        da.t.n_rec = rl.n_rec;
-        da.t.dense_spaces = pl->dense_spaces;
-        da.t.use_lds = c.lds_mode;
-        da.through_plain = (pl->deriv_flags & EPGX_DERIV_THROUGH_PLAIN_OPS) ? 1 : 0;
-        da.contig = c.contig ? 1 : 0;
-        if (c.family == FAM_DRUN && knobs().grow) {   // (0, 0: four orders per lane throughout; EPGX_GROW=0, measurements)
-            da.grow1 = rl.dgrow1;
-            da.grow2 = rl.dgrow2;
-        }
-        if (c.family == FAM_PACKED_DFOLD || c.family == FAM_DRUN) {   // the records with run headers (and E_b's logarithmic partials)
-            da.recs = pr->recs(DEV_DRUNS);
-            da.drecs = (const DRec *)pr->dev[DEV_DDRUNS];
-            da.drecs_b = (const DRecB *)pr->dev[DEV_BDRUNS];
-            da.t.n_rec = rl.n_druns;
-            // (these kernels exist for 1 and 4 index spaces: a space the plan does not have counts as dense -- no index row is read for it)
-            da.t.dense_spaces |= 0xfu & ~((1u << pl->host.n_spaces) - 1u);
-            if (tracing())
-                fprintf(stderr, "[epgx] run: %d records with headers (%d unfolded); %d runs (%d of one repeated record) hold %d records; [0, %d) "
-                                "with one order per lane, [%d, %d) with two\n",
-                        rl.n_druns, rl.n_rec, rl.drun_headers, rl.drun_ident, rl.drun_inside, da.grow1, da.grow1, da.grow2);
-        }
-        switch (c.family) {
-        case FAM_HESS: e = epgx_launch_hess(ctx->stream, da, K, pl->host.n_spaces, pl->host.n_vars == 2); break;
-        case FAM_PACKED_DFOLD: e = epgx_launch_packed_dfold(ctx->stream, da, K, pl->host.n_vars); break;
-        case FAM_DRUN:
-            if (c.split3) {
-                // three derivative states of folded runs: the last variable alone (rows shifted by two), then the first two over it
-                DerivArgs last = da;
-                last.signal = da.signal ? da.signal + 2 * da.signal_ld : nullptr;
-                e = epgx_launch_drun(ctx->stream, last, K, pl->host.n_spaces, 1, rl.drun_code | (int)DRUN_LAST);
-                if (e == hipSuccess) e = epgx_launch_drun(ctx->stream, da, K, pl->host.n_spaces, 2, rl.drun_code);
-            } else
-                e = epgx_launch_drun(ctx->stream, da, K, pl->host.n_spaces, pl->host.n_vars, rl.drun_code);
-            break;
-        case FAM_ROWS_DERIV:
-            if (pl->host.n_vars == 2) {
-                switch (pl->host.n_spaces) {
-                case 0: e = epgx_launch_rows_deriv_v2_nsp0(ctx->stream, da, K); break;
-                case 1: e = epgx_launch_rows_deriv_v2_nsp1(ctx->stream, da, K); break;
-                case 2: e = epgx_launch_rows_deriv_v2_nsp2(ctx->stream, da, K); break;
-                default: e = epgx_launch_rows_deriv_v2_nsp4(ctx->stream, da, K); break;
-                }
-            } else {
-                switch (pl->host.n_spaces) {
-                case 0: e = epgx_launch_rows_deriv_nsp0(ctx->stream, da, K); break;
-                case 1: e = epgx_launch_rows_deriv_nsp1(ctx->stream, da, K); break;
-                case 2: e = epgx_launch_rows_deriv_nsp2(ctx->stream, da, K); break;
-                default: e = epgx_launch_rows_deriv_nsp4(ctx->stream, da, K); break;
-                }
-            }
-            break;
-        case FAM_PACKED_DERIV: e = epgx_launch_packed_deriv(ctx->stream, da, K, pl->host.n_spaces, pl->host.n_vars); break;
-        default: e = epgx_launch_deriv(ctx->stream, da, K, pl->host.n_spaces, pl->host.n_vars); break;
-        }
-        if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_run: launch failed: %s", hipGetErrorString(e));
-        return EPGX_OK;
+    DerivArgs da;
+    memset(&da, 0, sizeof(da));
+    da.nvox = call.rq.nvox;
+    da.in = in ? in->data : nullptr;
+    da.dens_in = in ? in->dens : nullptr;
+    da.recs = pr->recs(DEV_RECS);
+    da.drecs = (const DRec *)pr->dev[DEV_DRECS];
+    da.coef = pl->d_coef;
+    da.signal = call.signal_col();
+    da.signal_ld = call.rq.signal_ld;
+    da.t.vidx = pl->d_vidx;
+    da.t.vidx_ld = pl->vidx_nvox;
+    da.t.vox0 = call.rq.vox0;
+    da.t.n_rec = rl.n_rec;
+    da.t.dense_spaces = pl->dense_spaces;
+    da.t.use_lds = c.lds_mode;
+    da.through_plain = (pl->deriv_flags & EPGX_DERIV_THROUGH_PLAIN_OPS) ? 1 : 0;
+    da.contig = c.contig ? 1 : 0;
+    if (c.family == FAM_DRUN && knobs().grow) {   // (0, 0: four orders per lane throughout; EPGX_GROW=0, measurements)
+        da.grow1 = rl.dgrow1;
+        da.grow2 = rl.dgrow2;
     }
+    if (c.family == FAM_PACKED_DFOLD || c.family == FAM_DRUN) {   // the records with run headers (and E_b's logarithmic partials)
+        da.recs = pr->recs(DEV_DRUNS);
+        da.drecs = (const DRec *)pr->dev[DEV_DDRUNS];
+        da.drecs_b = (const DRecB *)pr->dev[DEV_BDRUNS];
+        da.t.n_rec = rl.n_druns;
+        // (these kernels exist for 1 and 4 index spaces: a space the plan does not have counts as dense -- no index row is read for it)
+        da.t.dense_spaces |= 0xfu & ~((1u << pl->host.n_spaces) - 1u);
+        if (tracing())
+            fprintf(stderr, "[epgx] run: %d records with headers (%d unfolded); %d runs (%d of one repeated record) hold %d records; [0, %d) "
+                            "with one order per lane, [%d, %d) with two\n",
+                    rl.n_druns, rl.n_rec, rl.drun_headers, rl.drun_ident, rl.drun_inside, da.grow1, da.grow1, da.grow2);
+    }
+    switch (c.family) {
+    case FAM_HESS: e = epgx_launch_hess(ctx->stream, da, K, pl->host.n_spaces, pl->host.n_vars == 2); break;
+    case FAM_PACKED_DFOLD: e = epgx_launch_packed_dfold(ctx->stream, da, K, pl->host.n_vars); break;
+    case FAM_DRUN:
+        if (c.split3) {
+            // three derivative states of folded runs: the last variable alone (rows shifted by two), then the first two over it
+            DerivArgs last = da;
+            last.signal = da.signal ? da.signal + 2 * da.signal_ld : nullptr;
+            e = epgx_launch_drun(ctx->stream, last, K, pl->host.n_spaces, 1, rl.drun_code | (int)DRUN_LAST);
+            if (e == hipSuccess) e = epgx_launch_drun(ctx->stream, da, K, pl->host.n_spaces, 2, rl.drun_code);
+        } else
+            e = epgx_launch_drun(ctx->stream, da, K, pl->host.n_spaces, pl->host.n_vars, rl.drun_code);
+        break;
+    case FAM_ROWS_DERIV:
+        if (pl->host.n_vars == 2) {
+            switch (pl->host.n_spaces) {
+            case 0: e = epgx_launch_rows_deriv_v2_nsp0(ctx->stream, da, K); break;
+            case 1: e = epgx_launch_rows_deriv_v2_nsp1(ctx->stream, da, K); break;
+            case 2: e = epgx_launch_rows_deriv_v2_nsp2(ctx->stream, da, K); break;
+            default: e = epgx_launch_rows_deriv_v2_nsp4(ctx->stream, da, K); break;
+            }
+        } else {
+            switch (pl->host.n_spaces) {
+            case 0: e = epgx_launch_rows_deriv_nsp0(ctx->stream, da, K); break;
+            case 1: e = epgx_launch_rows_deriv_nsp1(ctx->stream, da, K); break;
+            case 2: e = epgx_launch_rows_deriv_nsp2(ctx->stream, da, K); break;
+            default: e = epgx_launch_rows_deriv_nsp4(ctx->stream, da, K); break;
+            }
+        }
+        break;
+    case FAM_PACKED_DERIV: e = epgx_launch_packed_deriv(ctx->stream, da, K, pl->host.n_spaces, pl->host.n_vars); break;
+    default: e = epgx_launch_deriv(ctx->stream, da, K, pl->host.n_spaces, pl->host.n_vars); break;
+    }
+    return e;
+}
+
+// K = 2048 in two legs per slab of voxels: records [0, j1) on one wavefront per voxel at 512 orders (run_kernel<8, ..>: the growing
+// kernel cannot hand its state on -- epgx_cgrow.hip), its state [3][512] + density through a scratch buffer (24 KiB per voxel:
+// slabs of at most 8 GiB), then the records [j1, n_rec) on four wavefronts per voxel
+static hipError_t launch_two_legs(epgx_ctx *ctx, const epgx_plan *pl, const RunArgs &a, const RangeLists &rl) {
+    const int64_t nvox = a.nvox, vox0 = a.t.vox0;
+    const int j1 = rl.cgrow[3], j2 = rl.cgrow[4], j3 = rl.cgrow[5];
+    const int64_t per_voxel = (int64_t)3 * 512 * sizeof(d2) + sizeof(double);
+    const int64_t slab = slab_voxels(nvox, per_voxel, knobs().slab_voxels, 0);
+    void *scratch = nullptr;
+    hipError_t e = dev_alloc(ctx, &scratch, (size_t)(slab * per_voxel));
+    if (e != hipSuccess) return e;
+    d2 *st = (d2 *)scratch;
+    double *dn = (double *)((char *)scratch + slab * 3 * 512 * sizeof(d2));
+    if (tracing())
+        fprintf(stderr, "[epgx] run: %d records: [0, %d) on one wavefront per voxel, the rest on four (parts 2 and 3 join at %d and %d); slabs of "
+                        "%lld voxels\n", rl.n_rec, j1, j2, j3, (long long)slab);
+    for (int64_t c0 = 0; c0 < nvox && e == hipSuccess; c0 += slab) {
+        RunArgs s = a;
+        s.nvox = std::min(slab, nvox - c0);
+        s.t.vox0 = vox0 + c0;
+        if (s.t.vidx) s.t.vidx += c0;
+        if (s.signal) s.signal += c0;
+        if (s.dens_in) s.dens_in += c0;
+        RunArgs leg = s;      // the first leg: the per-timestep kernel at 512 orders over the records [0, j1), its state to the scratch buffer
+        leg.t.n_rec = j1;
+        leg.t.prefetch = std::min(leg.t.prefetch, j1);
+        leg.out = st;
+        leg.t.dens_out = dn;
+        leg.t.write_dens = 1;
+        e = epgx_launch_run_m8(ctx->stream, leg, pl->host.n_spaces);
+        if (e == hipSuccess && j1 < rl.n_rec)
+            e = epgx_launch_run_split2048(ctx->stream, s, pl->host.n_spaces, st, dn, j1, j2, j3, rl.first_slot + rl.cgrow_adc3);
+    }
+    dev_free(ctx, scratch);
+    return e;
+}
+
+// the records route of a plain plan: RunArgs and the launch of the family `c` names
+static hipError_t launch_plain(epgx_ctx *ctx, const epgx_plan *pl, const RunCall &call, int K, const PackedRange *pr, const Choice &c) {
+    const RangeLists &rl = pr->lists;
+    const epgx_state *in = call.in, *out = call.out;
+    const int64_t nvox = call.rq.nvox, vox0 = call.rq.vox0;
+    hipError_t e = hipSuccess;
     RunArgs a;
     memset(&a, 0, sizeof(a));
     a.recs = pr->recs(DEV_RECS);
@@ -2174,8 +2090,8 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
     a.out = out ? out->data : nullptr;
     a.dens_in = in ? in->dens : nullptr;
     a.t.dens_out = out ? out->dens : nullptr;
-    a.signal = signal ? (d2 *)signal + signal_col0 : nullptr;
-    a.signal_ld = signal_ld;
+    a.signal = call.signal_col();
+    a.signal_ld = call.rq.signal_ld;
     a.t.use_lds = c.lds_mode;
     a.t.seq_slots = rl.seq_slots ? 1 : 0;
     a.t.first_slot = rl.first_slot;
@@ -2211,45 +2127,8 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
         }
         break;
     case FAM_RUN_SPLIT:
-        if (!c.split_grow) {
-            e = epgx_launch_run_split2048(ctx->stream, a, pl->host.n_spaces, nullptr, nullptr, 0, 0, 0, 0);
-            break;
-        }
-        {
-            // two legs per slab of voxels: records [0, j1) on one wavefront per voxel at 512 orders (run_kernel<8, ..>: the growing kernel
-            // cannot hand its state on -- epgx_cgrow.hip), its state [3][512] + density through a scratch buffer (24 KiB per voxel: slabs
-            // of at most 8 GiB), then the records [j1, n_rec) on four wavefronts per voxel
-            const int j1 = rl.cgrow[3], j2 = rl.cgrow[4], j3 = rl.cgrow[5];
-            const int64_t per_voxel = (int64_t)3 * 512 * sizeof(d2) + sizeof(double);
-            int64_t slab = std::min<int64_t>((nvox + 3) & ~(int64_t)3, std::max<int64_t>(4, (((int64_t)8 << 30) / per_voxel) & ~(int64_t)3));
-            if (knobs().slab_voxels > 0) slab = std::min<int64_t>(slab, (knobs().slab_voxels + 3) & ~3);
-            void *scratch = nullptr;
-            e = dev_alloc(ctx, &scratch, (size_t)(slab * per_voxel));
-            if (e != hipSuccess) break;
-            d2 *st = (d2 *)scratch;
-            double *dn = (double *)((char *)scratch + slab * 3 * 512 * sizeof(d2));
-            if (tracing())
-                fprintf(stderr, "[epgx] run: %d records: [0, %d) on one wavefront per voxel, the rest on four (parts 2 and 3 join at %d and %d); slabs of "
-                                "%lld voxels\n", rl.n_rec, j1, j2, j3, (long long)slab);
-            for (int64_t c0 = 0; c0 < nvox && e == hipSuccess; c0 += slab) {
-                RunArgs s = a;
-                s.nvox = std::min(slab, nvox - c0);
-                s.t.vox0 = vox0 + c0;
-                if (s.t.vidx) s.t.vidx += c0;
-                if (s.signal) s.signal += c0;
-                if (s.dens_in) s.dens_in += c0;
-                RunArgs leg = s;      // the first leg: the per-timestep kernel at 512 orders over the records [0, j1), its state to the scratch buffer
-                leg.t.n_rec = j1;
-                leg.t.prefetch = std::min(leg.t.prefetch, j1);
-                leg.out = st;
-                leg.t.dens_out = dn;
-                leg.t.write_dens = 1;
-                e = epgx_launch_run_m8(ctx->stream, leg, pl->host.n_spaces);
-                if (e == hipSuccess && j1 < rl.n_rec)
-                    e = epgx_launch_run_split2048(ctx->stream, s, pl->host.n_spaces, st, dn, j1, j2, j3, rl.first_slot + rl.cgrow_adc3);
-            }
-            dev_free(ctx, scratch);
-        }
+        if (c.split_grow) e = launch_two_legs(ctx, pl, a, rl);
+        else e = epgx_launch_run_split2048(ctx->stream, a, pl->host.n_spaces, nullptr, nullptr, 0, 0, 0, 0);
         break;
     case FAM_RUN_CONTIG: e = epgx_launch_run_contig(ctx->stream, a, K, pl->host.n_spaces); break;
     case FAM_RUN_CONTIG_GROW:
@@ -2271,62 +2150,98 @@ static int run_or_name(epgx_ctx *ctx, const epgx_plan *plan_c, int32_t op_begin,
         }
         break;
     }
+    return e;
+}
+
+// ROUTE_RECORDS up to the decision, for epgx_run and epgx_kernel_for alike: the lists of the range (cached, or built and uploaded),
+// room for its probes, the kernel.  The caller holds pl->cache_lock.  Nothing but NOPs: no records, and the name is "none"
+static int plan_records(epgx_plan *pl, const RunCall &call, int K, const PackedRange **pr, Choice *c) {
+    const RunRequest &rq = call.rq;
+    if (int rc = get_packed(pl, rq.op_begin, rq.op_end, K, pr)) return rc;
+    if ((*pr)->lists.has_adc)
+        if (int rc = signal_room(rq, false)) return rc;
+    if ((*pr)->lists.n_rec == 0) {
+        snprintf(c->name, sizeof(c->name), "none");
+        return EPGX_OK;
+    }
+    return choose_kernel(pl->host, (*pr)->lists, rq.op_begin, rq.op_end, K, call.in != nullptr, call.out != nullptr, knobs(), c);
+}
+
+// ROUTE_RECORDS, and every piece of the split path
+static int run_records(epgx_ctx *ctx, epgx_plan *pl, const RunCall &call, int K) {
+    if (int rc = set_device(ctx)) return rc;
+    // from here to the launch the plan's caches (packed records, table indices of the voxel range) are read and
+    // possibly rebuilt: one host thread at a time per plan (the launch itself is asynchronous)
+    std::lock_guard<std::mutex> plan_guard(pl->cache_lock);
+    const PackedRange *pr = nullptr;
+    Choice c;
+    if (int rc = plan_records(pl, call, K, &pr, &c)) return rc;
+    if (pr->lists.n_rec == 0) {  // only a state copy may be needed
+        if (call.out && call.in && call.out != call.in) return epgx_state_copy(call.out, call.in);
+        return EPGX_OK;
+    }
+    if (tracing()) fprintf(stderr, "[epgx] run: %s -- %s\n", c.name, c.why);
+    if (int rc = ensure_vidx(pl, call.rq.vox0, call.rq.nvox)) return rc;
+    const hipError_t e = pl->host.n_vars > 0 ? launch_deriv(ctx, pl, call, K, pr, c) : launch_plain(ctx, pl, call, K, pr, c);
     if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_run: launch failed: %s", hipGetErrorString(e));
     return EPGX_OK;
 }
 
 extern "C" int epgx_run(epgx_ctx *ctx, const epgx_plan *plan, int32_t op_begin, int32_t op_end, int64_t vox0, int64_t nvox,
                         const epgx_state *in, epgx_state *out, int32_t K, void *signal, int64_t signal_ld, int64_t signal_col0) {
-    return run_or_name(ctx, plan, op_begin, op_end, vox0, nvox, in, out, K, signal, signal_ld, signal_col0, nullptr, 0);
+    const RunCall call = run_call(ctx, op_begin, op_end, vox0, nvox, in, out, K, signal, signal_ld, signal_col0, false);
+    RunDecision d;
+    if (int rc = analyse_call(ctx, plan, call, &d)) return rc;
+    epgx_plan *pl = const_cast<epgx_plan *>(plan);
+    switch (d.route) {
+    case ROUTE_NONE: return EPGX_OK;
+    case ROUTE_RECORDS: return run_records(ctx, pl, call, d.K);
+    default: break;
+    }
+    if (int rc = set_device(ctx)) return rc;
+    return d.route == ROUTE_XSPLIT ? run_exchange_split(ctx, pl, call, d.K) : run_exchange_fused(ctx, pl, call, d);
 }
 
+// the same two steps as epgx_run, then the name instead of the launch (the records route: through get_packed and choose_kernel)
 extern "C" int epgx_kernel_for(epgx_ctx *ctx, const epgx_plan *plan, int32_t op_begin, int32_t op_end, int32_t K, const epgx_state *in,
                                epgx_state *out, char *name_out, int64_t name_bytes) {
     if (!name_out || name_bytes < 2) return fail(EPGX_ERR_INVALID, "epgx_kernel_for: no room for the name");
     if (!ctx || !plan) return fail(EPGX_ERR_INVALID, "epgx_kernel_for: NULL argument");
     const int64_t nvox = in ? in->nvox : (out ? out->nvox : plan->nvox_total);
-    return run_or_name(ctx, plan, op_begin, op_end, 0, nvox, in, out, K, nullptr, 0, 0, name_out, name_bytes);
+    const RunCall call = run_call(ctx, op_begin, op_end, 0, nvox, in, out, K, nullptr, 0, 0, true);
+    RunDecision d;
+    if (int rc = analyse_call(ctx, plan, call, &d)) return rc;
+    const char *name = d.name;
+    Choice c;
+    if (d.route == ROUTE_RECORDS) {
+        epgx_plan *pl = const_cast<epgx_plan *>(plan);
+        if (int rc = set_device(ctx)) return rc;
+        std::lock_guard<std::mutex> plan_guard(pl->cache_lock);
+        const PackedRange *pr = nullptr;
+        if (int rc = plan_records(pl, call, d.K, &pr, &c)) return rc;
+        name = c.name;
+    }
+    snprintf(name_out, (size_t)name_bytes, "%s", name);
+    return EPGX_OK;
 }
 
 // ------------------------------------------------------------------------------ tiled runs: state matrices of any length
 // (epgx_tiled.hip; the schedule -- blocks and shift steps -- comes from tiled_schedule, epgx_planner.cpp)
 
-static void tiled_knobs(int &M, int &H) {   // EPGX_TILED_M=16: 16 orders per lane, halo 64 (measurements)
-    static const int m = env_int("EPGX_TILED_M", 8);
-    M = m == 16 ? 16 : 8;
-    H = M == 16 ? 64 : 32;
-}
-
-
-static constexpr int TILED_DERIV_V = 2;      // derivative states one launch of tiled_deriv_kernel<8, 32, NSP, V> carries (_lib.py TILED_DERIV_V)
-
-static int tiled_check(epgx_ctx *ctx, const epgx_plan *pl, int32_t Kbuf, const char *who, bool deriv = false) {
+// the handles, then analyse_tiled (epgx_run_check.h): `rq` for a run, NULL and `top0` for an info call
+static int tiled_analysis(const char *who, bool deriv, const epgx_ctx *ctx, const epgx_plan *pl, int32_t Kbuf, const TiledRequest *rq, int32_t top0,
+                          TiledShape *shape) {
+    static const int tiled_m = env_int("EPGX_TILED_M", 8);   // 16: 16 orders per lane, halo 64 (measurements)
     if (!ctx || !pl) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
     if (pl->ctx != ctx) return fail(EPGX_ERR_INVALID, "%s: plan belongs to another context", who);
-    if (Kbuf < 64 || Kbuf % 64 != 0 || Kbuf > (1 << 24)) return fail(EPGX_ERR_INVALID, "%s: Kbuf=%d is not a multiple of 64 in [64, 2^24]", who, Kbuf);
-    if (!deriv && pl->host.n_vars > 0)
-        return fail(EPGX_ERR_UNSUPPORTED, "%s: plans with derivative states run at K <= 1024 (epgx_run)", who);
-    if (deriv) {
-        if (pl->host.second)
-            return fail(EPGX_ERR_UNSUPPORTED, "%s: second-order plans (EPGX_DERIV_SECOND) run at K <= 512 (epgx_run)", who);
-        if (pl->host.n_vars < 1 || pl->host.n_vars > TILED_DERIV_V)
-            return fail(EPGX_ERR_UNSUPPORTED, "%s: the plan has %d derivative states, a launch carries 1 .. %d", who, pl->host.n_vars, TILED_DERIV_V);
-    }
-    for (size_t i = 0; i < pl->host.ops.size(); ++i) {
-        const int oc = pl->host.ops[i].opcode;
-        if (oc == EPGX_OP_X || oc == EPGX_OP_GS || oc == EPGX_OP_D)
-            return fail(EPGX_ERR_UNSUPPORTED, "%s: operator %zu: exchange, gather shifts and diffusion run at K <= 1024 (epgx_run)", who, i);
-    }
-    return EPGX_OK;
+    return analyse_tiled(who, deriv, pl->host, *pl, Kbuf, tiled_m, rq, top0, shape);
 }
 
 static int tiled_info(const char *who, bool deriv, epgx_ctx *ctx, const epgx_plan *plan, int32_t Kbuf, int32_t top0, int32_t *blocks,
                       int32_t *shifts, int64_t *tile_launches, int32_t *peak, char *names, int64_t name_bytes) {
-    if (int rc = tiled_check(ctx, plan, Kbuf, who, deriv)) return rc;
-    if (top0 < 0 || top0 >= Kbuf) return fail(EPGX_ERR_INVALID, "%s: top0=%d outside [0, Kbuf)", who, top0);
-    int M, H;
-    tiled_knobs(M, H);
-    if (deriv) M = 8, H = 32;      // (the derivative kernel exists at 8 orders per lane only)
+    TiledShape shape;
+    if (int rc = tiled_analysis(who, deriv, ctx, plan, Kbuf, nullptr, top0, &shape)) return rc;
+    const int M = shape.M, H = shape.H;
     TiledSchedule ts;
     if (int rc = tiled_schedule(plan->host, Kbuf, top0, M, H, knobs(), ts)) return rc;
     const int nb = (int)ts.steps.size() - ts.n_shift;
@@ -2358,25 +2273,15 @@ extern "C" int epgx_tiled_deriv_info(epgx_ctx *ctx, const epgx_plan *plan, int32
 // derivative states, which start at zero) and the blocks run on tiled_deriv_kernel; a shift by more than H moves every window
 static int run_tiled(const char *who, bool deriv, epgx_ctx *ctx, const epgx_plan *plan_c, int64_t vox0, int64_t nvox, const epgx_state *in,
                      int32_t Kbuf, void *signal, int64_t signal_ld, int64_t signal_col0, int64_t slab_voxels) {
-    if (int rc = tiled_check(ctx, plan_c, Kbuf, who, deriv)) return rc;
+    TiledRequest rq;
+    rq.vox0 = vox0, rq.nvox = nvox, rq.slab_voxels = slab_voxels, rq.in = facts_of(in, ctx);
+    TiledShape shape;
+    if (int rc = tiled_analysis(who, deriv, ctx, plan_c, Kbuf, &rq, 0, &shape)) return rc;
     epgx_plan *pl = const_cast<epgx_plan *>(plan_c);
     const int nw = deriv ? 1 + pl->host.n_vars : 1;
-    if (nvox < 0 || vox0 < 0 || vox0 + nvox > pl->nvox_total)
-        return fail(EPGX_ERR_INVALID, "%s: voxel range [%lld,%lld) outside the grid (%lld voxels)", who, (long long)vox0,
-                    (long long)(vox0 + nvox), (long long)pl->nvox_total);
-    if (slab_voxels < 0) return fail(EPGX_ERR_INVALID, "%s: slab_voxels < 0", who);
-    if (in) {
-        if (in->ctx != ctx) return fail(EPGX_ERR_INVALID, "%s: `in` belongs to another context", who);
-        if (in->nvox != nvox)
-            return fail(EPGX_ERR_INVALID, "%s: `in` holds %lld voxels, range has %lld", who, (long long)in->nvox, (long long)nvox);
-        if (in->K > 1024) return fail(EPGX_ERR_UNSUPPORTED, "%s: `in` has %d orders (at most 1024)", who, in->K);
-        if (in->K > Kbuf) return fail(EPGX_ERR_INVALID, "%s: `in` has %d orders, Kbuf=%d", who, in->K, Kbuf);
-    }
-    int M, H;
-    tiled_knobs(M, H);
-    if (deriv) M = 8, H = 32;
+    const int M = shape.M, H = shape.H;
     TiledSchedule ts;
-    if (int rc = tiled_schedule(pl->host, Kbuf, in ? in->K - 1 : 0, M, H, knobs(), ts)) return rc;
+    if (int rc = tiled_schedule(pl->host, Kbuf, shape.top0, M, H, knobs(), ts)) return rc;
     if (deriv && ts.drecs.size() != ts.recs.size()) return fail(EPGX_ERR_INVALID, "%s: %zu records, %zu derivative records", who, ts.recs.size(), ts.drecs.size());
     if (ts.has_adc) {
         if (!signal) return fail(EPGX_ERR_INVALID, "%s: the plan contains an ADC but signal is NULL", who);
@@ -2390,9 +2295,7 @@ static int run_tiled(const char *who, bool deriv, epgx_ctx *ctx, const epgx_plan
     if (int rc = ensure_vidx(pl, vox0, nvox)) return rc;
     // two buffers [slab][3][Kbuf] + the density: at most 8 GiB per slab (as the two legs at 2048 orders)
     const int64_t per_voxel = (int64_t)2 * nw * 3 * Kbuf * sizeof(d2) + sizeof(double);
-    int64_t slab = std::min<int64_t>((nvox + 3) & ~(int64_t)3, std::max<int64_t>(4, (((int64_t)8 << 30) / per_voxel) & ~(int64_t)3));
-    if (knobs().slab_voxels > 0) slab = std::min<int64_t>(slab, (knobs().slab_voxels + 3) & ~3);
-    if (slab_voxels > 0) slab = std::min<int64_t>(slab, slab_voxels);
+    const int64_t slab = epgx::slab_voxels(nvox, per_voxel, knobs().slab_voxels, slab_voxels);
     const size_t buf_bytes = (size_t)slab * nw * 3 * Kbuf * sizeof(d2);
     void *mem = nullptr, *d_recs = nullptr, *d_drecs = nullptr;
     const size_t rec_bytes = (ts.recs.size() + 2) * sizeof(Rec);     // two padding records (the kernel fetches ahead)
