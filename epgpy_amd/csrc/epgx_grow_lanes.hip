@@ -18,13 +18,13 @@ using namespace epgx;
 int epgx_lanes_deck() { return EPGX_LANES_DECK; }   // (one definition for the four units)
 #endif
 
-// rem0: shifts up to the last probe; L: the largest live count (lanes_plan, epgx_planner.cpp), 1 <= L <= 24
-hipError_t EPGX_CAT(epgx_launch_rows_grow_lanes_nsp, EPGX_NSP)(hipStream_t stream, const RunArgs &a, int rem0, int L) {
+// rem0: shifts up to the last probe; L: the largest live count (lanes_plan, epgx_planner.cpp), 1 <= L <= 24; body: Knobs::lanes_body
+hipError_t EPGX_CAT(epgx_launch_rows_grow_lanes_nsp, EPGX_NSP)(hipStream_t stream, const RunArgs &a, int rem0, int L, int body) {
     if (L < 1 || L > LANES_CAP) return hipErrorInvalidValue;
     const unsigned groups = (unsigned)((a.nvox + 63) / 64);   // one wave of 64 voxels per workgroup
     RunTail t = a.t;
     t.n_blocks = groups;
     const size_t lds = epgx_lanes_lds_bytes(L, EPGX_LANES_DECK);
-    hipLaunchKernelGGL((rows_grow_lanes_kernel<EPGX_NSP>), dim3(groups), dim3(64), lds, stream, a.nvox, a.recs, a.coef, a.signal, a.signal_ld, t, rem0, L);
+    hipLaunchKernelGGL((rows_grow_lanes_kernel<EPGX_NSP>), dim3(groups), dim3(64), lds, stream, a.nvox, a.recs, a.coef, a.signal, a.signal_ld, t, rem0, L, body);
     return hipGetLastError();
 }

@@ -29,7 +29,20 @@
 // live count, <= 24) in 48 * 64 * (L - deck) bytes of dynamic LDS per wave, read and written with 128-bit LDS operations and
 // only by record executions whose window reaches them.  One wave per workgroup; no barrier: a lane only ever touches its own
 // column.
+//
+// Record bodies.  The generic body (lanes_cells) takes the chain kinds tk, t0, ek as wave-uniform run-time values and skips
+// order by order: every cell is a handful of basic blocks.  The records a train repeats have bodies specialised on their
+// shifts AND kinds (EPGX_LANES_BODIES, epgx_lanes_bodies.h; dispatched once per record), which run the cells IN BLOCKS of B:
+// block b holds the orders b B .. b B + B - 1.  With the window 0 .. lim, the block lim / B is partial -- its lim % B + 1
+// cells go through a per-cell ladder -- and every block below it is one straight-line region of B cells behind a single
+// wave-uniform test, in which the compiler interleaves the chains of neighbouring cells and issues the LDS reads of the
+// block ahead of the arithmetic.  A full block touches the slots up to its top order + 1 <= lim <= lcap - 1 only, so its
+// slot accesses need no test against lcap.  The cells are those of the generic body -- the same function with the kinds
+// as constants -- in the same order, top down, and `pend` carries across blocks exactly as it does across cells.
+// Invariant: `pend` is zero when the top cell of a window starts (every skipped cell above leaves it at its initial zeros).
+// EPGX_LANES_BODY=0 (kernel argument `body`) sends every record through the generic body: same bits, for A/B runs and tests.
 #pragma once
+#include "epgx_lanes_bodies.h"
 #include "epgx_rows_kernels.hip.h"
 
 namespace epgx {
@@ -92,9 +105,8 @@ __device__ __forceinline__ void lanes_put(double (&re)[D], double (&im)[D], lane
 // 2 cell_TX_sumdiff, 3 cell_TY; t0: constant term on order 0 (cell_offset: Re o0 with tk 1 and 3, Im o0 with tk 1 and 2); ek:
 // 0 no relaxation, 1 cell_E, 2 cell_ER.  pend: F- results on their way down (see the header)
 template <int D, int I, int O, int J>
-__device__ __forceinline__ void lanes_cell(LaneDeck<D> &s, lanes_d2 *lds, const int lcap, const int lim, const int tk, const bool t0,
-                                           const int ek, const LaneLine &k, double (&pend)[4]) {
-    if (J > lim) return;
+__device__ __forceinline__ void lanes_cell_body(LaneDeck<D> &s, lanes_d2 *lds, const int lcap, const int tk, const bool t0, const int ek,
+                                                const LaneLine &k, double (&pend)[4]) {
     double ar, ai, br, bi, zr, zi;
     lanes_get<D, J + I>(s.Br, s.Bi, lds, 1, lcap, br, bi);
     if constexpr (I == 1 && J == 0) {   // rows_shift: X_0 <- conj(Y_1)
@@ -178,18 +190,51 @@ __device__ __forceinline__ void lanes_cell(LaneDeck<D> &s, lanes_d2 *lds, const 
     }
 }
 
+// the generic body: one scalar compare and branch per order is the skip
+template <int D, int I, int O, int J>
+__device__ __forceinline__ void lanes_cell(LaneDeck<D> &s, lanes_d2 *lds, const int lcap, const int lim, const int tk, const bool t0,
+                                           const int ek, const LaneLine &k, double (&pend)[4]) {
+    if (J > lim) return;
+    lanes_cell_body<D, I, O, J>(s, lds, lcap, tk, t0, ek, k, pend);
+}
+
+// the blocked body: block BLK = the orders BLK * B .. BLK * B + B - 1, tb = lim / B the partial block.  TK, T0, EK are
+// compile-time constants: inlined into the cell, they leave the one chain the record runs and the line entries it reads
+template <int D, int I, int O, int TK, bool T0, int EK, int B, int BLK, int... Cs>
+__device__ __forceinline__ void lanes_block(LaneDeck<D> &s, lanes_d2 *lds, const int lcap, const int lim, const int tb, const LaneLine &k,
+                                            double (&pend)[4], std::integer_sequence<int, Cs...>) {
+    if (tb < BLK) return;
+    if (B == 1 || tb == BLK) {   // the top of the window: cell by cell, slots tested against lcap
+        (lanes_cell<D, I, O, BLK * B + B - 1 - Cs>(s, lds, lcap, lim, TK, T0, EK, k, pend), ...);
+    } else {                     // a full block: straight line, every slot exists (header)
+        (lanes_cell_body<D, I, O, BLK * B + B - 1 - Cs>(s, lds, LANES_CAP, TK, T0, EK, k, pend), ...);
+    }
+}
+template <int D, int I, int O, int TK, bool T0, int EK, int B, int... Bs>
+__device__ __forceinline__ void lanes_blocks(LaneDeck<D> &s, lanes_d2 *lds, int lcap, int lim, const LaneLine &k, double (&pend)[4],
+                                             std::integer_sequence<int, Bs...>) {
+    static_assert(LANES_CAP % B == 0 && (B & (B - 1)) == 0, "whole blocks, a power of two");
+    constexpr int NB = LANES_CAP / B;
+    const int tb = lim / B;
+    (lanes_block<D, I, O, TK, T0, EK, B, NB - 1 - Bs>(s, lds, lcap, lim, tb, k, pend, std::make_integer_sequence<int, B>()), ...);
+}
+
 template <int D, int I, int O, int... Js>
 __device__ __forceinline__ void lanes_cells(LaneDeck<D> &s, lanes_d2 *lds, int lcap, int lim, int tk, bool t0, int ek, const LaneLine &k,
                                             double (&pend)[4], std::integer_sequence<int, Js...>) {
     (lanes_cell<D, I, O, LANES_CAP - 1 - Js>(s, lds, lcap, lim, tk, t0, ek, k, pend), ...);   // from the top order down
 }
 
-// one record execution on the orders 0 .. lim
-template <int D, int I, int O>
+// one record execution on the orders 0 .. lim.  B == 0: the generic body, the kinds tk, t0, ek at run time; B > 0: blocks
+// of B cells specialised on TK, T0, EK
+template <int D, int I, int O, int B, int TK, bool T0, int EK>
 __device__ __forceinline__ void lanes_record(LaneDeck<D> &s, lanes_d2 *lds, int lcap, int lim, int tk, bool t0, int ek, const LaneLine &k) {
     if (lim < 0) return;   // (behind the last probe)
     double pend[4] = {0.0, 0.0, 0.0, 0.0};
-    lanes_cells<D, I, O>(s, lds, lcap, lim, tk, t0, ek, k, pend, std::make_integer_sequence<int, LANES_CAP>());
+    if constexpr (B == 0)
+        lanes_cells<D, I, O>(s, lds, lcap, lim, tk, t0, ek, k, pend, std::make_integer_sequence<int, LANES_CAP>());
+    else
+        lanes_blocks<D, I, O, TK, T0, EK, B>(s, lds, lcap, lim, k, pend, std::make_integer_sequence<int, LANES_CAP / B>());
     if constexpr (I == 1) {   // the F- result of order O has no reader left: slot 0
         s.Br[0] = pend[2 * O];
         s.Bi[0] = pend[2 * O + 1];
@@ -197,29 +242,6 @@ __device__ __forceinline__ void lanes_record(LaneDeck<D> &s, lanes_d2 *lds, int 
     if constexpr (O == 1) {   // rows_shift: X_0 <- conj(Y_1), the new Y_0
         s.Ar[0] = s.Br[0];
         s.Ai[0] = -s.Bi[0];
-    }
-}
-
-// `rep` executions of record r (its line is loaded once), probes to consecutive rows
-template <int NSP, int D, int I, int O>
-__device__ __forceinline__ void lanes_run(LaneDeck<D> &s, lanes_d2 *lds, const int lcap, const Rec &r, const int rep, int &top, int &rem, const int tk,
-                                          const bool t0, const int ek, const LaneLine &k, d2 *sig_base, const int64_t signal_ld, const int nvalid,
-                                          const uint32_t voff) {
-    int slot = r.slot;
-    for (int e = 0; e < rep; ++e, ++slot) {
-        // the cells work between the record's two shifts: top + I orders are populated there, rem - I shifts are left
-        int lim = top + I < rem - I ? top + I : rem - I;
-        lim = lim < lcap - 1 ? lim : lcap - 1;   // (never beyond the slots the launch has, whatever the host passed)
-        lanes_record<D, I, O>(s, lds, lcap, lim, tk, t0, ek, k);
-        top += I + O;
-        rem -= I + O;
-        if (r.flags & F_ADC) {
-            u32x4 bits;
-            bits.x = (uint32_t)__double2loint(s.Ar[0]); bits.y = (uint32_t)__double2hiint(s.Ar[0]);
-            bits.z = (uint32_t)__double2loint(s.Ai[0]); bits.w = (uint32_t)__double2hiint(s.Ai[0]);
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(sig_base + (int64_t)slot * signal_ld, 0, 16 * nvalid, 0x00020000);
-            __builtin_amdgcn_raw_buffer_store_b128(bits, rs, voff, 0, 0);
-        }
     }
 }
 
@@ -276,12 +298,40 @@ __device__ __forceinline__ void lanes_line(const Rec &r, const __amdgpu_buffer_r
     }
 }
 
-// rem0: the shifts of the list up to its last probe; lcap: L, the slots a lane has (deck + LDS).  n1, n2 and the capacities of
-// rows_grow_kernel's ranges are not used: the window follows top and rem record by record
+// `rep` executions of record r, probes to consecutive rows.  The line is loaded once, here and not in front of the dispatch:
+// a specialised body then holds the entries it reads and nothing else
+template <int NSP, int D, int I, int O, int B = 0, int TK = 0, bool T0 = false, int EK = 0>
+__device__ __forceinline__ void lanes_run(LaneDeck<D> &s, lanes_d2 *lds, const int lcap, const Rec &r, const int rep, int &top, int &rem, const int tk,
+                                          const bool t0, const int ek, const __amdgpu_buffer_rsrc_t pool, const uint32_t p0, const uint32_t p1,
+                                          const uint32_t p2, const uint32_t p3, d2 *sig_base, const int64_t signal_ld, const int nvalid,
+                                          const uint32_t voff) {
+    LaneLine k;
+    lanes_line<NSP>(r, pool, p0, p1, p2, p3, tk, k);
+    int slot = r.slot;
+    for (int e = 0; e < rep; ++e, ++slot) {
+        // the cells work between the record's two shifts: top + I orders are populated there, rem - I shifts are left
+        int lim = top + I < rem - I ? top + I : rem - I;
+        lim = lim < lcap - 1 ? lim : lcap - 1;   // (never beyond the slots the launch has, whatever the host passed)
+        lanes_record<D, I, O, B, TK, T0, EK>(s, lds, lcap, lim, tk, t0, ek, k);
+        top += I + O;
+        rem -= I + O;
+        if (r.flags & F_ADC) {
+            u32x4 bits;
+            bits.x = (uint32_t)__double2loint(s.Ar[0]); bits.y = (uint32_t)__double2hiint(s.Ar[0]);
+            bits.z = (uint32_t)__double2loint(s.Ai[0]); bits.w = (uint32_t)__double2hiint(s.Ai[0]);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(sig_base + (int64_t)slot * signal_ld, 0, 16 * nvalid, 0x00020000);
+            __builtin_amdgcn_raw_buffer_store_b128(bits, rs, voff, 0, 0);
+        }
+    }
+}
+
+// rem0: the shifts of the list up to its last probe; lcap: L, the slots a lane has (deck + LDS); body: 0 the generic body for
+// every record, else the specialised bodies where they exist.  n1, n2 and the capacities of rows_grow_kernel's ranges are not
+// used: the window follows top and rem record by record
 template <int NSP>
 __global__ void __launch_bounds__(64, 2) rows_grow_lanes_kernel(const int64_t nvox, const Rec *__restrict__ recs_, const double *__restrict__ coef_,
                                                                d2 *__restrict__ signal, const int64_t signal_ld, const RunTail a, const int rem0,
-                                                               const int lcap) {
+                                                               const int lcap, const int body) {
     constexpr int D = EPGX_LANES_DECK;
     extern __shared__ __attribute__((aligned(16))) lanes_d2 lanes_lds[];
     const int lane = threadIdx.x & 63;
@@ -320,16 +370,21 @@ __global__ void __launch_bounds__(64, 2) rows_grow_lanes_kernel(const int64_t nv
             const int rep = members ? 1 : (count > 1 ? count : 1);
             if (members) --members;
             // the chains the rows code runs for this record: rows_T / rows_generic (a record without a leaf runs the plain chains)
-            const int tk = !(f & F_T) ? 0 : ((f & F_TX) ? 2 : (((f & F_TY) && head != LEAF_NONE) ? 3 : 1));
+            const int tk = lanes_tk(f, head);
             const bool t0 = (f & F_T0) != 0;
-            const int ek = !(f & F_E) ? 0 : ((f & F_ER) ? 2 : 1);
-            LaneLine k;
-            lanes_line<NSP>(r, pool, p0, p1, p2, p3, tk, k);
+            const int ek = lanes_ek(f);
+            switch (body ? lanes_body_id(f, head) : -1) {
+#define EPGX_LANES_CASE(id, I, O, TK, T0, EK, B, name) \
+    case id: lanes_run<NSP, D, I, O, B, TK, T0, EK>(s, lds, lcap, r, rep, top, rem, TK, T0, EK, pool, p0, p1, p2, p3, sig_base, signal_ld, nvalid, voff); continue;
+                EPGX_LANES_BODIES(EPGX_LANES_CASE)
+#undef EPGX_LANES_CASE
+            default: break;
+            }
             switch (((f & F_S0) ? 2 : 0) | ((f & F_S) ? 1 : 0)) {
-            case 0: lanes_run<NSP, D, 0, 0>(s, lds, lcap, r, rep, top, rem, tk, t0, ek, k, sig_base, signal_ld, nvalid, voff); break;
-            case 1: lanes_run<NSP, D, 0, 1>(s, lds, lcap, r, rep, top, rem, tk, t0, ek, k, sig_base, signal_ld, nvalid, voff); break;
-            case 2: lanes_run<NSP, D, 1, 0>(s, lds, lcap, r, rep, top, rem, tk, t0, ek, k, sig_base, signal_ld, nvalid, voff); break;
-            default: lanes_run<NSP, D, 1, 1>(s, lds, lcap, r, rep, top, rem, tk, t0, ek, k, sig_base, signal_ld, nvalid, voff); break;
+            case 0: lanes_run<NSP, D, 0, 0>(s, lds, lcap, r, rep, top, rem, tk, t0, ek, pool, p0, p1, p2, p3, sig_base, signal_ld, nvalid, voff); break;
+            case 1: lanes_run<NSP, D, 0, 1>(s, lds, lcap, r, rep, top, rem, tk, t0, ek, pool, p0, p1, p2, p3, sig_base, signal_ld, nvalid, voff); break;
+            case 2: lanes_run<NSP, D, 1, 0>(s, lds, lcap, r, rep, top, rem, tk, t0, ek, pool, p0, p1, p2, p3, sig_base, signal_ld, nvalid, voff); break;
+            default: lanes_run<NSP, D, 1, 1>(s, lds, lcap, r, rep, top, rem, tk, t0, ek, pool, p0, p1, p2, p3, sig_base, signal_ld, nvalid, voff); break;
             }
         }
     }

@@ -32,6 +32,7 @@ struct Knobs {
     bool reach;     // EPGX_REACH (default 1): a range of rows_grow_kernel runs at the orders that can still reach a probe (grow_reach); 0: at 16 / 32 / 64
     int cgrow;      // EPGX_CGROW: 0 off, 1 (default): growing launches at K = 256 .. 1024, at K = 128 when 60 % of the records run below 64 orders; 2: at K = 128 whenever the other capacities would
     int lanes;      // EPGX_LANES: the one-voxel-per-lane variant of a FAM_ROWS_GROW launch (lanes_plan) -- 0 never, 1 from LANES_MIN_VOXELS voxels on, 2 whenever the list is eligible (tests)
+    int lanes_body = 1;   // EPGX_LANES_BODY: the record bodies of that variant -- 1 (default) specialised and blocked where one exists, 0 the generic per-cell body everywhere.  The kernel's alone: no part of lanes_plan / lanes_selected
 };
 // EPGX_TRACE is read per call (tests switch it on and off)
 inline bool tracing() { return getenv("EPGX_TRACE") != nullptr; }
