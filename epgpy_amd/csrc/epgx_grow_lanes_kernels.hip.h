@@ -41,6 +41,17 @@
 // as constants -- in the same order, top down, and `pend` carries across blocks exactly as it does across cells.
 // Invariant: `pend` is zero when the top cell of a window starts (every skipped cell above leaves it at its initial zeros).
 // EPGX_LANES_BODY=0 (kernel argument `body`) sends every record through the generic body: same bits, for A/B runs and tests.
+//
+// Two instantiations per NSP.  rows_grow_lanes_kernel<NSP, false> is the kernel described so far: any eligible list, the generic
+// body as the fallback of the dispatch, and with it a 15-double line live next to the state -- a deck of EPGX_LANES_DECK = 14.
+// rows_grow_lanes_kernel<NSP, true> runs TRAINS (LanesPlan::train, epgx_planner.cpp): lists in which every record that is not a
+// head record has a specialised body.  A head record executes before any shift (top == 0) and has no leading shift: it touches
+// order 0 alone and runs ONE cell, lanes_cell_body<D, 0, O, 0>, with the kinds at run time -- its line is dead before the
+// next record's line is loaded.  (With a trailing shift it executes once: a second execution would start at top == 1.)
+// No generic body, no fallback switch: a body holds the line entries its kinds read and nothing else, and the deck is EPGX_LANES_TRAIN_DECK = 16 (eight one-wave workgroups per CU at L = 21 where deck 14 has
+// seven, and half the cells on LDS slots).  The host never sends this kernel a record without a body; if one arrived it would be
+// SKIPPED (top and rem unchanged, every window still capped by lcap): wrong probes, no access outside the slots.  The cells,
+// their operands and their order are those of the other instantiation: same bits.
 #pragma once
 #include "epgx_lanes_bodies.h"
 #include "epgx_rows_kernels.hip.h"
@@ -49,6 +60,9 @@ namespace epgx {
 
 #ifndef EPGX_LANES_DECK
 #define EPGX_LANES_DECK 14
+#endif
+#ifndef EPGX_LANES_TRAIN_DECK
+#define EPGX_LANES_TRAIN_DECK 16
 #endif
 constexpr int LANES_CAP = 24;   // orders the unrolled loop covers (lanes_plan, epgx_planner.cpp: L <= 24)
 
@@ -226,12 +240,16 @@ __device__ __forceinline__ void lanes_cells(LaneDeck<D> &s, lanes_d2 *lds, int l
 }
 
 // one record execution on the orders 0 .. lim.  B == 0: the generic body, the kinds tk, t0, ek at run time; B > 0: blocks
-// of B cells specialised on TK, T0, EK
+// of B cells specialised on TK, T0, EK; B < 0: a head record (no leading shift, top == 0, so lim <= 0): the cell of order 0,
+// kinds at run time
 template <int D, int I, int O, int B, int TK, bool T0, int EK>
 __device__ __forceinline__ void lanes_record(LaneDeck<D> &s, lanes_d2 *lds, int lcap, int lim, int tk, bool t0, int ek, const LaneLine &k) {
     if (lim < 0) return;   // (behind the last probe)
     double pend[4] = {0.0, 0.0, 0.0, 0.0};
-    if constexpr (B == 0)
+    if constexpr (B < 0) {
+        static_assert(I == 0, "a head record has no leading shift");
+        lanes_cell_body<D, 0, O, 0>(s, lds, lcap, tk, t0, ek, k, pend);
+    } else if constexpr (B == 0)
         lanes_cells<D, I, O>(s, lds, lcap, lim, tk, t0, ek, k, pend, std::make_integer_sequence<int, LANES_CAP>());
     else
         lanes_blocks<D, I, O, TK, T0, EK, B>(s, lds, lcap, lim, k, pend, std::make_integer_sequence<int, LANES_CAP / B>());
@@ -327,12 +345,13 @@ __device__ __forceinline__ void lanes_run(LaneDeck<D> &s, lanes_d2 *lds, const i
 
 // rem0: the shifts of the list up to its last probe; lcap: L, the slots a lane has (deck + LDS); body: 0 the generic body for
 // every record, else the specialised bodies where they exist.  n1, n2 and the capacities of rows_grow_kernel's ranges are not
-// used: the window follows top and rem record by record
-template <int NSP>
+// used: the window follows top and rem record by record.  TRAIN: head records and specialised bodies only, on its own deck
+// (header); `body` is not read there -- the launcher sends EPGX_LANES_BODY=0 to the other instantiation
+template <int NSP, bool TRAIN>
 __global__ void __launch_bounds__(64, 2) rows_grow_lanes_kernel(const int64_t nvox, const Rec *__restrict__ recs_, const double *__restrict__ coef_,
                                                                d2 *__restrict__ signal, const int64_t signal_ld, const RunTail a, const int rem0,
                                                                const int lcap, const int body) {
-    constexpr int D = EPGX_LANES_DECK;
+    constexpr int D = TRAIN ? EPGX_LANES_TRAIN_DECK : EPGX_LANES_DECK;
     extern __shared__ __attribute__((aligned(16))) lanes_d2 lanes_lds[];
     const int lane = threadIdx.x & 63;
     const const_rec_t recs = (const_rec_t)(uintptr_t)recs_;
@@ -373,6 +392,23 @@ __global__ void __launch_bounds__(64, 2) rows_grow_lanes_kernel(const int64_t nv
             const int tk = lanes_tk(f, head);
             const bool t0 = (f & F_T0) != 0;
             const int ek = lanes_ek(f);
+            if constexpr (TRAIN) {
+                if (top == 0 && !(f & F_S0) && (!(f & F_S) || rep == 1)) {   // a head record (as lanes_plan decides it)
+                    if (f & F_S)
+                        lanes_run<NSP, D, 0, 1, -1>(s, lds, lcap, r, rep, top, rem, tk, t0, ek, pool, p0, p1, p2, p3, sig_base, signal_ld, nvalid, voff);
+                    else
+                        lanes_run<NSP, D, 0, 0, -1>(s, lds, lcap, r, rep, top, rem, tk, t0, ek, pool, p0, p1, p2, p3, sig_base, signal_ld, nvalid, voff);
+                    continue;
+                }
+                switch (lanes_body_id(f, head)) {
+#define EPGX_LANES_CASE(id, I, O, TK, T0, EK, B, name) \
+    case id: lanes_run<NSP, D, I, O, B, TK, T0, EK>(s, lds, lcap, r, rep, top, rem, TK, T0, EK, pool, p0, p1, p2, p3, sig_base, signal_ld, nvalid, voff); break;
+                    EPGX_LANES_BODIES(EPGX_LANES_CASE)
+#undef EPGX_LANES_CASE
+                default: break;   // (no body: not a train -- skipped, see the header)
+                }
+                continue;
+            }
             switch (body ? lanes_body_id(f, head) : -1) {
 #define EPGX_LANES_CASE(id, I, O, TK, T0, EK, B, name) \
     case id: lanes_run<NSP, D, I, O, B, TK, T0, EK>(s, lds, lcap, r, rep, top, rem, TK, T0, EK, pool, p0, p1, p2, p3, sig_base, signal_ld, nvalid, voff); continue;

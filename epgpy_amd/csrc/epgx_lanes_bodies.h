@@ -22,6 +22,8 @@ constexpr int lanes_ek(uint32_t f) { return !(f & F_E) ? 0 : ((f & F_ER) ? 2 : 1
 //   echo-x   the folded echo S T0 S (run-time fold or fused on the host): what a spin-echo train repeats
 // One entry: bodies for the excitation (tk 1 / 3) and for the halves of an unfused echo (tk 2 with ek 1 / 2, ek alone) were
 // written and taken out again -- each of them next to the generic body took the kernel beyond 256 VGPRs.
+// A list in which every record behind the head records (no leading shift, nothing shifted yet: one cell of the generic body)
+// is listed here is a TRAIN (LanesPlan::train): it runs the instantiation of the kernel that has these bodies and no generic one.
 #define EPGX_LANES_BODIES(X) X(0, 1, 1, 2, true, 0, 4, "echo-x")
 constexpr int LANES_N_BODIES = 1;
 

@@ -13,31 +13,36 @@
 // big enough to fill the chip with waves of 64 voxels.  choose_kernel does not know of the second: it names the family, the
 // launcher picks the variant from the list, the knob EPGX_LANES and the number of voxels.  EPGX_LANES_BODY (default 1) is the
 // kernel's business alone: 0 runs every record of the variant through its generic body (epgx_lanes_bodies.h).
-hipError_t epgx_launch_rows_grow_lanes_nsp0(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L, int body);
-hipError_t epgx_launch_rows_grow_lanes_nsp1(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L, int body);
-hipError_t epgx_launch_rows_grow_lanes_nsp2(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L, int body);
-hipError_t epgx_launch_rows_grow_lanes_nsp4(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L, int body);
-int epgx_lanes_deck();   // orders of a lane that live in VGPRs (EPGX_LANES_DECK); the rest, up to L, in LDS
+// The variant has two kernels (epgx_grow_lanes_kernels.hip.h): the one with the generic body as its fallback, and -- `train` -- the
+// one without it, on a larger register deck, for lists in which every record behind the first shift has a specialised body
+// (LanesPlan::train).  EPGX_LANES_TRAIN=0 and EPGX_LANES_BODY=0 both keep a launch on the first.
+hipError_t epgx_launch_rows_grow_lanes_nsp0(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L, int body, bool train);
+hipError_t epgx_launch_rows_grow_lanes_nsp1(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L, int body, bool train);
+hipError_t epgx_launch_rows_grow_lanes_nsp2(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L, int body, bool train);
+hipError_t epgx_launch_rows_grow_lanes_nsp4(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L, int body, bool train);
+int epgx_lanes_deck(bool train);   // orders of a lane that live in VGPRs (EPGX_LANES_DECK / EPGX_LANES_TRAIN_DECK); the rest, up to L, in LDS
 inline size_t epgx_lanes_lds_bytes(int L, int deck) { return L > deck ? (size_t)48 * 64 * (size_t)(L - deck) : 0; }
 // `grow`: the host copy of the list `a.recs` holds; n1, n2, cap: the ranges of the rows variant
 inline hipError_t epgx_launch_rows_grow(hipStream_t stream, const epgx::RunArgs &a, int n_spaces, const std::vector<epgx::Rec> &grow, int n1, int n2,
                                         const int cap[3], const epgx::Knobs &kn) {
     const epgx::LanesPlan lp = epgx::lanes_plan(grow, a.in != nullptr, a.out != nullptr, kn);
     const bool lanes = epgx::lanes_selected(lp, a.nvox, kn);
+    const bool train = epgx::lanes_train_selected(lp, kn);
     if (epgx::tracing()) {
         if (lanes)
-            fprintf(stderr, "[epgx] run: variant lanes (one voxel per lane): L = %d, %zu bytes of LDS per wave, %d shifts before the last probe, body %s\n",
-                    lp.L, epgx_lanes_lds_bytes(lp.L, epgx_lanes_deck()), lp.rem0, epgx::lanes_body_names(grow, kn.lanes_body != 0).c_str());
+            fprintf(stderr, "[epgx] run: variant lanes (one voxel per lane): L = %d, kernel %s (deck %d), %zu bytes of LDS per wave, %d shifts before the last probe, body %s\n",
+                    lp.L, train ? "train" : "any list", epgx_lanes_deck(train), epgx_lanes_lds_bytes(lp.L, epgx_lanes_deck(train)), lp.rem0,
+                    epgx::lanes_body_names(grow, kn.lanes_body != 0).c_str());
         else
             fprintf(stderr, "[epgx] run: variant rows (four voxels per wave): %s\n",
                     lp.eligible ? "fewer voxels than the one-voxel-per-lane variant is taken for" : lp.why);
     }
     if (lanes) {
         switch (n_spaces) {
-        case 0: return epgx_launch_rows_grow_lanes_nsp0(stream, a, lp.rem0, lp.L, kn.lanes_body);
-        case 1: return epgx_launch_rows_grow_lanes_nsp1(stream, a, lp.rem0, lp.L, kn.lanes_body);
-        case 2: return epgx_launch_rows_grow_lanes_nsp2(stream, a, lp.rem0, lp.L, kn.lanes_body);
-        default: return epgx_launch_rows_grow_lanes_nsp4(stream, a, lp.rem0, lp.L, kn.lanes_body);
+        case 0: return epgx_launch_rows_grow_lanes_nsp0(stream, a, lp.rem0, lp.L, kn.lanes_body, train);
+        case 1: return epgx_launch_rows_grow_lanes_nsp1(stream, a, lp.rem0, lp.L, kn.lanes_body, train);
+        case 2: return epgx_launch_rows_grow_lanes_nsp2(stream, a, lp.rem0, lp.L, kn.lanes_body, train);
+        default: return epgx_launch_rows_grow_lanes_nsp4(stream, a, lp.rem0, lp.L, kn.lanes_body, train);
         }
     }
     switch (n_spaces) {

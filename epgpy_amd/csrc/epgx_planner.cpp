@@ -1,5 +1,6 @@
 // epgx_planner.cpp -- launch planning on host data alone (epgx_planner.h): no HIP call, no device pointer.
 #include "epgx_planner.h"
+#include "epgx_lanes_bodies.h"
 
 #include <algorithm>
 #include <cmath>
@@ -373,7 +374,7 @@ LanesPlan lanes_plan(const std::vector<Rec> &grow, bool has_in, bool has_out, co
     if (kn.lanes <= 0) return refuse("EPGX_LANES=0");
     if (has_in || has_out) return refuse("a state input or output");
     if (grow.empty()) return refuse("no growing record list");
-    struct Exec { int d, rep; bool adc; };
+    struct Exec { int d, rep; bool adc, body, lead; };
     std::vector<Exec> ex;
     size_t members = 0;
     for (const Rec &r : grow) {
@@ -395,7 +396,7 @@ LanesPlan lanes_plan(const std::vector<Rec> &grow, bool has_in, bool has_out, co
         if (f & F_ADC_Z) return refuse("a Z0 probe");
         if ((f & F_S) && !(f & F_FOLD) && r.shift != 1) return refuse(r.shift == -1 ? "S(-1)" : "a shift by more than one order");
         if ((f & F_T0) && !(f & F_T)) return refuse("a constant term without a rotation");
-        ex.push_back({((f & F_S0) ? 1 : 0) + ((f & F_S) ? 1 : 0), rep, (f & F_ADC) != 0});
+        ex.push_back({((f & F_S0) ? 1 : 0) + ((f & F_S) ? 1 : 0), rep, (f & F_ADC) != 0, lanes_body_id(f, head) >= 0, (f & F_S0) != 0});
     }
     // the shifts up to the last probe (a record shifts before it probes), then shift by shift: between two shifts the state
     // holds 1 + min(top, rem) live orders
@@ -416,6 +417,15 @@ LanesPlan lanes_plan(const std::vector<Rec> &grow, bool has_in, bool has_out, co
     lp.L = (int)std::min<long>(need, 1 << 30);
     if (need > LANES_MAX_ORDERS) return refuse("more than 24 live orders");
     lp.eligible = true;
+    // a train: head records, then bodies only.  A head record executes while nothing has shifted yet and has no leading shift
+    // (its window is order 0 alone; a trailing shift is where its one cell puts the result), once if it shifts
+    lp.train = true;
+    top = 0;
+    for (const Exec &x : ex) {
+        const bool head_rec = top == 0 && !x.lead && (x.d == 0 || x.rep == 1);
+        if (!head_rec && !x.body) lp.train = false;
+        top += (long)x.d * x.rep;
+    }
     return lp;
 }
 

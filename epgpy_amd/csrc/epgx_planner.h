@@ -33,6 +33,7 @@ struct Knobs {
     int cgrow;      // EPGX_CGROW: 0 off, 1 (default): growing launches at K = 256 .. 1024, at K = 128 when 60 % of the records run below 64 orders; 2: at K = 128 whenever the other capacities would
     int lanes;      // EPGX_LANES: the one-voxel-per-lane variant of a FAM_ROWS_GROW launch (lanes_plan) -- 0 never, 1 from LANES_MIN_VOXELS voxels on, 2 whenever the list is eligible (tests)
     int lanes_body = 1;   // EPGX_LANES_BODY: the record bodies of that variant -- 1 (default) specialised and blocked where one exists, 0 the generic per-cell body everywhere.  The kernel's alone: no part of lanes_plan / lanes_selected
+    int lanes_train = 1;  // EPGX_LANES_TRAIN: 1 (default) a train (LanesPlan::train) runs the kernel without a generic body on its larger deck, 0 every list runs the kernel with it.  lanes_plan reports `train` whatever this says; lanes_train_selected is the choice
 };
 // EPGX_TRACE is read per call (tests switch it on and off)
 inline bool tracing() { return getenv("EPGX_TRACE") != nullptr; }
@@ -127,18 +128,27 @@ void grow_reach(const std::vector<Rec> &list, int n1, int n2, int cap[3]);
 //             instead of record by record, without the rounding to 16 / 32 / 64.  An n-echo train (two shifts each): n + 1
 //   rem0      the shifts of the whole list up to its last probe (what the kernel starts `rem` from)
 //   why       "" or the first reason the list was refused for
+//   train     eligible, and every record is a head record or has a specialised body (lanes_body_id, epgx_lanes_bodies.h).  A head
+//             record executes before any shift has taken place (top == 0) and has no leading shift: it touches order 0 alone,
+//             whatever its kinds; a trailing shift (one execution then: the second would start at top == 1) only moves where its
+//             cell puts the result.  Such a list can run the instantiation of the kernel that has no generic body
 constexpr int LANES_MAX_ORDERS = 24;
 constexpr int64_t LANES_MIN_VOXELS = 1 << 19;   // EPGX_LANES=1: the variant from this many voxels on (the crossover)
 struct LanesPlan {
     bool eligible = false;
     int L = 0, rem0 = 0;
     const char *why = "";
+    bool train = false;
 };
 LanesPlan lanes_plan(const std::vector<Rec> &grow, bool has_in, bool has_out, const Knobs &kn);
 // the launcher's choice: the knob, the list and the size of the launch
 inline bool lanes_selected(const LanesPlan &lp, int64_t nvox, const Knobs &kn) {
     return lp.eligible && (kn.lanes >= 2 || (kn.lanes == 1 && nvox >= LANES_MIN_VOXELS));
 }
+
+// which kernel of the variant: the one without a generic body for a train, unless a knob asks for the other (EPGX_LANES_BODY=0
+// means the generic body for every record, and only the other kernel has it)
+inline bool lanes_train_selected(const LanesPlan &lp, const Knobs &kn) { return lp.eligible && lp.train && kn.lanes_train != 0 && kn.lanes_body != 0; }
 
 // pack_records, then in this order: run folding, the phases of rows_grow_kernel, the phases of run_contig_grow_kernel, the runs of
 // derivative plans
