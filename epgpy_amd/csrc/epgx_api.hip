@@ -83,7 +83,8 @@ const Knobs &knobs() {
                             getenv("EPGX_GROW_SHARE") ? atof(getenv("EPGX_GROW_SHARE")) : 0.1, env_int("EPGX_LEAD_FORWARD", 1) != 0,
                             env_int("EPGX_SLAB_VOXELS", 0), env_int("EPGX_SPLIT_GROW", 1) != 0, env_int("EPGX_XRUN", 1) != 0,
                             env_int("EPGX_REACH", 1) != 0,  env_int("EPGX_CGROW", 1),           env_int("EPGX_LANES", 1),
-                            env_int("EPGX_LANES_BODY", 1),  env_int("EPGX_LANES_TRAIN", 1)};
+                            env_int("EPGX_LANES_BODY", 1),  env_int("EPGX_LANES_TRAIN", 1),
+                            env_int("EPGX_LANES_ODD", 1)};
     return k;
 }
 

@@ -54,6 +54,7 @@
 // their operands and their order are those of the other instantiation: same bits.
 #pragma once
 #include "epgx_lanes_bodies.h"
+#include "epgx_lanes_odd_cells.h"
 #include "epgx_rows_kernels.hip.h"
 
 namespace epgx {
@@ -71,13 +72,7 @@ struct LaneDeck {
     double Ar[D], Ai[D], Br[D], Bi[D], Zr[D], Zi[D];
 };
 
-// the line of a record in this lane's registers, indexed like the coefficient line of the rows layout (epgx_packed_kernels.hip.h):
-// 0 c00  1 pr  2 pi  3 qr  4 qi  5 tr  6 ti  7 c22 | 8 er  9 ei  10 e2  11 r0 | 12 Re o0  13 Im o0  14 o2; a rotation about x
-// keeps (m00 + m01) / 2 and (m00 - m01) / 2 in slots 0 and 1 (line_bcasts, EPGX_SUMDIFF)
-struct LaneLine {
-    double c[15];
-};
-
+// (LaneLine, the line of a record in this lane's registers: epgx_lanes_odd_cells.h)
 typedef double lanes_d2 __attribute__((ext_vector_type(2)));
 
 // slot IDX of component `comp` (0 F+, 1 F-, 2 Z): a register pair below the deck, this lane's 16 bytes of LDS above it; slots
@@ -137,7 +132,7 @@ __device__ __forceinline__ void lanes_cell_body(LaneDeck<D> &s, lanes_d2 *lds, c
         pend[2] = pend[0];
         pend[3] = pend[1];
     }
-    if (tk == 2) {   // cell_TX_sumdiff
+    if (tk == 2) {   // cell_TX_sumdiff (restated as lanes_tx_sumdiff, epgx_lanes_odd_cells.h: calling that function here changes this kernel's schedule)
         const double ur = ar + br, ui = ai + bi, vr = ar - br, vi = ai - bi;
         const double pr = __builtin_fma(-k.c[4], zi, k.c[1] * vr), pi = __builtin_fma(k.c[4], zr, k.c[1] * vi);
         const double nzr = __builtin_fma(-k.c[6], vi, k.c[7] * zr), nzi = __builtin_fma(k.c[6], vr, k.c[7] * zi);

@@ -37,6 +37,14 @@ constexpr int lanes_body_id(uint32_t f, uint32_t head) {
     return -1;
 }
 
+// the one record rows_grow_lanes_kernel_odd (epgx_grow_lanes_odd_kernels.hip.h) runs behind the head records, and the one
+// LanesPlan::odd admits there: the folded echo about x -- leading and trailing shift, a rotation about x with its constant
+// term, no relaxation stage.  Kernel and planner test this one predicate: a second body with both shifts added to the table
+// above does not become `odd` by itself
+constexpr bool lanes_odd_echo(uint32_t f, uint32_t head) {
+    return (f & F_S0) != 0 && (f & F_S) != 0 && lanes_tk(f, head) == 2 && (f & F_T0) != 0 && lanes_ek(f) == 0;
+}
+
 // the bodies the records of a cut list run, in the order of their first use: "exc-y/1+echo-x/4", "generic", ...
 inline std::string lanes_body_names(const std::vector<Rec> &grow, bool specialised) {
     static const char *const names[LANES_N_BODIES] = {

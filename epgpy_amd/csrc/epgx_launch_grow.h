@@ -16,10 +16,18 @@
 // The variant has two kernels (epgx_grow_lanes_kernels.hip.h): the one with the generic body as its fallback, and -- `train` -- the
 // one without it, on a larger register deck, for lists in which every record behind the first shift has a specialised body
 // (LanesPlan::train).  EPGX_LANES_TRAIN=0 and EPGX_LANES_BODY=0 both keep a launch on the first.
+// A train that repeats S(+1) . X . S(+1) from an unshifted state (LanesPlan::odd) has a third: rows_grow_lanes_kernel_odd
+// (epgx_grow_lanes_odd.hip) computes the orders whose parity reaches an echo and nothing else, half the cells, all in registers.
+// lanes_odd_selected (EPGX_LANES_ODD) routes to it, with a trace line of its own.
 hipError_t epgx_launch_rows_grow_lanes_nsp0(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L, int body, bool train);
 hipError_t epgx_launch_rows_grow_lanes_nsp1(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L, int body, bool train);
 hipError_t epgx_launch_rows_grow_lanes_nsp2(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L, int body, bool train);
 hipError_t epgx_launch_rows_grow_lanes_nsp4(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L, int body, bool train);
+hipError_t epgx_launch_rows_grow_lanes_odd_nsp0(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L);
+hipError_t epgx_launch_rows_grow_lanes_odd_nsp1(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L);
+hipError_t epgx_launch_rows_grow_lanes_odd_nsp2(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L);
+hipError_t epgx_launch_rows_grow_lanes_odd_nsp4(hipStream_t stream, const epgx::RunArgs &a, int rem0, int L);
+int epgx_lanes_odd_cells();   // the compact capacity of rows_grow_lanes_kernel_odd: cells of a lane, 12 VGPRs each
 int epgx_lanes_deck(bool train);   // orders of a lane that live in VGPRs (EPGX_LANES_DECK / EPGX_LANES_TRAIN_DECK); the rest, up to L, in LDS
 inline size_t epgx_lanes_lds_bytes(int L, int deck) { return L > deck ? (size_t)48 * 64 * (size_t)(L - deck) : 0; }
 // `grow`: the host copy of the list `a.recs` holds; n1, n2, cap: the ranges of the rows variant
@@ -28,6 +36,18 @@ inline hipError_t epgx_launch_rows_grow(hipStream_t stream, const epgx::RunArgs 
     const epgx::LanesPlan lp = epgx::lanes_plan(grow, a.in != nullptr, a.out != nullptr, kn);
     const bool lanes = epgx::lanes_selected(lp, a.nvox, kn);
     const bool train = epgx::lanes_train_selected(lp, kn);
+    const bool odd = epgx::lanes_odd_selected(lp, a.nvox, kn);
+    if (odd) {
+        if (epgx::tracing())
+            fprintf(stderr, "[epgx] run: variant lanes-odd (one voxel per lane, odd orders only): L = %d, kernel rows_grow_lanes_kernel_odd (%d cells of 2 orders), state in %d VGPRs, 0 bytes of LDS per wave, %d shifts before the last probe\n",
+                    lp.L, epgx_lanes_odd_cells(), 12 * epgx_lanes_odd_cells(), lp.rem0);
+        switch (n_spaces) {
+        case 0: return epgx_launch_rows_grow_lanes_odd_nsp0(stream, a, lp.rem0, lp.L);
+        case 1: return epgx_launch_rows_grow_lanes_odd_nsp1(stream, a, lp.rem0, lp.L);
+        case 2: return epgx_launch_rows_grow_lanes_odd_nsp2(stream, a, lp.rem0, lp.L);
+        default: return epgx_launch_rows_grow_lanes_odd_nsp4(stream, a, lp.rem0, lp.L);
+        }
+    }
     if (epgx::tracing()) {
         if (lanes)
             fprintf(stderr, "[epgx] run: variant lanes (one voxel per lane): L = %d, kernel %s (deck %d), %zu bytes of LDS per wave, %d shifts before the last probe, body %s\n",

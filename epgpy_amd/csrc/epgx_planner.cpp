@@ -374,7 +374,7 @@ LanesPlan lanes_plan(const std::vector<Rec> &grow, bool has_in, bool has_out, co
     if (kn.lanes <= 0) return refuse("EPGX_LANES=0");
     if (has_in || has_out) return refuse("a state input or output");
     if (grow.empty()) return refuse("no growing record list");
-    struct Exec { int d, rep; bool adc, body, lead; };
+    struct Exec { int d, rep; bool adc, body, lead, odd_echo; };
     std::vector<Exec> ex;
     size_t members = 0;
     for (const Rec &r : grow) {
@@ -396,7 +396,7 @@ LanesPlan lanes_plan(const std::vector<Rec> &grow, bool has_in, bool has_out, co
         if (f & F_ADC_Z) return refuse("a Z0 probe");
         if ((f & F_S) && !(f & F_FOLD) && r.shift != 1) return refuse(r.shift == -1 ? "S(-1)" : "a shift by more than one order");
         if ((f & F_T0) && !(f & F_T)) return refuse("a constant term without a rotation");
-        ex.push_back({((f & F_S0) ? 1 : 0) + ((f & F_S) ? 1 : 0), rep, (f & F_ADC) != 0, lanes_body_id(f, head) >= 0, (f & F_S0) != 0});
+        ex.push_back({((f & F_S0) ? 1 : 0) + ((f & F_S) ? 1 : 0), rep, (f & F_ADC) != 0, lanes_body_id(f, head) >= 0, (f & F_S0) != 0, lanes_odd_echo(f, head)});
     }
     // the shifts up to the last probe (a record shifts before it probes), then shift by shift: between two shifts the state
     // holds 1 + min(top, rem) live orders
@@ -424,6 +424,16 @@ LanesPlan lanes_plan(const std::vector<Rec> &grow, bool has_in, bool has_out, co
     for (const Exec &x : ex) {
         const bool head_rec = top == 0 && !x.lead && (x.d == 0 || x.rep == 1);
         if (!head_rec && !x.body) lp.train = false;
+        top += (long)x.d * x.rep;
+    }
+    // the odd class alone: every record behind the head records has both shifts and is the folded echo the kernel runs
+    // (lanes_odd_echo: the kernel skips anything else), starts at an even `top` (the head records have not shifted) and leaves
+    // an even `rem`
+    lp.odd = lp.train && lp.rem0 % 2 == 0;
+    top = 0;
+    for (const Exec &x : ex) {
+        const bool head_rec = top == 0 && !x.lead && (x.d == 0 || x.rep == 1);
+        if (head_rec ? x.d != 0 : !(x.lead && x.d == 2 && x.odd_echo)) lp.odd = false;
         top += (long)x.d * x.rep;
     }
     return lp;

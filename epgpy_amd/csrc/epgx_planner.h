@@ -34,6 +34,7 @@ struct Knobs {
     int lanes;      // EPGX_LANES: the one-voxel-per-lane variant of a FAM_ROWS_GROW launch (lanes_plan) -- 0 never, 1 from LANES_MIN_VOXELS voxels on, 2 whenever the list is eligible (tests)
     int lanes_body = 1;   // EPGX_LANES_BODY: the record bodies of that variant -- 1 (default) specialised and blocked where one exists, 0 the generic per-cell body everywhere.  The kernel's alone: no part of lanes_plan / lanes_selected
     int lanes_train = 1;  // EPGX_LANES_TRAIN: 1 (default) a train (LanesPlan::train) runs the kernel without a generic body on its larger deck, 0 every list runs the kernel with it.  lanes_plan reports `train` whatever this says; lanes_train_selected is the choice
+    int lanes_odd = 1;    // EPGX_LANES_ODD: the kernel of that variant that computes only the orders whose parity reaches an echo (LanesPlan::odd, rows_grow_lanes_kernel_odd) -- 0 never, 1 (default) for launches of LANES_MIN_VOXELS voxels and more, 2 whenever the list allows it (tests).  Only ever for a launch that lanes_selected already gives to the one-voxel-per-lane variant (EPGX_LANES) and lanes_train_selected to its train kernel: the knob never takes a launch from the rows variant.  lanes_plan reports `odd` whatever this says; lanes_odd_selected is the choice
 };
 // EPGX_TRACE is read per call (tests switch it on and off)
 inline bool tracing() { return getenv("EPGX_TRACE") != nullptr; }
@@ -132,6 +133,13 @@ void grow_reach(const std::vector<Rec> &list, int n1, int n2, int cap[3]);
 //             record executes before any shift has taken place (top == 0) and has no leading shift: it touches order 0 alone,
 //             whatever its kinds; a trailing shift (one execution then: the second would start at top == 1) only moves where its
 //             cell puts the result.  Such a list can run the instantiation of the kernel that has no generic body
+//   odd       a train that repeats S(+1) . X . S(+1) from an unshifted state: `train`; every record that is not a head record has
+//             a leading AND a trailing S(+1) and is the folded echo about x (lanes_odd_echo, epgx_lanes_bodies.h: checked on its own,
+//             whatever bodies the table holds); no head record shifts, so the
+//             first such record starts at top == 0; rem0 is even.  Between two pulses F moves by two orders, Z by none, and a
+//             rotation mixes one order: the orders that are odd when a pulse acts never exchange anything with the even ones, the
+//             excitation enters the odd class through the first shift and a probe (F0 behind the trailing shift, F-(1) at the pulse)
+//             reads it.  Such a list can run the kernel that computes the odd class alone (epgx_grow_lanes_odd_kernels.hip.h)
 constexpr int LANES_MAX_ORDERS = 24;
 constexpr int64_t LANES_MIN_VOXELS = 1 << 19;   // EPGX_LANES=1: the variant from this many voxels on (the crossover)
 struct LanesPlan {
@@ -139,6 +147,7 @@ struct LanesPlan {
     int L = 0, rem0 = 0;
     const char *why = "";
     bool train = false;
+    bool odd = false;
 };
 LanesPlan lanes_plan(const std::vector<Rec> &grow, bool has_in, bool has_out, const Knobs &kn);
 // the launcher's choice: the knob, the list and the size of the launch
@@ -149,6 +158,13 @@ inline bool lanes_selected(const LanesPlan &lp, int64_t nvox, const Knobs &kn) {
 // which kernel of the variant: the one without a generic body for a train, unless a knob asks for the other (EPGX_LANES_BODY=0
 // means the generic body for every record, and only the other kernel has it)
 inline bool lanes_train_selected(const LanesPlan &lp, const Knobs &kn) { return lp.eligible && lp.train && kn.lanes_train != 0 && kn.lanes_body != 0; }
+
+// which train runs the odd-class kernel.  1 gates on the size by itself: forced-lanes runs on small grids (EPGX_LANES=2) stay
+// on the train kernel unless EPGX_LANES_ODD=2 asks
+inline bool lanes_odd_selected(const LanesPlan &lp, int64_t nvox, const Knobs &kn) {
+    return lanes_selected(lp, nvox, kn) && lanes_train_selected(lp, kn) && lp.odd &&
+           (kn.lanes_odd >= 2 || (kn.lanes_odd == 1 && nvox >= LANES_MIN_VOXELS));
+}
 
 // pack_records, then in this order: run folding, the phases of rows_grow_kernel, the phases of run_contig_grow_kernel, the runs of
 // derivative plans
