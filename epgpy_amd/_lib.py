@@ -182,6 +182,7 @@ SYMBOLS = {
     "epgx_signal_project": (_i, [_p, _p, _i32, _p, _i64, _i32, _i64, _p, _i64]),
     "epgx_signal_norms_c64": (_i, [_p, _p, _i64, _i32, _i64, _p]),
     "epgx_signal_match_c64": (_i, [_p, _p, _i64, _p, _i64, _p, _i64, _i32, _i64, _i32, _p, _p, _p]),
+    "epgx_signal_refine": (_i, [_p, _p, _i64, _i64, _i32, _i32, _i32, _p, _i64, _p, _i64, _i64, _p, _p, _d, _p, _p, _p]),
     "epgx_simulate_f64": (_i, [_p, ctypes.POINTER(PlanDesc), _i32, _p, _p, _p, _p, _i32]),
     "epgx_simulate_sharded_f64": (_i, [ctypes.POINTER(PlanDesc), _i32, _i32, _p, _p, _i32]),
     "epgx_comm_unique_id": (_i, [_p]),
@@ -855,6 +856,57 @@ def signal_match(ctx, dict_ptr, dict_row_stride, norms_ptr, natoms, sig_ptr, sig
         return raw[2 * n:3 * n].view(np.int64), raw[:2 * n].view(np.complex128), raw[3 * n:]
     finally:
         out.free()         # (back to the context's pool)
+
+
+REFINE_SLICE, REFINE_MAX_SLICES = 16, 8      # csrc/epgx_refine.h
+
+
+def refine_slices(nrec):
+    """the slices `epgx_signal_refine` cuts the records of a voxel into (include/epgx.h): a function of nrec alone"""
+    s = 1
+    while s < REFINE_MAX_SLICES and s * REFINE_SLICE < int(nrec):
+        s *= 2
+    return s
+
+
+def signal_refine(ctx, jac_ptr, record_stride, row_stride, nrow, nrec, rows, natoms, sig_ptr, sig_row_stride, nmeas, index,
+                  limit=None, rcond=1e-10):
+    """epgx_signal_refine: one Gauss-Newton step at the matched atom of every measured voxel, from a dictionary and its Jacobian
+    in device memory (atom a of row r of record t at jac_ptr + 16 * (t * record_stride + r * row_stride + a), row 0 the
+    dictionary, rows[p] >= 1 the chosen columns; signals as for `signal_match`).  `index`: int64 [nmeas] on the host, uploaded at
+    8 bytes per voxel, or the address of such an array in device memory.  Returns (delta float64 [len(rows), nmeas], scale
+    complex128 [nmeas], score float64 [nmeas]); only these 8 P + 24 bytes per voxel cross PCIe"""
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    lim = None if limit is None else np.ascontiguousarray(limit, dtype=np.float64)
+    if rows.ndim != 1 or (lim is not None and lim.shape != rows.shape):
+        raise ValueError(f"signal_refine: rows {rows.shape} and limit {None if lim is None else lim.shape} do not fit together")
+    nmeas, P = int(nmeas), len(rows)
+    n = max(nmeas, 1)
+    ibuf = None
+    if isinstance(index, np.ndarray):
+        host = np.ascontiguousarray(index, dtype=np.int64)
+        if host.shape != (nmeas,):
+            raise ValueError(f"signal_refine: index {host.shape} for {nmeas} voxels")
+        ibuf = DeviceBuffer(ctx, 8 * n, itemsize=8)
+        if nmeas:
+            ibuf.upload(host)
+        index = ibuf.ptr.value
+    out = DeviceBuffer(ctx, (24 + 8 * P) * n, itemsize=8)      # scale [nmeas] complex128, then delta [P][nmeas], then score [nmeas]
+    try:
+        check(ctx.lib.epgx_signal_refine(ctx.handle, ctypes.c_void_p(jac_ptr) if jac_ptr else None, int(record_stride), int(row_stride),
+                                         int(nrow), int(nrec), P, rows.ctypes.data, int(natoms),
+                                         ctypes.c_void_p(sig_ptr) if sig_ptr else None, int(sig_row_stride), nmeas,
+                                         ctypes.c_void_p(index) if index else None, lim.ctypes.data if lim is not None else None,
+                                         float(rcond), ctypes.c_void_p(out.ptr.value + 16 * n), out.ptr,
+                                         ctypes.c_void_p(out.ptr.value + (16 + 8 * P) * n)), "epgx_signal_refine")
+        if nmeas == 0:
+            return np.empty((P, 0), np.float64), np.empty(0, np.complex128), np.empty(0, np.float64)
+        raw = out.download(np.float64, ((3 + P) * n,))
+        return raw[2 * n:(2 + P) * n].reshape(P, n), raw[:2 * n].view(np.complex128), raw[(2 + P) * n:]
+    finally:
+        out.free()         # (back to the context's pool; stream-ordered behind the kernel)
+        if ibuf is not None:
+            ibuf.free()
 
 
 GRAM_BLOCK, GRAM_WORKGROUPS, GRAM_MIN_ATOMS = 64, 2048, 1024      # csrc/epgx_compress.h

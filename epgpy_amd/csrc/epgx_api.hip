@@ -50,6 +50,7 @@
 #include "epgx_match.h"
 #include "epgx_match32.h"
 #include "epgx_compress.h"
+#include "epgx_refine.h"
 #include "epgx_merge.h"
 #include "epgx_prune.h"
 #include "epgx_launch_grow.h"
@@ -1158,6 +1159,66 @@ extern "C" int epgx_signal_match_c64(epgx_ctx *ctx, const void *dict, int64_t di
         e = epgx_launch_match32_merge(ctx->stream, g);
     }
     dev_free(ctx, part);      // (stream-ordered: the block is recycled behind the kernels that use it)
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return EPGX_OK;
+}
+
+// ------------------------------------------------------------------------------ Gauss-Newton refinement (epgx_refine.hip)
+extern "C" int epgx_signal_refine(epgx_ctx *ctx, const void *jac, int64_t record_stride, int64_t row_stride, int32_t nrow, int32_t nrec,
+                                  int32_t nparam, const int32_t *rows, int64_t natoms, const void *sig, int64_t sig_row_stride,
+                                  int64_t nmeas, const void *index, const double *limit, double rcond, void *out_delta, void *out_scale,
+                                  void *out_score) {
+    const char *who = "epgx_signal_refine";
+    if (!ctx || !jac || !rows || !sig || !index || !out_delta || !out_scale || !out_score) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
+    if (((uintptr_t)jac & 15) || ((uintptr_t)sig & 15) || ((uintptr_t)out_scale & 15) || ((uintptr_t)index & 7) ||
+        ((uintptr_t)out_delta & 7) || ((uintptr_t)out_score & 7))
+        return fail(EPGX_ERR_INVALID, "%s: jac, sig and out_scale must be aligned to 16 bytes, index, out_delta and out_score to 8", who);
+    if (nparam < 1 || nparam > REFINE_MAX_P) return fail(EPGX_ERR_INVALID, "%s: nparam = %d not in [1, %d]", who, nparam, REFINE_MAX_P);
+    if (nrec < 1 || nrow < 1) return fail(EPGX_ERR_INVALID, "%s: nrec = %d, nrow = %d: both must be >= 1", who, nrec, nrow);
+    if (natoms < 1 || nmeas < 0) return fail(EPGX_ERR_INVALID, "%s: natoms = %lld (>= 1), nmeas = %lld (>= 0)", who, (long long)natoms, (long long)nmeas);
+    if (row_stride < 1 || natoms > row_stride)
+        return fail(EPGX_ERR_INVALID, "%s: %lld atoms outside a row of %lld", who, (long long)natoms, (long long)row_stride);
+    if (record_stride / nrow < row_stride)
+        return fail(EPGX_ERR_INVALID, "%s: record_stride = %lld holds fewer than nrow = %d rows of %lld", who, (long long)record_stride, nrow,
+                    (long long)row_stride);
+    int64_t span, last;      // elements from `jac` to the end of the last record: must be expressible (the kernel's pointer arithmetic)
+    if (__builtin_mul_overflow((int64_t)(nrec - 1), record_stride, &span) || __builtin_mul_overflow((int64_t)nrow, row_stride, &last) ||
+        __builtin_add_overflow(span, last, &span) || span > INT64_MAX / 16)
+        return fail(EPGX_ERR_INVALID, "%s: nrec = %d records of record_stride = %lld elements overflow the address range", who, nrec,
+                    (long long)record_stride);
+    if (!match_extent_ok(nrec, sig_row_stride, nmeas))
+        return fail(EPGX_ERR_INVALID, "%s: %d records of sig_row_stride = %lld do not hold %lld voxels each (or overflow the address range)", who,
+                    nrec, (long long)sig_row_stride, (long long)nmeas);
+    if (nmeas / 64 >= 0x7fffffff) return fail(EPGX_ERR_INVALID, "%s: %lld voxels in one call", who, (long long)nmeas);
+    if (!(rcond >= 0.0 && rcond < 1.0)) return fail(EPGX_ERR_INVALID, "%s: rcond = %g not in [0, 1)", who, rcond);
+    RefineArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int c = 0; c < nparam; ++c) {
+        if (rows[c] < 1 || rows[c] >= nrow)
+            return fail(EPGX_ERR_INVALID, "%s: rows[%d] = %d not in [1, nrow = %d) (row 0 is the state)", who, c, rows[c], nrow);
+        for (int k = 0; k < c; ++k)
+            if (rows[k] == rows[c]) return fail(EPGX_ERR_INVALID, "%s: rows[%d] = rows[%d] = %d: a repeated row", who, k, c, rows[c]);
+        if (limit && !(limit[c] > 0.0)) return fail(EPGX_ERR_INVALID, "%s: limit[%d] = %g is not positive", who, c, limit[c]);
+        a.rows[c] = rows[c];
+        a.limit[c] = limit ? limit[c] : (double)INFINITY;
+    }
+    if (nmeas == 0) return EPGX_OK;
+    if (int rc = set_device(ctx)) return rc;
+    a.jac = (const d2 *)jac;
+    a.record_stride = record_stride;
+    a.row_stride = row_stride;
+    a.nrec = nrec;
+    a.natoms = natoms;
+    a.sig = (const d2 *)sig;
+    a.sig_stride = sig_row_stride;
+    a.nmeas = nmeas;
+    a.index = (const int64_t *)index;
+    a.rcond = rcond;
+    refine_slices(nrec, &a.slices, &a.slice_len);
+    a.delta = (double *)out_delta;
+    a.scale = (d2 *)out_scale;
+    a.score = (double *)out_score;
+    hipError_t e = epgx_launch_refine(ctx->stream, nparam, a);
     if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return EPGX_OK;
 }

@@ -42,12 +42,49 @@ inner product, about nrec 2^-22 sum_t |D||S| at most.
 Dictionaries: a `DeviceSignal` over the whole grid on one GPU (any probe of its buffer), a `DeviceJacobian` (its probed-state
 row), or a NumPy array `[nrec, *grid]` (uploaded once).  Signals: a NumPy array `[nrec, *shape]` (real or complex; uploaded as
 complex128) or a whole `DeviceSignal` on the same device.  Dictionaries of a run over several GPUs raise `NotImplementedError`.
+
+Off the grid (`refine`, csrc/epgx_refine.hip through `epgx_signal_refine`): a match ends at a grid point; one variable-projection
+Gauss-Newton step at the matched atom, from the derivative rows of a `DeviceJacobian` that lie in HBM next to the dictionary,
+moves it between the grid points,
+
+    res = match.match(jac, signals)            # jac = simulate(..., probe=epg.Jacobian([...]), out="device")
+    ref = match.refine(jac, signals, res)      # .delta, .scale, .score, .estimate([T1, T2])
+
+For measured voxel `m` with atom `a = index[m]`: `d_t = D[t,a]`, `j_pt = J_p[t,a]` for `p < P`, `s_t = S[t,m]`, all complex128;
+`P` = 1 ... 4 chosen columns of the Jacobian.  Accumulated over the records:
+
+    n = sum |d|^2 (real)    E = sum |s|^2 (real)    c = sum conj(d) s    b_p = sum conj(j_p) s    h_p = sum conj(d) j_p
+    M_pq = sum conj(j_p) j_q   (Hermitian, M_pp real; only Re M_pq enters below)
+
+From those, per voxel and in float64:
+
+    rho   = c / n                                       (match's scale, recomputed here from the same records)
+    N_pq  = |rho|^2 Re(M_pq - conj(h_p) h_q / n)         Gauss-Newton matrix of  min over real delta of ||s - rho (d + J delta)||^2,
+    y_p   = Re(conj(rho) (b_p - rho conj(h_p)))         rho projected out (Kaufman's variable projection)
+    Nhat_pq = N_pq / (|rho|^2 sqrt(M_pp M_qq))           equilibrated by the UNPROJECTED column norms: pivots in [0, 1]
+    delta = solution of N delta = y by Cholesky of Nhat
+    delta_p clipped to +-limit_p where a limit is given
+    num   = c + sum_p delta_p b_p
+    den   = n + 2 sum_p delta_p Re h_p + sum_pq delta_p delta_q Re M_pq
+    scale' = num / den
+    score' = |num| / sqrt(den E)                        of the LINEARISED atom d + J delta (0 where E = 0)
+
+(Nhat is evaluated as Re(M_pq - conj(h_p) h_q / n) / sqrt(M_pp M_qq); where |rho|^2 is zero or not finite -- an all-zero signal --
+the quotient above is 0 / 0 and every pivot counts as not finite.)  A voxel is UNRESOLVED where `index` lies outside
+`[0, natoms)`, -1 included, where `n` or an `M_pp` is zero or not finite, or where a Cholesky pivot of `Nhat` (the diagonal entry
+before its root) is `<= rcond` or not finite.  `rcond` is a documented condition like `lstsq`'s: a pivot of 1e-10 means a Jacobian
+column lies within 1e-5 rad of the span of `d` and the earlier columns.  An unresolved voxel gets NaN in every `delta_p`,
+`scale' = rho` and `score'` = the unrefined score; where `index` is invalid scale 0 and score 0.  Never an error, and no atom
+outside `[0, natoms)` is read.  A voxel's bits depend on its own signal, its atom's columns, nrec and the arguments only.
+`refine_host` states the same formulas in NumPy on host arrays; it is the definition the tests hold, not a path of `refine`.
 """
 import numpy as np
 
-__all__ = ["Dictionary", "MatchResult", "match", "Basis", "compress", "gram_basis", "select_rank", "MAX_RANK"]
+__all__ = ["Dictionary", "MatchResult", "match", "Basis", "compress", "gram_basis", "select_rank", "MAX_RANK",
+           "RefineResult", "refine", "refine_host", "MAX_REFINE_PARAMS"]
 
 MAX_RANK = 64          # basis vectors `epgx_signal_project` takes
+MAX_REFINE_PARAMS = 4  # REFINE_MAX_P of csrc/epgx_refine.h
 
 
 def _dtype(dtype, name):
@@ -80,6 +117,11 @@ def _signal_handle(arg, name):
                                       "match takes handles that cover the whole grid on one GPU")
         return arg
     return None
+
+
+def _is_jacobian(arg):
+    from . import functions
+    return isinstance(arg, functions.DeviceJacobian)
 
 
 class _Records:
@@ -166,6 +208,7 @@ class Dictionary:
         self._rec = rec
         self.grid, self.natoms, self.nrec, self.device, self.dtype = rec.shape, rec.ncol, rec.nrec, rec.device, rec.dtype
         self.basis = None          # the `Basis` of a dictionary that `compress` made
+        self.jacobian = handle if _is_jacobian(handle) else None      # the DeviceJacobian it was built from (`refine`)
         self._norms = _lib.signal_norms(rec.ctx, rec.ptr, rec.row_stride, rec.nrec, rec.ncol, c64=self.dtype == np.complex64)
 
     @property
@@ -437,3 +480,242 @@ def compress(dictionary, rank=None, energy=None, *, nsplit=0, device=None, dtype
         out.free()
     cdic.basis, basis.dictionary = basis, cdic
     return basis
+
+
+# ------------------------------------------------------------------------------------------------ Gauss-Newton refinement
+class RefineResult:
+    """`delta` float64 `[*shape, P]` (NaN where unresolved), `scale` complex128 and `score` float64 of the linearised atom, `index`
+    int64 (the atoms the step started from), all over the shape of the measured voxels; `variables` the P chosen columns, `grid`
+    the dictionary's grid"""
+
+    def __init__(self, delta, scale, score, index, variables, grid):
+        self.delta, self.scale, self.score, self.index = delta, scale, score, index
+        self.variables, self.grid = list(variables), tuple(grid)
+
+    def estimate(self, values):
+        """the refined parameters `values[p][index] + delta[..., p]` as float64 `[*shape, P]`, NaN where unresolved.
+        values: P arrays, each broadcastable to the grid, that hold the parameter of every atom (in the order of `variables`)"""
+        values = list(values)
+        if len(values) != len(self.variables):
+            raise ValueError(f"estimate: {len(values)} arrays of values for the {len(self.variables)} variables {self.variables}")
+        none = (self.index < 0) | (self.index >= int(np.prod(self.grid, dtype=np.int64)))
+        at = np.where(none, 0, self.index)
+        out = np.empty(self.delta.shape, dtype=np.float64)
+        for p, val in enumerate(values):
+            flat = np.broadcast_to(np.asarray(val, dtype=np.float64), self.grid).reshape(-1)
+            out[..., p] = np.where(none, np.nan, flat[at]) + self.delta[..., p]
+        return out
+
+
+def _refine_limit(limit, nparam):
+    """limit as float64 [nparam] of positive numbers (a scalar holds for every column, None entries and +Inf: no limit), or None"""
+    if limit is None:
+        return None
+    if np.ndim(limit) == 0:
+        limit = [limit] * nparam
+    lim = np.array([np.inf if v is None else v for v in limit], dtype=np.float64)
+    if lim.shape != (nparam,):
+        raise ValueError(f"limit: {lim.shape[0] if lim.ndim == 1 else lim.shape} values for {nparam} variables")
+    if not np.all(lim > 0):
+        raise ValueError(f"limit: {lim.tolist()}; every limit must be positive (None or inf for none)")
+    return lim
+
+
+def _refine_rcond(rcond):
+    if np.ndim(rcond) != 0 or not 0.0 <= float(rcond) < 1.0:
+        raise ValueError(f"rcond: {rcond!r} not in [0, 1)")
+    return float(rcond)
+
+
+def _refine_index(result, shape, grid, natoms):
+    """the atoms as int64 of the signals' shape, from a MatchResult or an int array; ValueError for values < -1 or >= natoms"""
+    if isinstance(result, (MatchResult, RefineResult)):
+        if tuple(result.grid) != tuple(grid):
+            raise ValueError(f"result: matched against the grid {tuple(result.grid)}, the dictionary has {tuple(grid)}")
+        result = result.index
+    idx = np.asarray(result)
+    if idx.dtype.kind not in "iu":
+        raise ValueError(f"result: a MatchResult or an array of integer indices, got {idx.dtype}")
+    if idx.shape != tuple(shape):
+        raise ValueError(f"result: indices of shape {idx.shape}, the signals have {tuple(shape)}")
+    idx = np.ascontiguousarray(idx, dtype=np.int64)
+    if idx.size and (idx.min() < -1 or idx.max() >= natoms):
+        raise ValueError(f"result: indices in [{idx.min()}, {idx.max()}]; -1 (no atom) .. {natoms - 1} are valid")
+    return idx
+
+
+def _refine_columns(variables, known):
+    """positions in `known` of the chosen `variables` (None: all), 1 .. MAX_REFINE_PARAMS of them, each once"""
+    chosen = list(known) if variables is None else list(variables)
+    for v in chosen:
+        if v not in known:
+            raise ValueError(f"variables: {v!r} is not a column of the Jacobian, {list(known)}")
+    if len(set(map(repr, chosen))) != len(chosen):
+        raise ValueError(f"variables: {chosen} names a column twice")
+    if not 1 <= len(chosen) <= MAX_REFINE_PARAMS:
+        raise NotImplementedError(f"variables: {len(chosen)} columns; refine takes 1 .. {MAX_REFINE_PARAMS} -- choose them with "
+                                  "variables=, or download the Jacobian (np.asarray) and use refine_host for more")
+    return chosen, [list(known).index(v) for v in chosen]
+
+
+def _refine_source(dictionary, jacobian):
+    """the DeviceJacobian behind `dictionary`, or None for host arrays; raises for what `refine` does not take"""
+    from . import functions
+    if isinstance(dictionary, Dictionary):
+        if dictionary.basis is not None:
+            raise NotImplementedError("dictionary: a compressed dictionary holds no derivative rows; refine on the uncompressed "
+                                      "DeviceJacobian with the indices of the compressed match")
+        if dictionary.dtype != np.complex128:
+            raise NotImplementedError("dictionary: a complex64 dictionary; refine runs in float64 on the complex128 DeviceJacobian "
+                                      "-- pass that (the indices of a complex64 match are valid for it)")
+        if dictionary.jacobian is None:
+            raise ValueError("dictionary: this Dictionary was not built from a DeviceJacobian and holds no derivative rows")
+        dictionary = dictionary.jacobian
+    if isinstance(dictionary, functions.ShardedDeviceSignal):
+        raise NotImplementedError("dictionary: a ShardedDeviceSignal (a run over several GPUs); refine takes the DeviceJacobian of a "
+                                  "run on one GPU -- download it (np.asarray) or simulate the dictionary on one device")
+    if isinstance(dictionary, functions.DeviceHessian):
+        raise NotImplementedError("dictionary: a DeviceHessian holds second derivatives; refine takes the DeviceJacobian of the run "
+                                  "(probe=epg.Jacobian([...]))")
+    if isinstance(dictionary, functions.DeviceSignal):
+        raise ValueError("dictionary: a DeviceSignal holds no derivative rows; simulate with probe=epg.Jacobian([...]) or pass host "
+                         "arrays with jacobian=")
+    if isinstance(dictionary, functions.DeviceJacobian):
+        if jacobian is not None:
+            raise ValueError("jacobian=: goes with a dictionary on the host; a DeviceJacobian brings its own derivative rows")
+        return dictionary
+    if jacobian is None:
+        raise ValueError("jacobian=: a dictionary on the host needs its derivatives, a NumPy array [nrec, *grid, P]")
+    return None
+
+
+def refine(dictionary, signals, result, *, jacobian=None, variables=None, limit=None, rcond=1e-10):
+    """one Gauss-Newton step off the grid at the matched atom of every measured voxel (module docstring), on the device.
+
+    dictionary: a `DeviceJacobian`; a `Dictionary` built from one (its `.jacobian`); or a NumPy array `[nrec, *grid]` together
+    with jacobian= NumPy `[nrec, *grid, P]` -- the two are uploaded once into one buffer in the `[record][row][atom]` layout.
+    signals: as for `match`.  result: the `MatchResult` of these signals, or an int array of their shape (flat atom indices, -1:
+    none); a value < -1 or >= natoms raises ValueError.
+    variables: the columns to step in, a subset of the handle's `variables` in any order (host arrays: of 0 .. P - 1); default
+    all of them -- "magnitude" apart, which is the probed state itself (the complex scale carries it) and raises ValueError
+    when named.  1 .. 4, else NotImplementedError.  limit: None, one positive number, or one per variable (None / inf: no
+    limit): |delta_p| <= limit_p.  rcond: the smallest Cholesky pivot of the equilibrated matrix that counts as resolved.
+    The index goes up at 8 bytes per voxel and 8 P + 24 bytes per voxel come back; dictionary and Jacobian do not move.
+    NotImplementedError, naming the way out, for a compressed or complex64 `Dictionary`, a ShardedDeviceSignal, a DeviceHessian.
+    Returns a `RefineResult`."""
+    from . import _lib
+    handle = _refine_source(dictionary, jacobian)
+    rcond = _refine_rcond(rcond)
+    sig = _Records(signals, "signals")
+    if handle is not None:
+        # (a column at row 0, "magnitude", is the probed state itself: rho carries it already and the step leaves it out)
+        known = list(handle.variables)
+        chosen, cols = _refine_columns([v for v, r in zip(known, handle.rows) if r > 0] if variables is None else variables, known)
+        rows = [handle.rows[c] for c in cols]
+        if 0 in rows:
+            raise ValueError(f"variables: {chosen[rows.index(0)]!r} is the probed state itself, not a derivative; the complex scale "
+                             "of the result carries it")
+        nrec, grid, natoms = handle.nrec, tuple(handle.grid), handle.nvox
+    else:
+        D, J = np.asarray(dictionary), np.asarray(jacobian)
+        if D.ndim < 2 or D.dtype.kind not in "fciub" or J.dtype.kind not in "fciub" or J.shape[:-1] != D.shape:
+            raise ValueError(f"dictionary [nrec, *grid] and jacobian [nrec, *grid, P]: got shapes {D.shape} and {J.shape}")
+        if 0 in J.shape:
+            raise ValueError(f"jacobian: shape {J.shape}; records, atoms and columns must be at least 1 each")
+        chosen, cols = _refine_columns(variables, list(range(J.shape[-1])))
+        rows = [1 + p for p in range(len(cols))]
+        nrec, grid = D.shape[0], tuple(D.shape[1:])
+        natoms = int(np.prod(grid, dtype=np.int64))
+    if sig.nrec != nrec:
+        raise ValueError(f"signals: {sig.nrec} records, the dictionary has {nrec}")
+    lim = _refine_limit(limit, len(chosen))
+    index = _refine_index(result, sig.shape, grid, natoms)
+
+    if handle is not None:
+        buf = handle._buf
+        ctx = buf.ctx
+        if sig.device is not None and (sig.device != handle.device or sig.ctx is not ctx):
+            raise ValueError(f"signals: on device {sig.device}, the dictionary on device {handle.device}; both must be on one GPU (and context)")
+        # (a handle whose buffer was freed hands over NULL: the library's EpgxError, as for a download)
+        own, ptr, record_stride, row_stride, nrow = None, handle.ptr if buf.ptr else None, handle.record_stride, handle.row_stride, handle._nrow
+    else:
+        ctx = sig.ctx if sig.ctx is not None else _lib.get_context(None)
+        host = np.empty((nrec, 1 + len(cols), natoms), dtype=np.complex128)
+        host[:, 0] = D.reshape(nrec, natoms)
+        host[:, 1:] = np.moveaxis(J.reshape(nrec, natoms, -1)[:, :, cols], 2, 1)
+        own = _lib.DeviceBuffer(ctx, host.nbytes)
+        own.upload(host)
+        ptr, record_stride, row_stride, nrow = own.ptr.value, (1 + len(cols)) * natoms, natoms, 1 + len(cols)
+    sig.upload(ctx)
+    try:
+        delta, scale, score = _lib.signal_refine(ctx, ptr, record_stride, row_stride, nrow, nrec, rows, natoms, sig.ptr, sig.row_stride,
+                                                 sig.ncol, index.reshape(-1), limit=lim, rcond=rcond)
+    finally:
+        if isinstance(sig.keep, _lib.DeviceBuffer):
+            sig.keep.free()        # (stream-ordered: the block is recycled behind the kernel that reads it)
+        if own is not None:
+            own.free()
+    return RefineResult(np.ascontiguousarray(delta.T).reshape(sig.shape + (len(chosen),)), scale.reshape(sig.shape).copy(),
+                        score.reshape(sig.shape).copy(), index, chosen, grid)
+
+
+def refine_host(D, J, S, index, limit=None, rcond=1e-10):
+    """the formulas of `refine` (module docstring) in NumPy float64 on host arrays: the documented definition.  Not a path of
+    `refine`, which never calls it.
+
+    D `[nrec, *grid]`, J `[nrec, *grid, P]` (any P), S `[nrec, *shape]`, index int `[*shape]` (values outside [0, natoms) come
+    back unresolved), limit and rcond as for `refine`.  Returns a `RefineResult` (`variables` = 0 .. P - 1)."""
+    D, J, S = np.asarray(D, dtype=np.complex128), np.asarray(J, dtype=np.complex128), np.asarray(S, dtype=np.complex128)
+    if D.ndim < 2 or J.shape[:-1] != D.shape or S.ndim < 1 or S.shape[0] != D.shape[0]:
+        raise ValueError(f"refine_host: D [nrec, *grid], J [nrec, *grid, P], S [nrec, *shape]: got {D.shape}, {J.shape}, {S.shape}")
+    nrec, grid, shape, P = D.shape[0], D.shape[1:], S.shape[1:], J.shape[-1]
+    natoms = int(np.prod(grid, dtype=np.int64))
+    idx = np.asarray(index, dtype=np.int64)
+    if idx.shape != shape:
+        raise ValueError(f"refine_host: indices of shape {idx.shape}, the signals have {shape}")
+    lim = _refine_limit(limit, P)
+    rcond = _refine_rcond(rcond)
+    flat = idx.reshape(-1)
+    valid = (flat >= 0) & (flat < natoms)
+    at = np.where(valid, flat, 0)
+    d = D.reshape(nrec, natoms)[:, at]                         # [nrec, nmeas]
+    j = J.reshape(nrec, natoms, P)[:, at, :]                   # [nrec, nmeas, P]
+    s = S.reshape(nrec, -1)
+    with np.errstate(all="ignore"):
+        n = (d.real ** 2 + d.imag ** 2).sum(axis=0)
+        E = (s.real ** 2 + s.imag ** 2).sum(axis=0)
+        c = (np.conj(d) * s).sum(axis=0)
+        b = np.einsum("tmp,tm->mp", np.conj(j), s)
+        h = np.einsum("tm,tmp->mp", np.conj(d), j)
+        M = np.einsum("tmp,tmq->mpq", np.conj(j), j).real
+        rho = c / n
+        rho2 = rho.real ** 2 + rho.imag ** 2
+        score0 = np.where(E == 0, 0.0, np.abs(c) / (np.sqrt(n) * np.sqrt(E)))
+        mpp = np.einsum("mpp->mp", M)
+        ok = valid & (n > 0) & np.isfinite(n) & (rho2 > 0) & np.isfinite(rho2) & np.all((mpp > 0) & np.isfinite(mpp), axis=1)
+        sd = np.sqrt(mpp)
+        A = M - (np.conj(h)[:, :, None] * h[:, None, :]).real / n[:, None, None]
+        L = A / (sd[:, :, None] * sd[:, None, :])               # Nhat, factored in place below (lower triangle)
+        y = (np.conj(rho)[:, None] * (b - rho[:, None] * np.conj(h))).real
+        z = y / (rho2[:, None] * sd)
+        for q in range(P):
+            piv = L[:, q, q] - (L[:, q, :q] ** 2).sum(axis=1)
+            ok &= (piv > rcond) & np.isfinite(piv)
+            L[:, q, q] = np.sqrt(piv)
+            for p in range(q + 1, P):
+                L[:, p, q] = (L[:, p, q] - (L[:, p, :q] * L[:, q, :q]).sum(axis=1)) / L[:, q, q]
+        for p in range(P):
+            z[:, p] = (z[:, p] - (L[:, p, :p] * z[:, :p]).sum(axis=1)) / L[:, p, p]
+        for p in range(P - 1, -1, -1):
+            z[:, p] = (z[:, p] - (L[:, p + 1:, p] * z[:, p + 1:]).sum(axis=1)) / L[:, p, p]
+        delta = z / sd
+        if lim is not None:
+            delta = np.where(delta > lim, lim, np.where(delta < -lim, -lim, delta))
+        num = c + (delta * b).sum(axis=1)
+        den = n + 2 * (delta * h.real).sum(axis=1) + np.einsum("mp,mq,mpq->m", delta, delta, M)
+        scale = np.where(ok, num / den, rho)
+        score = np.where(ok, np.where(E == 0, 0.0, np.abs(num) / (np.sqrt(den) * np.sqrt(E))), score0)
+    delta = np.where(ok[:, None], delta, np.nan)
+    scale = np.where(valid, scale, 0.0)
+    score = np.where(valid, score, 0.0)
+    return RefineResult(delta.reshape(shape + (P,)), scale.reshape(shape), score.reshape(shape), idx, list(range(P)), grid)

@@ -742,6 +742,49 @@ int epgx_signal_match_c64(epgx_ctx *ctx, const void *dict, int64_t dict_row_stri
                           const void *sig, int64_t sig_row_stride, int32_t nrec, int64_t nmeas, int32_t nsplit,
                           void *out_index, void *out_scale, void *out_score);
 
+/* One variable-projection Gauss-Newton step off the grid (csrc/epgx_refine.hip; within ABI 11): the consumer of the derivative
+ * rows of a Jacobian left in HBM by simulate(..., probe=Jacobian, out="device").  For measured voxel m with atom a = index[m]:
+ *   d_t = D[t,a] = jac[t * record_stride + a],   j_pt = J_p[t,a] = jac[t * record_stride + rows[p] * row_stride + a],  p < P = nparam,
+ *   s_t = S[t,m] = sig[t * sig_row_stride + m],  all complex128, strides in elements of 16 bytes.
+ * Accumulated over the records:
+ *   n = sum |d|^2 (real)    E = sum |s|^2 (real)    c = sum conj(d) s    b_p = sum conj(j_p) s    h_p = sum conj(d) j_p
+ *   M_pq = sum conj(j_p) j_q   (Hermitian, M_pp real; only Re M_pq enters below and only that is accumulated)
+ * From those, per voxel and in float64:
+ *   rho   = c / n                                       (match's scale, recomputed here from the same records)
+ *   N_pq  = |rho|^2 Re(M_pq - conj(h_p) h_q / n)         Gauss-Newton matrix of  min over real delta of ||s - rho (d + J delta)||^2,
+ *   y_p   = Re(conj(rho) (b_p - rho conj(h_p)))         rho projected out (Kaufman's variable projection)
+ *   Nhat_pq = N_pq / (|rho|^2 sqrt(M_pp M_qq))           equilibrated by the UNPROJECTED column norms: pivots in [0, 1]
+ *   delta = solution of N delta = y by Cholesky of Nhat
+ *   delta_p clipped to +-limit_p where a limit is given
+ *   num   = c + sum_p delta_p b_p
+ *   den   = n + 2 sum_p delta_p Re h_p + sum_pq delta_p delta_q Re M_pq
+ *   scale' = num / den
+ *   score' = |num| / sqrt(den E)                        of the LINEARISED atom d + J delta (0 where E = 0)
+ * (Nhat is evaluated as Re(M_pq - conj(h_p) h_q / n) / sqrt(M_pp M_qq); where |rho|^2 is zero or not finite -- an all-zero
+ * signal -- the quotient above is 0 / 0 and every pivot counts as not finite.)
+ * A voxel is UNRESOLVED where index[m] lies outside [0, natoms) (-1 included), where n or an M_pp is zero or not finite, or where a
+ * Cholesky pivot of Nhat (the diagonal entry before its root) is <= rcond or not finite.  It gets NaN in every delta_p, scale' =
+ * rho and score' = the unrefined score |c| / sqrt(n E) (0 where E = 0); where the index is invalid scale 0 and score 0.  Never an
+ * error.  The kernel never reads an atom outside [0, natoms); a voxel with an invalid index loads nothing.
+ * rcond: a pivot of 1e-10 means a Jacobian column lies within 1e-5 rad of the span of d and the earlier columns.
+ * Invariance: the records are cut into 1 (nrec <= 16), 2 (<= 32), 4 (<= 64) or 8 slices by nrec alone and the slices are added
+ * in ascending order, so the bits of a voxel's result depend on its own column of S, its atom's columns, nrec and the arguments
+ * -- not on nmeas, the voxel's place in the call, or other voxels.
+ *   jac       : DEVICE, at row 0 (the probed state) of record 0 of the probe: [record][row][atom], record_stride >= nrow * row_stride,
+ *               row_stride >= natoms (the layout and stride checks of epgx_signal_crlb)
+ *   rows      : host [nparam], the row of every chosen column, 1 .. nrow - 1, each once, in any order; nparam = 1 .. 4
+ *   index     : DEVICE int64 [nmeas]
+ *   limit     : host [nparam] of positive numbers (+Inf allowed), or NULL for no clipping;  rcond in [0, 1)
+ *   out_delta : DEVICE float64 [nparam][nmeas];  out_scale : DEVICE complex128 [nmeas];  out_score : DEVICE float64 [nmeas]
+ * Stream-ordered; nothing is uploaded or synchronised.
+ * Errors (nothing is launched): EPGX_ERR_INVALID for a NULL (limit apart) or misaligned pointer (16 bytes: jac, sig, out_scale; 8:
+ * the others), nparam outside [1, 4], nrec < 1, nrow < 1, natoms < 1, nmeas < 0, row_stride < natoms, record_stride < nrow *
+ * row_stride, sig_row_stride < nmeas, an extent that overflows, rows[c] < 1 (row 0 is the state) or >= nrow, a repeated row, a
+ * limit that is not positive, rcond outside [0, 1).  nmeas = 0: nothing to do. */
+int epgx_signal_refine(epgx_ctx *ctx, const void *jac, int64_t record_stride, int64_t row_stride, int32_t nrow, int32_t nrec,
+                       int32_t nparam, const int32_t *rows, int64_t natoms, const void *sig, int64_t sig_row_stride, int64_t nmeas,
+                       const void *index, const double *limit, double rcond, void *out_delta, void *out_scale, void *out_score);
+
 /* Convenience for bindings that only have host arrays (what a ctypes/NumPy binding inside
  * the reference would call once per simulate()): builds the plan, runs the whole sequence
  * state-resident over the full grid, copies signal (and optionally the final state) back. */
