@@ -219,15 +219,41 @@ class _Marker(Operator):
         enc.add(self.OPCODE)
         enc.note(self.NOTE)
 
+    def __call__(self, sm, *, inplace=False):
+        """op(sm, inplace=True) on a state matrix that carries derivative states (sm.order1 / sm.order2): what a derivative
+        plan does.  (Not in place, a plain operator returns a copy without derivative states, as before.)"""
+        carried = getattr(sm, "order1", None) or getattr(sm, "order2", None)
+        rows = getattr(sm, "_kspace", None)
+        out = super().__call__(sm, inplace=inplace)
+        if carried and out is sm:
+            self._derivatives(out, rows)
+        return out
+
+    def _derivatives(self, out, rows):
+        pass
+
 
 class Spoiler(_Marker):
     """perfect spoiler: transverse magnetisation <- 0 (operator.py:281-286)"""
     OPCODE, NOTE = _lib.OP_SPOIL, "spoil"
 
+    def _derivatives(self, out, rows):
+        # the derivative states are not spoiled (the default of a derivative plan): their transverse rows stay populated, so the
+        # state keeps its rows too -- S moves the state and its derivative states by one table each, and T adds (dOp/dp)(S) to
+        # dS row by row (plan.py Encoder.note does the same for a compiled derivative plan)
+        now = getattr(out, "_kspace", None)
+        if rows is not None and now is not None and type(now) is type(rows) and hasattr(rows, "nz_f") and now.nrow == rows.nrow:
+            out._kspace = rows
+
 
 class Reset(_Marker):
     """back to equilibrium, nstate <- 0 (operator.py:297-304)"""
     OPCODE, NOTE = _lib.OP_RESET, "reset"
+
+    def _derivatives(self, out, rows):
+        # as every derivative kernel does: the derivative states are cleared (stale ones of the old size were an accident of
+        # the reference, and their rows would no longer be the state's)
+        out.order1, out.order2 = {}, {}
 
     def _encode(self, enc):
         super()._encode(enc)

@@ -282,7 +282,10 @@ class Encoder:
         elif what == "relax":
             self.kspace = self.kspace.after_relaxation(kw.get("recovery", True))
         elif what == "spoil":
-            self.kspace = self.kspace.after_spoiler()
+            # (a derivative plan spoils its derivative states only with exact_partials, which is set after the plan is compiled:
+            # their transverse rows stay populated, so the rows are kept -- pruning them made the next gather drop dF)
+            if not self.variables:
+                self.kspace = self.kspace.after_spoiler()
         elif what == "reset":
             self.kspace = type(self.kspace).equilibrium(self.kspace.kdim)      # (float coordinates stay float: statematrix.py:293-297)
 
