@@ -183,6 +183,8 @@ SYMBOLS = {
     "epgx_signal_norms_c64": (_i, [_p, _p, _i64, _i32, _i64, _p]),
     "epgx_signal_match_c64": (_i, [_p, _p, _i64, _p, _i64, _p, _i64, _i32, _i64, _i32, _p, _p, _p]),
     "epgx_signal_refine": (_i, [_p, _p, _i64, _i64, _i32, _i32, _i32, _p, _i64, _p, _i64, _i64, _p, _p, _d, _p, _p, _p]),
+    "epgx_signal_component_gram": (_i, [_p, _p, _i64, _i32, _i32, _i64, _i64, _i64, _p, _p]),
+    "epgx_signal_nnls": (_i, [_p, _p, _i64, _i32, _i32, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _d, _d, _p, _p, _p, _p, _p]),
     "epgx_simulate_f64": (_i, [_p, ctypes.POINTER(PlanDesc), _i32, _p, _p, _p, _p, _i32]),
     "epgx_simulate_sharded_f64": (_i, [ctypes.POINTER(PlanDesc), _i32, _i32, _p, _p, _i32]),
     "epgx_comm_unique_id": (_i, [_p]),
@@ -907,6 +909,67 @@ def signal_refine(ctx, jac_ptr, record_stride, row_stride, nrow, nrec, rows, nat
         out.free()         # (back to the context's pool; stream-ordered behind the kernel)
         if ibuf is not None:
             ibuf.free()
+
+
+NNLS_MAX_A = 64      # csrc/epgx_nnls.h
+
+
+def signal_component_gram(ctx, dict_ptr, row_stride, nrec, ncomp, axis_stride, nouter, ninner):
+    """epgx_signal_component_gram: H_g[a, b] = Re sum_t conj(D[t, a, g]) D[t, b, g] and the validity masks of a dictionary in
+    device memory read as D[t, a, g] (atom a of group g = o * ninner + i of record t at dict_ptr + 16 * (t * row_stride +
+    (o * ncomp + a) * axis_stride + i)).  Returns the DeviceBuffers that hold float64 [G, ncomp, ncomp] and uint64 [G];
+    nothing crosses PCIe"""
+    G = max(int(nouter) * int(ninner), 1)
+    gram = DeviceBuffer(ctx, 8 * G * max(int(ncomp), 1) ** 2, itemsize=8)
+    mask = DeviceBuffer(ctx, 8 * G, itemsize=8)
+    try:
+        check(ctx.lib.epgx_signal_component_gram(ctx.handle, ctypes.c_void_p(dict_ptr) if dict_ptr else None, int(row_stride), int(nrec),
+                                                 int(ncomp), int(axis_stride), int(nouter), int(ninner), gram.ptr, mask.ptr),
+              "epgx_signal_component_gram")
+    except Exception:
+        gram.free()
+        mask.free()
+        raise
+    return gram, mask
+
+
+def signal_nnls(ctx, dict_ptr, row_stride, nrec, ncomp, axis_stride, nouter, ninner, gram_ptr, mask_ptr, sig_ptr, sig_row_stride,
+                nmeas, reg, tol, group=None):
+    """epgx_signal_nnls: per measured voxel the non-negative weights of the ncomp atoms of the best (or the given) group, from a
+    dictionary in device memory (layout, `gram_ptr` and `mask_ptr` as for `signal_component_gram`; signals as for `signal_match`).
+    `group`: None, int64 [nmeas] on the host (uploaded at 8 bytes per voxel), or the address of such an array in device memory.
+    Returns (weights float64 [ncomp, nmeas], group int64 [nmeas], residual float64 [nmeas], status int32 [nmeas]); only these
+    8 ncomp + 20 bytes per voxel cross PCIe"""
+    nmeas, A = int(nmeas), int(ncomp)
+    n = max(nmeas, 1)
+    gbuf = None
+    if isinstance(group, np.ndarray):
+        host = np.ascontiguousarray(group, dtype=np.int64)
+        if host.shape != (nmeas,):
+            raise ValueError(f"signal_nnls: group {host.shape} for {nmeas} voxels")
+        gbuf = DeviceBuffer(ctx, 8 * n, itemsize=8)
+        if nmeas:
+            gbuf.upload(host)
+        group = gbuf.ptr.value
+    rows = max(A, 0) + 3      # weights [A][nmeas], then group [nmeas] int64, residual [nmeas], status [nmeas] int32 (padded to 8 bytes)
+    out = DeviceBuffer(ctx, 8 * rows * n, itemsize=8)
+    try:
+        base = out.ptr.value
+        check(ctx.lib.epgx_signal_nnls(ctx.handle, ctypes.c_void_p(dict_ptr) if dict_ptr else None, int(row_stride), int(nrec), A,
+                                       int(axis_stride), int(nouter), int(ninner), ctypes.c_void_p(gram_ptr) if gram_ptr else None,
+                                       ctypes.c_void_p(mask_ptr) if mask_ptr else None, ctypes.c_void_p(sig_ptr) if sig_ptr else None,
+                                       int(sig_row_stride), nmeas, float(reg), float(tol), ctypes.c_void_p(group) if group else None,
+                                       ctypes.c_void_p(base), ctypes.c_void_p(base + 8 * A * n), ctypes.c_void_p(base + 8 * (A + 1) * n),
+                                       ctypes.c_void_p(base + 8 * (A + 2) * n)), "epgx_signal_nnls")
+        if nmeas == 0:
+            return np.empty((A, 0), np.float64), np.empty(0, np.int64), np.empty(0, np.float64), np.empty(0, np.int32)
+        raw = out.download(np.float64, (rows * n,))
+        return (raw[:A * n].reshape(A, n), raw[A * n:(A + 1) * n].view(np.int64), raw[(A + 1) * n:(A + 2) * n],
+                raw[(A + 2) * n:].view(np.int32)[:n])
+    finally:
+        out.free()         # (back to the context's pool; stream-ordered behind the kernel)
+        if gbuf is not None:
+            gbuf.free()
 
 
 GRAM_BLOCK, GRAM_WORKGROUPS, GRAM_MIN_ATOMS = 64, 2048, 1024      # csrc/epgx_compress.h

@@ -51,6 +51,7 @@
 #include "epgx_match32.h"
 #include "epgx_compress.h"
 #include "epgx_refine.h"
+#include "epgx_nnls.h"
 #include "epgx_merge.h"
 #include "epgx_prune.h"
 #include "epgx_launch_grow.h"
@@ -1219,6 +1220,89 @@ extern "C" int epgx_signal_refine(epgx_ctx *ctx, const void *jac, int64_t record
     a.scale = (d2 *)out_scale;
     a.score = (double *)out_score;
     hipError_t e = epgx_launch_refine(ctx->stream, nparam, a);
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return EPGX_OK;
+}
+
+// ------------------------------------------------------------------------------ non-negative mixtures (epgx_nnls.hip)
+// the checks both entries share; 0, or the error already recorded by fail()
+static int component_args(const char *who, const void *dict, int64_t row_stride, int32_t nrec, int32_t ncomp, int64_t axis_stride,
+                          int64_t nouter, int64_t ninner, ComponentArgs *c) {
+    if (ncomp < 1 || ncomp > NNLS_MAX_A) return fail(EPGX_ERR_INVALID, "%s: ncomp = %d not in [1, %d]", who, ncomp, NNLS_MAX_A);
+    if (nrec < 1) return fail(EPGX_ERR_INVALID, "%s: nrec = %d must be >= 1", who, nrec);
+    if (nouter < 1 || ninner < 1)
+        return fail(EPGX_ERR_INVALID, "%s: nouter = %lld, ninner = %lld: both must be >= 1", who, (long long)nouter, (long long)ninner);
+    if (axis_stride < ninner)
+        return fail(EPGX_ERR_INVALID, "%s: axis_stride = %lld below ninner = %lld", who, (long long)axis_stride, (long long)ninner);
+    int64_t groups, cols;      // cols: one past the last column an atom lies at
+    if (__builtin_mul_overflow(nouter, ninner, &groups) || groups > 0x7fffffff)
+        return fail(EPGX_ERR_INVALID, "%s: nouter = %lld times ninner = %lld groups in one call", who, (long long)nouter, (long long)ninner);
+    if (__builtin_mul_overflow(nouter, (int64_t)ncomp, &cols) || __builtin_mul_overflow(cols - 1, axis_stride, &cols) ||
+        __builtin_add_overflow(cols, ninner, &cols) || !match_extent_ok(nrec, row_stride, cols))
+        return fail(EPGX_ERR_INVALID, "%s: %d records of row_stride = %lld do not hold %lld x %d atoms of stride %lld (or overflow the address range)",
+                    who, nrec, (long long)row_stride, (long long)nouter, ncomp, (long long)axis_stride);
+    c->dict = (const d2 *)dict;
+    c->row_stride = row_stride;
+    c->nrec = nrec;
+    c->ncomp = ncomp;
+    c->axis_stride = axis_stride;
+    c->nouter = nouter;
+    c->ninner = ninner;
+    return 0;
+}
+
+extern "C" int epgx_signal_component_gram(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int32_t ncomp,
+                                          int64_t axis_stride, int64_t nouter, int64_t ninner, void *out_gram, void *out_mask) {
+    const char *who = "epgx_signal_component_gram";
+    if (!ctx || !dict || !out_gram || !out_mask) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
+    if (((uintptr_t)dict & 15) || ((uintptr_t)out_gram & 7) || ((uintptr_t)out_mask & 7))
+        return fail(EPGX_ERR_INVALID, "%s: dict must be aligned to 16 bytes, out_gram and out_mask to 8", who);
+    ComponentGramArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = component_args(who, dict, row_stride, nrec, ncomp, axis_stride, nouter, ninner, &a.c)) return rc;
+    if (int rc = set_device(ctx)) return rc;
+    a.gram = (double *)out_gram;
+    a.mask = (unsigned long long *)out_mask;
+    hipError_t e = epgx_launch_component_gram(ctx->stream, a);
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return EPGX_OK;
+}
+
+extern "C" int epgx_signal_nnls(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int32_t ncomp, int64_t axis_stride,
+                                int64_t nouter, int64_t ninner, const void *gram, const void *mask, const void *sig,
+                                int64_t sig_row_stride, int64_t nmeas, double reg, double tol, const void *group, void *out_weights,
+                                void *out_group, void *out_residual, void *out_status) {
+    const char *who = "epgx_signal_nnls";
+    if (!ctx || !dict || !gram || !mask || !sig || !out_weights || !out_group || !out_residual || !out_status)
+        return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
+    if (((uintptr_t)dict & 15) || ((uintptr_t)sig & 15) || ((uintptr_t)gram & 7) || ((uintptr_t)mask & 7) || ((uintptr_t)group & 7) ||
+        ((uintptr_t)out_weights & 7) || ((uintptr_t)out_group & 7) || ((uintptr_t)out_residual & 7) || ((uintptr_t)out_status & 3))
+        return fail(EPGX_ERR_INVALID, "%s: dict and sig must be aligned to 16 bytes, out_status to 4, the others to 8", who);
+    NnlsArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = component_args(who, dict, row_stride, nrec, ncomp, axis_stride, nouter, ninner, &a.c)) return rc;
+    if (nmeas < 0) return fail(EPGX_ERR_INVALID, "%s: nmeas = %lld must be >= 0", who, (long long)nmeas);
+    if (!match_extent_ok(nrec, sig_row_stride, nmeas))
+        return fail(EPGX_ERR_INVALID, "%s: %d records of sig_row_stride = %lld do not hold %lld voxels each (or overflow the address range)", who,
+                    nrec, (long long)sig_row_stride, (long long)nmeas);
+    if (nmeas >= 0x7fffffff) return fail(EPGX_ERR_INVALID, "%s: %lld voxels in one call", who, (long long)nmeas);
+    if (!(reg >= 0.0 && reg < (double)INFINITY)) return fail(EPGX_ERR_INVALID, "%s: reg = %g is not a finite number >= 0", who, reg);
+    if (!(tol >= 0.0 && tol < (double)INFINITY)) return fail(EPGX_ERR_INVALID, "%s: tol = %g is not a finite number >= 0", who, tol);
+    if (nmeas == 0) return EPGX_OK;
+    if (int rc = set_device(ctx)) return rc;
+    a.gram = (const double *)gram;
+    a.mask = (const unsigned long long *)mask;
+    a.sig = (const d2 *)sig;
+    a.sig_stride = sig_row_stride;
+    a.nmeas = nmeas;
+    a.reg = reg;
+    a.tol = tol;
+    a.group = (const int64_t *)group;
+    a.weights = (double *)out_weights;
+    a.out_group = (int64_t *)out_group;
+    a.residual = (double *)out_residual;
+    a.status = (int32_t *)out_status;
+    hipError_t e = epgx_launch_nnls(ctx->stream, a);
     if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return EPGX_OK;
 }

@@ -77,14 +77,47 @@ column lies within 1e-5 rad of the span of `d` and the earlier columns.  An unre
 `scale' = rho` and `score'` = the unrefined score; where `index` is invalid scale 0 and score 0.  Never an error, and no atom
 outside `[0, natoms)` is read.  A voxel's bits depend on its own signal, its atom's columns, nrec and the arguments only.
 `refine_host` states the same formulas in NumPy on host arrays; it is the definition the tests hold, not a path of `refine`.
+
+Mixtures (`Components`, `nnls`, csrc/epgx_nnls.hip through `epgx_signal_component_gram` / `epgx_signal_nnls`): everything above
+takes a voxel as ONE atom.  Multi-component analysis (T2 spectra, myelin water fraction, partial volume) takes it as a
+non-negative mixture of the atoms along one grid axis, the component axis, and chooses every other axis (B1, say) by the best fit,
+
+    comp = match.Components(handle, axis=0)     # H_g and the validity masks, computed once, kept in HBM
+    fit = match.nnls(comp, signals)             # .weights, .group, .residual, .status, .fraction(lo, hi, T2), .gmean(T2)
+
+`D[t, a, g]`: records t, atoms a < A <= 64 along the component axis, groups g < G = every other grid axis flattened in C order;
+`S[t, m]` the measured signals, complex128.  For every voxel m and group g
+
+    H_g[a,b] = Re sum_t conj(D[t,a,g]) D[t,b,g]          (A x A, real symmetric; once per dictionary)
+    f[a]     = Re sum_t conj(D[t,a,g]) S[t,m]            E = sum_t |S[t,m]|^2
+    mu_g     = reg * (trace(H_g over the valid atoms) / (number of valid atoms))
+    x*       = argmin over real x >= 0 of  J(x) = ||S[:,m] - sum_a x_a D[:,a,g]||^2 + mu_g ||x||^2
+             = argmin over x >= 0 of  x^T (H_g + mu_g I) x - 2 f^T x + E
+
+An atom is VALID where `H_g[a,a]` is finite and > 0 (match's rule); an invalid atom gets weight 0 and is never a candidate.  The
+solver is Lawson and Hanson's active set on the Gram form: with x = 0 and an empty passive set P, the atom outside P with the
+largest `w_a = f_a - ((H_g + mu_g I) x)_a` enters (the LOWEST a among equal w) while `w_a > tol sqrt(H_g[a,a] E)`; the passive
+set is solved by Cholesky of `(H_g + mu_g I)[P,P]` in the order the atoms entered; while a solution s has an entry <= 0 the
+iterate moves by `alpha = min x_p / (x_p - s_p)` over those entries towards s and the atoms that reach 0 leave.  In the end
+`J = E - sum_a x_a (f_a + w_a)`.  Per voxel: the weights of the chosen group; the group (without `group=`: the g of the smallest
+finite J, the LOWEST g among equal J); `residual = sqrt(max(J - mu_g ||x||^2, 0))`; `status` 0: solved, 1: the cap of 3 A
+passive-set solves (scipy's) was reached and the weights are the last feasible iterate, 2: a pivot of the factorisation was not
+finite or <= 0, or a sum (E, an f_a, an entry of a solution, J) was not finite -- the weights are NaN and the search skips the group.
+Where every group is skipped: group -1, NaN weights, NaN residual, status 2.  An all-zero signal: weights 0, status 0, residual 0
+in group 0.  Never an error.  A voxel's bits depend on its own signal, the dictionary and the arguments only.
+The Gram form resolves the problem down to about sqrt(2^-53) only (the caveat of `compress`): `reg = 0` is for well-conditioned
+dictionaries; the default 1e-8 bounds cond(H_g + mu_g I) by about A / reg and costs 1e-8 of the mean atom energy per unit weight.
+`nnls_host` states the same method in NumPy on host arrays; it is the definition the tests hold, not a path of `nnls`.
 """
 import numpy as np
 
 __all__ = ["Dictionary", "MatchResult", "match", "Basis", "compress", "gram_basis", "select_rank", "MAX_RANK",
-           "RefineResult", "refine", "refine_host", "MAX_REFINE_PARAMS"]
+           "RefineResult", "refine", "refine_host", "MAX_REFINE_PARAMS", "Components", "NnlsResult", "nnls", "nnls_host",
+           "MAX_COMPONENTS"]
 
 MAX_RANK = 64          # basis vectors `epgx_signal_project` takes
 MAX_REFINE_PARAMS = 4  # REFINE_MAX_P of csrc/epgx_refine.h
+MAX_COMPONENTS = 64    # NNLS_MAX_A of csrc/epgx_nnls.h: one lane of a wavefront per atom of the component axis
 
 
 def _dtype(dtype, name):
@@ -719,3 +752,291 @@ def refine_host(D, J, S, index, limit=None, rcond=1e-10):
     scale = np.where(valid, scale, 0.0)
     score = np.where(valid, score, 0.0)
     return RefineResult(delta.reshape(shape + (P,)), scale.reshape(shape), score.reshape(shape), idx, list(range(P)), grid)
+
+
+# ------------------------------------------------------------------------------------------------ non-negative mixtures
+NNLS_REG = 1e-8        # default reg of `nnls`
+NNLS_TOL = 1e-10       # default tol of `nnls`
+
+
+def _component_axis(axis, grid):
+    """`axis` as an index into `grid` (negative from the end) -> (axis, A, nouter, ninner, groups)"""
+    if isinstance(axis, (bool, np.bool_)) or int(axis) != axis or not -len(grid) <= axis < len(grid):
+        raise ValueError(f"axis: {axis!r} is not an axis of the grid {tuple(grid)}")
+    axis = int(axis) % len(grid)
+    nouter = int(np.prod(grid[:axis], dtype=np.int64))
+    ninner = int(np.prod(grid[axis + 1:], dtype=np.int64))
+    return axis, int(grid[axis]), nouter, ninner, tuple(grid[:axis]) + tuple(grid[axis + 1:])
+
+
+def _check_ncomp(A):
+    if not 1 <= A <= MAX_COMPONENTS:
+        raise NotImplementedError(f"axis: {A} atoms along the component axis; nnls takes 1 .. {MAX_COMPONENTS} (one lane of a wavefront "
+                                  "each) -- thin the axis, or download the dictionary (np.asarray) and use nnls_host")
+
+
+def _nnls_reg_tol(reg, tol):
+    if np.ndim(reg) != 0 or not 0.0 <= float(reg) < np.inf:
+        raise ValueError(f"reg: {reg!r} is not a finite number >= 0")
+    if np.ndim(tol) != 0 or not 0.0 <= float(tol) < np.inf:
+        raise ValueError(f"tol: {tol!r} is not a finite number >= 0")
+    return float(reg), float(tol)
+
+
+def _nnls_group(group, shape):
+    """group= as int64 of the signals' shape, or None"""
+    if group is None:
+        return None
+    grp = np.asarray(group)
+    if grp.dtype.kind not in "iu":
+        raise ValueError(f"group: an array of integer group indices, got {grp.dtype}")
+    if grp.shape != tuple(shape):
+        raise ValueError(f"group: indices of shape {grp.shape}, the signals have {tuple(shape)}")
+    return np.ascontiguousarray(grp, dtype=np.int64)
+
+
+class Components:
+    """a dictionary on the device read as `D[t, a, g]` (module docstring): atoms a along the grid axis `axis`, groups g = every
+    other axis flattened in C order, with its Gram matrices `H_g` and validity masks (computed once, kept in HBM next to the
+    records, as `Dictionary` keeps its norms).
+
+    handle: what `Dictionary` takes as complex128 -- a whole DeviceSignal, a DeviceJacobian (its probed-state row), a NumPy array
+    `[nrec, *grid]` (uploaded once) -- or a complex128, uncompressed `Dictionary`.  axis: an index into `grid`, negative from the
+    end; ANY axis: the kernels take its stride and the dictionary is not copied.
+    `.grid`, `.axis`, `.ncomp` (A), `.groups` (the grid without the axis), `.ngroups` (G), `.nrec`; `.gram` downloads `H` as
+    float64 `[G, A, A]`, `.valid` the masks as bool `[G, A]`.
+    NotImplementedError, naming the way out: more than 64 atoms along the axis, a ShardedDeviceSignal or a voxel slab, a
+    DeviceHessian, a complex64 or compressed `Dictionary`."""
+
+    def __init__(self, handle, axis, *, device=None):
+        from . import _lib
+        if isinstance(handle, Dictionary):
+            if handle.basis is not None:
+                raise NotImplementedError("components: a compressed dictionary; its records are coefficients of a temporal basis and "
+                                          "the mixture is fitted to the records themselves -- pass the uncompressed handle")
+            if handle.dtype != np.complex128:
+                raise NotImplementedError("components: a complex64 dictionary; nnls runs in float64 on the complex128 records "
+                                          "-- pass the handle the dictionary was narrowed from")
+            rec = handle._rec
+        else:
+            rec = _Records(handle, "components")
+        if len(rec.shape) == 0:
+            raise ValueError(f"components: an array [nrec, *grid] with at least one grid axis, got shape ({rec.nrec},)")
+        if rec.nrec < 1 or rec.ncol < 1:
+            raise ValueError(f"components: {rec.nrec} records of {rec.ncol} atoms; both must be at least 1")
+        self.axis, self.ncomp, self._nouter, self._ninner, self.groups = _component_axis(axis, rec.shape)
+        _check_ncomp(self.ncomp)
+        if rec.keep is None:
+            rec.upload(_lib.get_context(device))
+        self._rec = rec
+        self.grid, self.nrec, self.device = rec.shape, rec.nrec, rec.device
+        self.ngroups = self._nouter * self._ninner
+        self._gram, self._mask = _lib.signal_component_gram(rec.ctx, rec.ptr, rec.row_stride, rec.nrec, self.ncomp, self._ninner,
+                                                            self._nouter, self._ninner)
+
+    @property
+    def gram(self):
+        return self._gram.download(np.float64, (self.ngroups, self.ncomp, self.ncomp))
+
+    @property
+    def valid(self):
+        bits = self._mask.download(np.uint64, (self.ngroups,))
+        return ((bits[:, None] >> np.arange(self.ncomp, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
+
+
+class NnlsResult:
+    """`weights` float64 `[A, *shape]` (>= 0; NaN where no group could be solved), `group` int64 `shape` (flat index into `groups`,
+    -1: none), `residual` float64 (the norm of the data misfit), `status` int32 (0 solved, 1 iteration cap, 2 not solved), all
+    over the shape of the measured voxels; `groups` the dictionary's grid without the component axis.  `nnls_host` adds `solves`
+    (passive-set solves) and `left` (atoms that left the passive set) of the chosen group, int64; None from the device."""
+
+    def __init__(self, weights, group, residual, status, groups, solves=None, left=None):
+        self.weights, self.group, self.residual, self.status, self.groups = weights, group, residual, status, tuple(groups)
+        self.solves, self.left = solves, left
+
+    def unravel(self):
+        """tuple of index arrays, one per axis of `groups` (np.unravel_index); -1 stays -1 on every axis"""
+        if not self.groups:
+            return ()
+        none = self.group < 0
+        axes = np.unravel_index(np.where(none, 0, self.group), self.groups)
+        return tuple(np.where(none, -1, ax) for ax in axes)
+
+    def _values(self, values, what):
+        v = np.asarray(values, dtype=np.float64)
+        if v.shape != (self.weights.shape[0],):
+            raise ValueError(f"{what}: {v.shape} values for the {self.weights.shape[0]} atoms of the component axis")
+        return v.reshape((-1,) + (1,) * (self.weights.ndim - 1))
+
+    def fraction(self, lo, hi, values):
+        """the share of the weights whose `values[a]` lie in `[lo, hi)`: sum over those / sum over all; NaN where that sum is 0"""
+        v = self._values(values, "fraction")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            total = self.weights.sum(axis=0)
+            return np.where(total == 0, np.nan, (self.weights * ((v >= lo) & (v < hi))).sum(axis=0) / total)
+
+    def gmean(self, values):
+        """the weighted geometric mean `exp(sum_a w_a log values[a] / sum_a w_a)`; NaN where the sum of the weights is 0"""
+        v = self._values(values, "gmean")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            total = self.weights.sum(axis=0)
+            return np.where(total == 0, np.nan, np.exp((self.weights * np.log(v)).sum(axis=0) / total))
+
+
+def nnls(components, signals, *, reg=NNLS_REG, tol=NNLS_TOL, group=None):
+    """non-negative mixture of the atoms along the component axis for every measured voxel and the best group (module
+    docstring), on the device: `nnls_kernel` of csrc/epgx_nnls.hip, one wavefront per voxel, one lane per atom.
+
+    components: a `Components`.  signals: as for `match` (a NumPy array `[nrec, *shape]`, real or complex, or a whole DeviceSignal
+    on the dictionary's device and context).
+    reg >= 0: the ridge `mu_g = reg * mean valid H_g[a,a]`.  Default 1e-8: the Gram form squares the condition of the dictionary,
+    and 1e-8 of the mean atom energy bounds cond(H_g + mu_g I) by about A / reg ~ 1e10, which float64 Cholesky resolves, while
+    it moves the objective by at most 1e-8 ||x||^2 mean|D_a|^2; reg = 0 is for well-conditioned dictionaries.
+    tol >= 0: an atom outside the passive set enters only while `w_a > tol sqrt(H_g[a,a] E)`.  By Cauchy-Schwarz
+    `w_a / sqrt(H_g[a,a] E)` is at most the cosine between atom and residual times |residual| / |signal|, in [-1, 1]; w_a is
+    evaluated from the Gram form with an error of about A 2^-53 sqrt(cond) on that scale, 1e-14 .. 1e-12.  The default 1e-10
+    stands two orders above that noise, so no atom enters on rounding alone (which would cycle up to the cap), and an atom left
+    out at w_a <= tol sqrt(H_aa E) could lower J by w_a^2 / H_aa <= tol^2 E = 1e-20 E at most: far below what float64 shows.
+    group: None (search all groups), or an int array of the signals' shape that fixes each voxel's group, a binned B1 map say; an
+    entry outside [0, G) gives that voxel group -1, NaN weights, NaN residual and status 2, and reads nothing.
+    A 8 + 20 bytes per voxel come back; the dictionary does not move.  Returns an `NnlsResult`."""
+    from . import _lib
+    if not isinstance(components, Components):
+        raise ValueError("components: a match.Components (the dictionary with its component axis chosen)")
+    reg, tol = _nnls_reg_tol(reg, tol)
+    sig = _Records(signals, "signals")
+    if sig.nrec != components.nrec:
+        raise ValueError(f"signals: {sig.nrec} records, the dictionary has {components.nrec}")
+    rec = components._rec
+    if sig.device is not None and (sig.device != rec.device or sig.ctx is not rec.ctx):
+        raise ValueError(f"signals: on device {sig.device}, the dictionary on device {rec.device}; both must be on one GPU (and context)")
+    grp = _nnls_group(group, sig.shape)
+    sig.upload(rec.ctx)
+    try:
+        weights, chosen, residual, status = _lib.signal_nnls(
+            rec.ctx, rec.ptr, rec.row_stride, components.nrec, components.ncomp, components._ninner, components._nouter,
+            components._ninner, components._gram.ptr.value if components._gram.ptr else None,
+            components._mask.ptr.value if components._mask.ptr else None, sig.ptr, sig.row_stride, sig.ncol, reg, tol,
+            None if grp is None else grp.reshape(-1))
+    finally:
+        if isinstance(sig.keep, _lib.DeviceBuffer):
+            sig.keep.free()        # (stream-ordered: the block is recycled behind the kernel that reads it)
+    return NnlsResult(weights.reshape((components.ncomp,) + sig.shape).copy(), chosen.reshape(sig.shape).copy(),
+                      residual.reshape(sig.shape).copy(), status.reshape(sig.shape).copy(), components.groups)
+
+
+def _nnls_task(H, valid, mu, f, E, tol, cap=None):
+    """one (voxel, group) of `nnls_host`: H [A, A] without the ridge, valid bool [A], f [A], E -> (x, J, J_data, status, solves, left);
+    cap: the passive-set solves allowed, 3 A (a test lowers it)"""
+    A = len(f)
+    cap = 3 * A if cap is None else cap
+    nan = np.full(A, np.nan)
+    diag = np.where(valid, np.diagonal(H), 0.0)
+    if not np.isfinite(E) or not np.isfinite(f[valid]).all():
+        return nan, np.nan, np.nan, 2, 0, 0
+    Hm = H + mu * np.eye(A)
+    thr = tol * np.sqrt(diag * E)
+    x, w, P = np.zeros(A), np.where(valid, f, 0.0), []
+    status, solves, left = 0, 0, 0
+
+    def gradient():
+        out = f.copy()
+        for p in P:                                    # in the order the atoms entered
+            out = out - np.where(valid, Hm[p], 0.0) * x[p]
+        return np.where(valid, out, 0.0)
+
+    while status == 0:
+        cand = valid & (w > thr)
+        cand[P] = False
+        if not cand.any():
+            break
+        P.append(int(np.argmax(np.where(cand, w, -np.inf))))       # (the first among equal w)
+        while True:
+            if solves == cap:
+                status = 1
+                break
+            solves += 1
+            k = len(P)
+            L = np.zeros((k, k))
+            for q in range(k):
+                for i in range(q):
+                    L[q, i] = (Hm[P[q], P[i]] - L[q, :i] @ L[i, :i]) / L[i, i]
+                piv = Hm[P[q], P[q]] - L[q, :q] @ L[q, :q]
+                if not (np.isfinite(piv) and piv > 0):
+                    return nan, np.nan, np.nan, 2, solves, left
+                L[q, q] = np.sqrt(piv)
+            s = f[P].copy()
+            for q in range(k):
+                s[q] = (s[q] - L[q, :q] @ s[:q]) / L[q, q]
+            for q in range(k - 1, -1, -1):
+                s[q] = (s[q] - L[q + 1:, q] @ s[q + 1:]) / L[q, q]
+            if not np.isfinite(s).all():
+                return nan, np.nan, np.nan, 2, solves, left
+            xp = x[P]
+            neg = ~(s > 0)
+            if not neg.any():
+                x[:] = 0.0
+                x[P] = s
+                break
+            with np.errstate(invalid="ignore", divide="ignore"):
+                al = np.where(neg, np.where(xp == 0, 0.0, xp / (xp - s)), np.inf)
+            alpha = al.min()
+            xn = xp + alpha * (s - xp)
+            drop = neg & (~(xn > 0) | (al == alpha))
+            x[:] = 0.0
+            x[P] = np.where(drop, 0.0, xn)
+            left += int(drop.sum())
+            P = [p for p, d in zip(P, drop) if not d]
+            if not P:
+                break
+        w = gradient()
+    J, n2 = E, 0.0
+    for a in range(A):
+        if x[a] != 0:
+            J = J - x[a] * (f[a] + w[a])
+            n2 = n2 + x[a] * x[a]
+    if not np.isfinite(J):
+        return nan, np.nan, np.nan, 2, solves, left
+    return x, J, J - mu * n2, status, solves, left
+
+
+def nnls_host(D, S, axis, *, reg=NNLS_REG, tol=NNLS_TOL, group=None):
+    """the method of `nnls` (module docstring) in NumPy float64 on host arrays: the documented definition -- the same active set on
+    the Gram form, one (voxel, group) at a time.  Not a path of `nnls`, which never calls it, and any number of atoms.
+
+    D `[nrec, *grid]`, S `[nrec, *shape]`, axis into `grid`; reg, tol, group as for `nnls`.  Returns an `NnlsResult` with `solves`
+    and `left` filled."""
+    D, S = np.asarray(D, dtype=np.complex128), np.asarray(S, dtype=np.complex128)
+    if D.ndim < 2 or S.ndim < 1 or S.shape[0] != D.shape[0] or D.shape[0] < 1 or D.size == 0:
+        raise ValueError(f"nnls_host: D [nrec, *grid], S [nrec, *shape]: got {D.shape}, {S.shape}")
+    reg, tol = _nnls_reg_tol(reg, tol)
+    nrec, shape = D.shape[0], S.shape[1:]
+    axis, A, nouter, ninner, groups = _component_axis(axis, D.shape[1:])
+    G = nouter * ninner
+    Dg = np.moveaxis(D.reshape(nrec, nouter, A, ninner), 2, 1).reshape(nrec, A, G)
+    s = S.reshape(nrec, -1)
+    nmeas = s.shape[1]
+    grp = _nnls_group(group, shape)
+    with np.errstate(all="ignore"):
+        H = np.einsum("tag,tbg->gab", Dg.real, Dg.real) + np.einsum("tag,tbg->gab", Dg.imag, Dg.imag)
+        diag = np.einsum("gaa->ga", H)
+        valid = np.isfinite(diag) & (diag > 0)
+        mu = np.array([reg * (diag[g][valid[g]].sum() / valid[g].sum()) if valid[g].any() else 0.0 for g in range(G)])
+        F = np.einsum("tag,tm->gma", Dg.real, s.real) + np.einsum("tag,tm->gma", Dg.imag, s.imag)
+        E = (s.real ** 2 + s.imag ** 2).sum(axis=0)
+    weights = np.full((A, nmeas), np.nan)
+    chosen, status = np.full(nmeas, -1, dtype=np.int64), np.full(nmeas, 2, dtype=np.int32)
+    residual = np.full(nmeas, np.nan)
+    solves, left = np.zeros(nmeas, dtype=np.int64), np.zeros(nmeas, dtype=np.int64)
+    for m in range(nmeas):
+        best = np.inf
+        todo = range(G) if grp is None else ([int(grp.reshape(-1)[m])] if 0 <= grp.reshape(-1)[m] < G else [])
+        for g in todo:
+            with np.errstate(all="ignore"):
+                x, J, Jd, st, ns, nl = _nnls_task(H[g], valid[g], mu[g], F[g, m], E[m], tol)
+            if st != 2 and J < best:
+                best = J
+                weights[:, m], chosen[m], status[m], solves[m], left[m] = x, g, st, ns, nl
+                residual[m] = np.sqrt(max(Jd, 0.0))
+    return NnlsResult(weights.reshape((A,) + shape), chosen.reshape(shape), residual.reshape(shape), status.reshape(shape), groups,
+                      solves.reshape(shape), left.reshape(shape))

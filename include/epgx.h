@@ -785,6 +785,48 @@ int epgx_signal_refine(epgx_ctx *ctx, const void *jac, int64_t record_stride, in
                        int32_t nparam, const int32_t *rows, int64_t natoms, const void *sig, int64_t sig_row_stride, int64_t nmeas,
                        const void *index, const double *limit, double rcond, void *out_delta, void *out_scale, void *out_score);
 
+/* Non-negative mixtures along one grid axis of a dictionary left in HBM (csrc/epgx_nnls.hip; within ABI 11): multi-component
+ * analysis (T2 spectra, myelin water fraction, partial volume).  The dictionary is read as D[t,a,g]: atom a < ncomp of the
+ * component axis, group g = o * ninner + i (o < nouter, i < ninner: every other grid axis, flattened in C order), record t at
+ *   dict[t * row_stride + (o * ncomp + a) * axis_stride + i]      complex128, strides in elements of 16 bytes;
+ * for a C-ordered grid axis_stride = ninner = the product of the axes behind the component axis, nouter that of the axes before.
+ * S[t,m] = sig[t * sig_row_stride + m].  For every voxel m and group g:
+ *   H_g[a,b] = Re sum_t conj(D[t,a,g]) D[t,b,g]          (epgx_signal_component_gram: once per dictionary)
+ *   f[a]     = Re sum_t conj(D[t,a,g]) S[t,m]            E = sum_t |S[t,m]|^2
+ *   mu_g     = reg * (trace(H_g over the valid atoms) / (number of valid atoms))
+ *   x*       = argmin over x >= 0 of  x^T (H_g + mu_g I) x - 2 f^T x + E
+ * An atom is VALID where H_g[a,a] is finite and > 0 (bit a of the group's mask); an invalid atom gets weight 0 and is never a candidate.
+ * Method: Lawson and Hanson's active set on the Gram form.  From x = 0 and an empty passive set P, the atom outside P with the
+ * largest w_a = f_a - ((H_g + mu_g I) x)_a enters, the LOWEST a among equal w, while w_a > tol sqrt(H_g[a,a] E); P is solved by
+ * Cholesky of (H_g + mu_g I)[P,P] in the order the atoms entered; while a solution s has an entry <= 0 the iterate moves by
+ * alpha = min x_p / (x_p - s_p) over those entries towards s, and they leave where they reach 0 or set alpha.  In the end
+ * J = E - sum_a x_a (f_a + w_a).
+ * Per voxel: the weights of the chosen group; the group (group = NULL: the g of the smallest finite J, the LOWEST g among equal J;
+ * else group[m]); residual = sqrt(max(J - mu_g |x|^2, 0)); status 0: solved, 1: the cap of 3 ncomp passive-set solves was reached
+ * (the weights are the last feasible iterate), 2: a pivot was not finite or <= 0, or E, an f_a, an entry of a solution or J was
+ * not finite (such a group is skipped).  Where every group is skipped, or group[m] lies outside [0, G): group -1, NaN weights,
+ * NaN residual, status 2; a voxel with such a group[m] reads nothing.  An all-zero signal: weights 0, status 0, residual 0, in
+ * group 0 of the search.  Never an error.
+ * Invariance: every sum runs in a fixed order (records, passive positions and atoms ascending) and the groups are compared in
+ * ascending order inside the wavefront that owns the voxel, so the bits of a voxel's result depend on its own column of S, the
+ * dictionary and the arguments -- not on nmeas, the voxel's place in the call, or other voxels.  H_g is symmetric to the bit.
+ *   out_gram  : DEVICE float64 [G][ncomp][ncomp];  out_mask : DEVICE uint64 [G]            (G = nouter * ninner)
+ *   gram, mask: DEVICE, what epgx_signal_component_gram wrote for the same dictionary and decomposition
+ *   group     : DEVICE int64 [nmeas], or NULL
+ *   out_weights : DEVICE float64 [ncomp][nmeas];  out_group : DEVICE int64 [nmeas];  out_residual : DEVICE float64 [nmeas];
+ *   out_status  : DEVICE int32 [nmeas]
+ * Stream-ordered; nothing is uploaded or synchronised.
+ * Errors (nothing is launched): EPGX_ERR_INVALID for a NULL (group apart) or misaligned pointer (16 bytes: dict, sig; 4: out_status;
+ * 8: the others), ncomp outside [1, 64], nrec < 1, nouter < 1, ninner < 1, axis_stride < ninner, more than 2^31 - 1 groups or
+ * voxels, a row_stride that does not hold the atoms, sig_row_stride < nmeas, an extent that overflows, nmeas < 0, reg or tol
+ * negative or not finite.  nmeas = 0: nothing to do. */
+int epgx_signal_component_gram(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int32_t ncomp, int64_t axis_stride,
+                               int64_t nouter, int64_t ninner, void *out_gram, void *out_mask);
+int epgx_signal_nnls(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int32_t ncomp, int64_t axis_stride,
+                     int64_t nouter, int64_t ninner, const void *gram, const void *mask, const void *sig, int64_t sig_row_stride,
+                     int64_t nmeas, double reg, double tol, const void *group, void *out_weights, void *out_group,
+                     void *out_residual, void *out_status);
+
 /* Convenience for bindings that only have host arrays (what a ctypes/NumPy binding inside
  * the reference would call once per simulate()): builds the plan, runs the whole sequence
  * state-resident over the full grid, copies signal (and optionally the final state) back. */
