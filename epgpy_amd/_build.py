@@ -38,6 +38,7 @@ UNITS = [("epgx_api.o", "epgx_api.hip", []), ("epgx_planner.o", "epgx_planner.cp
          ("epgx_merge.o", "epgx_merge.hip", []), ("epgx_match.o", "epgx_match.hip", []),
          ("epgx_compress.o", "epgx_compress.hip", []), ("epgx_match32.o", "epgx_match32.hip", []),
          ("epgx_refine.o", "epgx_refine.hip", []), ("epgx_nnls.o", "epgx_nnls.hip", []),
+         ("epgx_nnls_chi2.o", "epgx_nnls_chi2.hip", []),
          # (the per-voxel shift restates NumPy arithmetic operation by operation: no fused multiply-add anywhere in the unit)
          ("epgx_prune.o", "epgx_prune.hip", ["-ffp-contract=off"])]
 ARCH = "gfx950"

@@ -185,6 +185,8 @@ SYMBOLS = {
     "epgx_signal_refine": (_i, [_p, _p, _i64, _i64, _i32, _i32, _i32, _p, _i64, _p, _i64, _i64, _p, _p, _d, _p, _p, _p]),
     "epgx_signal_component_gram": (_i, [_p, _p, _i64, _i32, _i32, _i64, _i64, _i64, _p, _p]),
     "epgx_signal_nnls": (_i, [_p, _p, _i64, _i32, _i32, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _d, _d, _p, _p, _p, _p, _p]),
+    "epgx_signal_nnls_chi2": (_i, [_p, _p, _i64, _i32, _i32, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _d, _d, _p, _d, _d, _i32,
+                                   _p, _p, _p, _p, _p, _p, _p]),
     "epgx_simulate_f64": (_i, [_p, ctypes.POINTER(PlanDesc), _i32, _p, _p, _p, _p, _i32]),
     "epgx_simulate_sharded_f64": (_i, [ctypes.POINTER(PlanDesc), _i32, _i32, _p, _p, _i32]),
     "epgx_comm_unique_id": (_i, [_p]),
@@ -968,6 +970,53 @@ def signal_nnls(ctx, dict_ptr, row_stride, nrec, ncomp, axis_stride, nouter, nin
                 raw[(A + 2) * n:].view(np.int32)[:n])
     finally:
         out.free()         # (back to the context's pool; stream-ordered behind the kernel)
+        if gbuf is not None:
+            gbuf.free()
+
+
+NNLS_CHI2_FACTOR, NNLS_CHI2_EVALS = 16.0, 40      # csrc/epgx_nnls.h
+
+
+def signal_nnls_chi2(ctx, dict_ptr, row_stride, nrec, ncomp, axis_stride, nouter, ninner, gram_ptr, mask_ptr, sig_ptr, sig_row_stride,
+                     nmeas, reg, tol, chi2, chi2_rtol, group=None, max_evals=NNLS_CHI2_EVALS):
+    """epgx_signal_nnls_chi2: `signal_nnls` followed on the device by the search for the ridge at which the data misfit has grown
+    to chi2 times that of the unregularised fit; the group of a voxel goes from the first kernel to the second in device memory.
+    Arguments as for `signal_nnls`.  Returns (weights float64 [ncomp, nmeas], group int64 [nmeas], residual float64 [nmeas],
+    status int32 [nmeas], mu float64 [nmeas], chi2 float64 [nmeas], evals int32 [nmeas]); only these 8 ncomp + 40 bytes per voxel
+    cross PCIe"""
+    nmeas, A = int(nmeas), int(ncomp)
+    n = max(nmeas, 1)
+    gbuf = None
+    if isinstance(group, np.ndarray):
+        host = np.ascontiguousarray(group, dtype=np.int64)
+        if host.shape != (nmeas,):
+            raise ValueError(f"signal_nnls_chi2: group {host.shape} for {nmeas} voxels")
+        gbuf = DeviceBuffer(ctx, 8 * n, itemsize=8)
+        if nmeas:
+            gbuf.upload(host)
+        group = gbuf.ptr.value
+    # weights [A][nmeas], group [nmeas] int64, residual, mu, chi2 [nmeas], then status and evals [nmeas] int32 each
+    rows = max(A, 0) + 5
+    out = DeviceBuffer(ctx, 8 * rows * n, itemsize=8)
+    try:
+        base = out.ptr.value
+        row = lambda i: ctypes.c_void_p(base + 8 * (A + i) * n)      # noqa: E731
+        check(ctx.lib.epgx_signal_nnls_chi2(ctx.handle, ctypes.c_void_p(dict_ptr) if dict_ptr else None, int(row_stride), int(nrec), A,
+                                            int(axis_stride), int(nouter), int(ninner), ctypes.c_void_p(gram_ptr) if gram_ptr else None,
+                                            ctypes.c_void_p(mask_ptr) if mask_ptr else None,
+                                            ctypes.c_void_p(sig_ptr) if sig_ptr else None, int(sig_row_stride), nmeas, float(reg),
+                                            float(tol), ctypes.c_void_p(group) if group else None, float(chi2), float(chi2_rtol),
+                                            int(max_evals), ctypes.c_void_p(base), row(0), row(1), row(4), row(2), row(3),
+                                            ctypes.c_void_p(base + 8 * (A + 4) * n + 4 * n)), "epgx_signal_nnls_chi2")
+        if nmeas == 0:
+            return (np.empty((A, 0), np.float64), np.empty(0, np.int64), np.empty(0, np.float64), np.empty(0, np.int32),
+                    np.empty(0, np.float64), np.empty(0, np.float64), np.empty(0, np.int32))
+        raw = out.download(np.float64, (rows * n,))
+        ints = raw[(A + 4) * n:].view(np.int32)
+        return (raw[:A * n].reshape(A, n), raw[A * n:(A + 1) * n].view(np.int64), raw[(A + 1) * n:(A + 2) * n], ints[:n],
+                raw[(A + 2) * n:(A + 3) * n], raw[(A + 3) * n:(A + 4) * n], ints[n:2 * n])
+    finally:
+        out.free()         # (back to the context's pool; stream-ordered behind the kernels)
         if gbuf is not None:
             gbuf.free()
 

@@ -1268,19 +1268,19 @@ extern "C" int epgx_signal_component_gram(epgx_ctx *ctx, const void *dict, int64
     return EPGX_OK;
 }
 
-extern "C" int epgx_signal_nnls(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int32_t ncomp, int64_t axis_stride,
-                                int64_t nouter, int64_t ninner, const void *gram, const void *mask, const void *sig,
-                                int64_t sig_row_stride, int64_t nmeas, double reg, double tol, const void *group, void *out_weights,
-                                void *out_group, void *out_residual, void *out_status) {
-    const char *who = "epgx_signal_nnls";
+// the checks epgx_signal_nnls and epgx_signal_nnls_chi2 share; 0 with *a filled (nothing launched, no device set), or the error
+// already recorded by fail()
+static int nnls_args(const char *who, epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int32_t ncomp, int64_t axis_stride,
+                     int64_t nouter, int64_t ninner, const void *gram, const void *mask, const void *sig, int64_t sig_row_stride,
+                     int64_t nmeas, double reg, double tol, const void *group, void *out_weights, void *out_group, void *out_residual,
+                     void *out_status, NnlsArgs *a) {
     if (!ctx || !dict || !gram || !mask || !sig || !out_weights || !out_group || !out_residual || !out_status)
         return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
     if (((uintptr_t)dict & 15) || ((uintptr_t)sig & 15) || ((uintptr_t)gram & 7) || ((uintptr_t)mask & 7) || ((uintptr_t)group & 7) ||
         ((uintptr_t)out_weights & 7) || ((uintptr_t)out_group & 7) || ((uintptr_t)out_residual & 7) || ((uintptr_t)out_status & 3))
         return fail(EPGX_ERR_INVALID, "%s: dict and sig must be aligned to 16 bytes, out_status to 4, the others to 8", who);
-    NnlsArgs a;
-    memset(&a, 0, sizeof(a));
-    if (int rc = component_args(who, dict, row_stride, nrec, ncomp, axis_stride, nouter, ninner, &a.c)) return rc;
+    memset(a, 0, sizeof(*a));
+    if (int rc = component_args(who, dict, row_stride, nrec, ncomp, axis_stride, nouter, ninner, &a->c)) return rc;
     if (nmeas < 0) return fail(EPGX_ERR_INVALID, "%s: nmeas = %lld must be >= 0", who, (long long)nmeas);
     if (!match_extent_ok(nrec, sig_row_stride, nmeas))
         return fail(EPGX_ERR_INVALID, "%s: %d records of sig_row_stride = %lld do not hold %lld voxels each (or overflow the address range)", who,
@@ -1288,21 +1288,70 @@ extern "C" int epgx_signal_nnls(epgx_ctx *ctx, const void *dict, int64_t row_str
     if (nmeas >= 0x7fffffff) return fail(EPGX_ERR_INVALID, "%s: %lld voxels in one call", who, (long long)nmeas);
     if (!(reg >= 0.0 && reg < (double)INFINITY)) return fail(EPGX_ERR_INVALID, "%s: reg = %g is not a finite number >= 0", who, reg);
     if (!(tol >= 0.0 && tol < (double)INFINITY)) return fail(EPGX_ERR_INVALID, "%s: tol = %g is not a finite number >= 0", who, tol);
+    a->gram = (const double *)gram;
+    a->mask = (const unsigned long long *)mask;
+    a->sig = (const d2 *)sig;
+    a->sig_stride = sig_row_stride;
+    a->nmeas = nmeas;
+    a->reg = reg;
+    a->tol = tol;
+    a->group = (const int64_t *)group;
+    a->weights = (double *)out_weights;
+    a->out_group = (int64_t *)out_group;
+    a->residual = (double *)out_residual;
+    a->status = (int32_t *)out_status;
+    return 0;
+}
+
+extern "C" int epgx_signal_nnls(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int32_t ncomp, int64_t axis_stride,
+                                int64_t nouter, int64_t ninner, const void *gram, const void *mask, const void *sig,
+                                int64_t sig_row_stride, int64_t nmeas, double reg, double tol, const void *group, void *out_weights,
+                                void *out_group, void *out_residual, void *out_status) {
+    const char *who = "epgx_signal_nnls";
+    NnlsArgs a;
+    if (int rc = nnls_args(who, ctx, dict, row_stride, nrec, ncomp, axis_stride, nouter, ninner, gram, mask, sig, sig_row_stride, nmeas, reg,
+                           tol, group, out_weights, out_group, out_residual, out_status, &a))
+        return rc;
     if (nmeas == 0) return EPGX_OK;
     if (int rc = set_device(ctx)) return rc;
-    a.gram = (const double *)gram;
-    a.mask = (const unsigned long long *)mask;
-    a.sig = (const d2 *)sig;
-    a.sig_stride = sig_row_stride;
-    a.nmeas = nmeas;
-    a.reg = reg;
-    a.tol = tol;
-    a.group = (const int64_t *)group;
-    a.weights = (double *)out_weights;
-    a.out_group = (int64_t *)out_group;
-    a.residual = (double *)out_residual;
-    a.status = (int32_t *)out_status;
     hipError_t e = epgx_launch_nnls(ctx->stream, a);
+    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return EPGX_OK;
+}
+
+extern "C" int epgx_signal_nnls_chi2(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int32_t ncomp, int64_t axis_stride,
+                                     int64_t nouter, int64_t ninner, const void *gram, const void *mask, const void *sig,
+                                     int64_t sig_row_stride, int64_t nmeas, double reg, double tol, const void *group, double chi2,
+                                     double chi2_rtol, int32_t max_evals, void *out_weights, void *out_group, void *out_residual,
+                                     void *out_status, void *out_mu, void *out_chi2, void *out_evals) {
+    const char *who = "epgx_signal_nnls_chi2";
+    NnlsChi2Args a;
+    memset(&a, 0, sizeof(a));
+    if (!out_mu || !out_chi2 || !out_evals) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
+    if (((uintptr_t)out_mu & 7) || ((uintptr_t)out_chi2 & 7) || ((uintptr_t)out_evals & 3))
+        return fail(EPGX_ERR_INVALID, "%s: out_mu and out_chi2 must be aligned to 8 bytes, out_evals to 4", who);
+    if (int rc = nnls_args(who, ctx, dict, row_stride, nrec, ncomp, axis_stride, nouter, ninner, gram, mask, sig, sig_row_stride, nmeas, reg,
+                           tol, group, out_weights, out_group, out_residual, out_status, &a.n))
+        return rc;
+    if (!(reg > 0.0)) return fail(EPGX_ERR_INVALID, "%s: reg = %g must be > 0: the bracket grows from mu_0 = reg * mean H_aa", who, reg);
+    if (!(chi2 > 1.0 && chi2 < (double)INFINITY)) return fail(EPGX_ERR_INVALID, "%s: chi2 = %g is not a finite number > 1", who, chi2);
+    if (!(chi2_rtol > 0.0 && chi2_rtol < 1.0)) return fail(EPGX_ERR_INVALID, "%s: chi2_rtol = %g not in (0, 1)", who, chi2_rtol);
+    if (max_evals < 0 || max_evals > NNLS_CHI2_EVALS)
+        return fail(EPGX_ERR_INVALID, "%s: max_evals = %d not in [0, %d]", who, max_evals, NNLS_CHI2_EVALS);
+    if (nmeas == 0) return EPGX_OK;
+    if (int rc = set_device(ctx)) return rc;
+    a.chi2 = chi2;
+    a.rtol = chi2_rtol;
+    a.max_evals = max_evals;
+    a.mu = (double *)out_mu;
+    a.ratio = (double *)out_chi2;
+    a.evals = (int32_t *)out_evals;
+    if (!group) {      // the group search first; its out_group stays on the device and is what the second launch reads
+        hipError_t e = epgx_launch_nnls(ctx->stream, a.n);
+        if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+        a.n.group = a.n.out_group;
+    }
+    hipError_t e = epgx_launch_nnls_chi2(ctx->stream, a);
     if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return EPGX_OK;
 }

@@ -39,6 +39,20 @@ struct NnlsArgs {
     int32_t *status;              // [nmeas]
 };
 
+// the chi^2-driven ridge (include/epgx.h epgx_signal_nnls_chi2): the bracket grows by this factor per evaluation from mu_0, and a
+// voxel's search ends after this many fits (DESIGN 4.17 has the counts both come from)
+constexpr double NNLS_CHI2_FACTOR = 16.0;
+constexpr int NNLS_CHI2_EVALS = 40;
+
+struct NnlsChi2Args {
+    NnlsArgs n;                   // group is never NULL here: the caller's, or what nnls_kernel wrote to out_group just before
+    double chi2, rtol;
+    int32_t max_evals;            // NNLS_CHI2_EVALS (a test lowers it)
+    double *mu;                   // [nmeas]
+    double *ratio;                // [nmeas]: Jd(mu) / Jd(mu_0)
+    int32_t *evals;               // [nmeas]
+};
+
 // LDS of a block of nnls_kernel: H_g (A x A doubles), per wavefront the strict lower triangle of the passive-set Cholesky factor
 // (A (A - 1) / 2 doubles; the diagonal lives in registers as its inverse) and 64 ints of scratch for compactions.
 // A = 64: 32 KiB + waves x 16 000 B: 95.5 KiB for the 4 wavefronts of the search, 47.8 KiB for the single one of a fixed group
@@ -51,3 +65,5 @@ constexpr size_t nnls_lds_bytes(int A, int waves) {
 // every field validated by the caller (epgx_signal_component_gram, epgx_signal_nnls)
 hipError_t epgx_launch_component_gram(hipStream_t stream, const epgx::ComponentGramArgs &a);
 hipError_t epgx_launch_nnls(hipStream_t stream, const epgx::NnlsArgs &a);
+// (epgx_nnls_chi2.hip; validated by epgx_signal_nnls_chi2)  One wavefront, one block per voxel
+hipError_t epgx_launch_nnls_chi2(hipStream_t stream, const epgx::NnlsChi2Args &a);

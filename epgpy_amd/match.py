@@ -108,6 +108,28 @@ in group 0.  Never an error.  A voxel's bits depend on its own signal, the dicti
 The Gram form resolves the problem down to about sqrt(2^-53) only (the caveat of `compress`): `reg = 0` is for well-conditioned
 dictionaries; the default 1e-8 bounds cond(H_g + mu_g I) by about A / reg and costs 1e-8 of the mean atom energy per unit weight.
 `nnls_host` states the same method in NumPy on host arrays; it is the definition the tests hold, not a path of `nnls`.
+
+The chi^2-driven ridge (`nnls(..., chi2=1.02)`, csrc/epgx_nnls_chi2.hip through `epgx_signal_nnls_chi2`): the fixed ridge `reg` is
+there for the Cholesky factor, not for the spectrum, and the unregularised weights are the spiky minimum-support solution.
+Multi-component T2 analysis (Whittall and MacKay; DECAES) raises the ridge until the data misfit has grown by a chosen factor and
+reports the smooth spectrum there.  With `Jd(mu) = J - mu ||x(mu)||^2` the data misfit of the minimiser x(mu) >= 0 at the ridge mu:
+
+    1. group and baseline: exactly the above at mu_0 = reg * mean valid H_g[a,a]; x_0, Jd_0 = Jd(mu_0).  The group never changes
+       afterwards (the DECAES rule: the flip angle comes from the unregularised chi^2).  Status 1 and 2 pass through unchanged,
+       with mu = mu_0, chi2 = 1 (both NaN at status 2) and evals = 0
+    2. status 4 where Jd_0 <= 0 or Jd_0 < 4 * 8 (nrec + A) 2^-53 E / chi2_rtol: 8 (nrec + A) 2^-53 E is the rounding of the Gram-form
+       J, below that floor the ratio cannot be resolved to chi2_rtol; x_0, mu = mu_0, chi2 = 1, evals = 0
+    3. T = chi2 * Jd_0.  |Jd_0 / T - 1| <= chi2_rtol: status 0 at mu_0.  T >= E (no ridge reaches it: x = 0 has Jd = E): status 3 at mu_0
+    4. r(mu) = Jd(mu) / T - 1, every evaluation one cold fit (x = 0, empty passive set) at its mu:
+       bracket   mu = 16 mu_lo from mu_lo = mu_0 while r(mu) < -chi2_rtol
+       Illinois  mu = mu_lo exp(r_lo / (r_lo - r_hi) log(mu_hi / mu_lo)); the new point replaces the end of its sign; where the
+                 same end is replaced twice running, the r of the other end is halved
+       |r(mu)| <= chi2_rtol: status 0, the weights at that mu.  After NNLS_CHI2_EVALS = 40 fits, at a fit that is not status 0
+       or a mu that is not finite: status 3 with the evaluated point of the largest Jd <= T (the baseline if no other)
+
+`Jd` is non-decreasing in mu for the constrained problem, so the root is bracketed from mu_0 upward.  `.mu` is the ridge of the
+returned weights, `.chi2 = Jd / Jd_0`, `.evals` the fits of step 4, `.residual = sqrt(max(Jd, 0))`.  `nnls_host(..., chi2=)` is the
+same search in NumPy (its exp and log are NumPy's, so a mu agrees with the device's to rounding, not to the bit).
 """
 import numpy as np
 
@@ -757,6 +779,9 @@ def refine_host(D, J, S, index, limit=None, rcond=1e-10):
 # ------------------------------------------------------------------------------------------------ non-negative mixtures
 NNLS_REG = 1e-8        # default reg of `nnls`
 NNLS_TOL = 1e-10       # default tol of `nnls`
+NNLS_CHI2_RTOL = 1e-3  # default chi2_rtol of `nnls`
+NNLS_CHI2_FACTOR = 16.0  # NNLS_CHI2_FACTOR of csrc/epgx_nnls.h: the step of the bracket
+NNLS_CHI2_EVALS = 40     # NNLS_CHI2_EVALS of csrc/epgx_nnls.h: the fits a voxel's search may take
 
 
 def _component_axis(axis, grid):
@@ -781,6 +806,19 @@ def _nnls_reg_tol(reg, tol):
     if np.ndim(tol) != 0 or not 0.0 <= float(tol) < np.inf:
         raise ValueError(f"tol: {tol!r} is not a finite number >= 0")
     return float(reg), float(tol)
+
+
+def _nnls_chi2(chi2, chi2_rtol, reg):
+    """(chi2, chi2_rtol) as floats; chi2 None: (None, None)"""
+    if chi2 is None:
+        return None, None
+    if np.ndim(chi2) != 0 or isinstance(chi2, (bool, np.bool_)) or not 1.0 < float(chi2) < np.inf:
+        raise ValueError(f"chi2: {chi2!r} is not a finite number > 1 (the factor by which the data misfit may grow), or None")
+    if np.ndim(chi2_rtol) != 0 or isinstance(chi2_rtol, (bool, np.bool_)) or not 0.0 < float(chi2_rtol) < 1.0:
+        raise ValueError(f"chi2_rtol: {chi2_rtol!r} is not a number in (0, 1)")
+    if not reg > 0.0:
+        raise ValueError(f"reg: {reg!r} with chi2=: the search for the ridge grows from mu_0 = reg * mean H_aa and needs reg > 0")
+    return float(chi2), float(chi2_rtol)
 
 
 def _nnls_group(group, shape):
@@ -848,11 +886,16 @@ class NnlsResult:
     """`weights` float64 `[A, *shape]` (>= 0; NaN where no group could be solved), `group` int64 `shape` (flat index into `groups`,
     -1: none), `residual` float64 (the norm of the data misfit), `status` int32 (0 solved, 1 iteration cap, 2 not solved), all
     over the shape of the measured voxels; `groups` the dictionary's grid without the component axis.  `nnls_host` adds `solves`
-    (passive-set solves) and `left` (atoms that left the passive set) of the chosen group, int64; None from the device."""
+    (passive-set solves) and `left` (atoms that left the passive set) of the chosen group, int64; None from the device.
+    With `chi2=` (module docstring; None without): `mu` float64, the absolute ridge at which the returned weights were solved,
+    `chi2` float64, the achieved ratio Jd(mu) / Jd(mu_0), `evals` int32, the fits the search took; `status` 3: the search ended
+    without meeting `chi2_rtol`, 4: the misfit lies below the resolution of the Gram form and nothing was regularised; `solves` and
+    `left` are those of the baseline fit."""
 
-    def __init__(self, weights, group, residual, status, groups, solves=None, left=None):
+    def __init__(self, weights, group, residual, status, groups, solves=None, left=None, mu=None, chi2=None, evals=None):
         self.weights, self.group, self.residual, self.status, self.groups = weights, group, residual, status, tuple(groups)
         self.solves, self.left = solves, left
+        self.mu, self.chi2, self.evals = mu, chi2, evals
 
     def unravel(self):
         """tuple of index arrays, one per axis of `groups` (np.unravel_index); -1 stays -1 on every axis"""
@@ -883,7 +926,7 @@ class NnlsResult:
             return np.where(total == 0, np.nan, np.exp((self.weights * np.log(v)).sum(axis=0) / total))
 
 
-def nnls(components, signals, *, reg=NNLS_REG, tol=NNLS_TOL, group=None):
+def nnls(components, signals, *, reg=NNLS_REG, tol=NNLS_TOL, group=None, chi2=None, chi2_rtol=NNLS_CHI2_RTOL, _max_evals=None):
     """non-negative mixture of the atoms along the component axis for every measured voxel and the best group (module
     docstring), on the device: `nnls_kernel` of csrc/epgx_nnls.hip, one wavefront per voxel, one lane per atom.
 
@@ -899,11 +942,17 @@ def nnls(components, signals, *, reg=NNLS_REG, tol=NNLS_TOL, group=None):
     out at w_a <= tol sqrt(H_aa E) could lower J by w_a^2 / H_aa <= tol^2 E = 1e-20 E at most: far below what float64 shows.
     group: None (search all groups), or an int array of the signals' shape that fixes each voxel's group, a binned B1 map say; an
     entry outside [0, G) gives that voxel group -1, NaN weights, NaN residual and status 2, and reads nothing.
-    A 8 + 20 bytes per voxel come back; the dictionary does not move.  Returns an `NnlsResult`."""
+    chi2: None, or a finite number > 1: the chi^2-driven ridge of the module docstring -- after the fit above (which fixes the
+    group), `nnls_chi2_kernel` of csrc/epgx_nnls_chi2.hip raises the ridge of every voxel from mu_0 until the data misfit is
+    `chi2` times that of the unregularised fit within `chi2_rtol` (in (0, 1)), and the smooth weights at that ridge come back
+    with `.mu`, `.chi2`, `.evals` and the statuses 3 and 4.  1.02 is the convention of myelin water imaging.  Needs reg > 0.
+    The group goes from one kernel to the next in device memory.
+    A 8 + 20 bytes per voxel come back (A 8 + 40 with chi2=); the dictionary does not move.  Returns an `NnlsResult`."""
     from . import _lib
     if not isinstance(components, Components):
         raise ValueError("components: a match.Components (the dictionary with its component axis chosen)")
     reg, tol = _nnls_reg_tol(reg, tol)
+    chi2, chi2_rtol = _nnls_chi2(chi2, chi2_rtol, reg)
     sig = _Records(signals, "signals")
     if sig.nrec != components.nrec:
         raise ValueError(f"signals: {sig.nrec} records, the dictionary has {components.nrec}")
@@ -912,17 +961,23 @@ def nnls(components, signals, *, reg=NNLS_REG, tol=NNLS_TOL, group=None):
         raise ValueError(f"signals: on device {sig.device}, the dictionary on device {rec.device}; both must be on one GPU (and context)")
     grp = _nnls_group(group, sig.shape)
     sig.upload(rec.ctx)
-    try:
-        weights, chosen, residual, status = _lib.signal_nnls(
-            rec.ctx, rec.ptr, rec.row_stride, components.nrec, components.ncomp, components._ninner, components._nouter,
+    args = (rec.ctx, rec.ptr, rec.row_stride, components.nrec, components.ncomp, components._ninner, components._nouter,
             components._ninner, components._gram.ptr.value if components._gram.ptr else None,
-            components._mask.ptr.value if components._mask.ptr else None, sig.ptr, sig.row_stride, sig.ncol, reg, tol,
-            None if grp is None else grp.reshape(-1))
+            components._mask.ptr.value if components._mask.ptr else None, sig.ptr, sig.row_stride, sig.ncol, reg, tol)
+    extra = ()
+    try:
+        if chi2 is None:
+            weights, chosen, residual, status = _lib.signal_nnls(*args, None if grp is None else grp.reshape(-1))
+        else:
+            weights, chosen, residual, status, *extra = _lib.signal_nnls_chi2(
+                *args, chi2, chi2_rtol, None if grp is None else grp.reshape(-1),
+                _lib.NNLS_CHI2_EVALS if _max_evals is None else _max_evals)
     finally:
         if isinstance(sig.keep, _lib.DeviceBuffer):
             sig.keep.free()        # (stream-ordered: the block is recycled behind the kernel that reads it)
     return NnlsResult(weights.reshape((components.ncomp,) + sig.shape).copy(), chosen.reshape(sig.shape).copy(),
-                      residual.reshape(sig.shape).copy(), status.reshape(sig.shape).copy(), components.groups)
+                      residual.reshape(sig.shape).copy(), status.reshape(sig.shape).copy(), components.groups,
+                      **{k: v.reshape(sig.shape).copy() for k, v in zip(("mu", "chi2", "evals"), extra)})
 
 
 def _nnls_task(H, valid, mu, f, E, tol, cap=None):
@@ -1000,16 +1055,69 @@ def _nnls_task(H, valid, mu, f, E, tol, cap=None):
     return x, J, J - mu * n2, status, solves, left
 
 
-def nnls_host(D, S, axis, *, reg=NNLS_REG, tol=NNLS_TOL, group=None):
+def _nnls_chi2_task(H, valid, mu0, f, E, tol, nrec, base, chi2, rtol, max_evals=None, cap=None):
+    """the search of `nnls_host(..., chi2=)` for one voxel in its chosen group (module docstring, steps 2 to 4).  base: the
+    baseline `_nnls_task` result (x, J, J_data, status, ...) at mu0 -> (x, J_data, status, mu, ratio, evals); max_evals: the
+    fits allowed, NNLS_CHI2_EVALS, and cap: that of the passive-set solves of a fit (tests lower them)"""
+    A = len(f)
+    max_evals = NNLS_CHI2_EVALS if max_evals is None else max_evals
+    x0, _, Jd0, st0 = base[:4]
+    if st0 != 0:
+        return x0, Jd0, st0, mu0, 1.0, 0
+    floor = 32.0 * float(nrec + A) * 2.0 ** -53 * E / rtol
+    if not Jd0 > 0.0 or Jd0 < floor:
+        return x0, Jd0, 4, mu0, 1.0, 0
+    T = chi2 * Jd0
+    if abs(Jd0 / T - 1.0) <= rtol:
+        return x0, Jd0, 0, mu0, 1.0, 0
+    if not T < E or not mu0 > 0.0:
+        return x0, Jd0, 3, mu0, 1.0, 0
+    out = (x0, Jd0, 3, mu0, 1.0)
+    mu_lo, r_lo, mu_hi, r_hi, best = mu0, Jd0 / T - 1.0, 0.0, 0.0, Jd0
+    bracket, side, evals = False, 0, 0
+    while evals < max_evals:
+        mu = mu_lo * NNLS_CHI2_FACTOR
+        if bracket:
+            mu = mu_lo * np.exp(r_lo / (r_lo - r_hi) * np.log(mu_hi / mu_lo))
+        if not np.isfinite(mu):
+            break
+        evals += 1
+        x, J, Jd, st = _nnls_task(H, valid, mu, f, E, tol, cap)[:4]
+        if st != 0:
+            break
+        r = Jd / T - 1.0
+        hit = abs(r) <= rtol
+        if hit or (r < 0.0 and Jd > best):
+            best = Jd
+            out = (x, Jd, 3, mu, Jd / Jd0)
+        if hit:
+            out = out[:2] + (0,) + out[3:]
+            break
+        if r < 0.0:
+            mu_lo, r_lo = mu, r
+            if bracket:
+                if side < 0:
+                    r_hi *= 0.5
+                side = -1
+        else:
+            mu_hi, r_hi = mu, r
+            if bracket and side > 0:
+                r_lo *= 0.5
+            bracket, side = True, 1
+    return out + (evals,)
+
+
+def nnls_host(D, S, axis, *, reg=NNLS_REG, tol=NNLS_TOL, group=None, chi2=None, chi2_rtol=NNLS_CHI2_RTOL, _max_evals=None, _cap=None):
     """the method of `nnls` (module docstring) in NumPy float64 on host arrays: the documented definition -- the same active set on
     the Gram form, one (voxel, group) at a time.  Not a path of `nnls`, which never calls it, and any number of atoms.
 
-    D `[nrec, *grid]`, S `[nrec, *shape]`, axis into `grid`; reg, tol, group as for `nnls`.  Returns an `NnlsResult` with `solves`
-    and `left` filled."""
+    D `[nrec, *grid]`, S `[nrec, *shape]`, axis into `grid`; reg, tol, group, chi2, chi2_rtol as for `nnls`.  Returns an `NnlsResult`
+    with `solves` and `left` filled (with chi2=: those of the baseline fit)."""
     D, S = np.asarray(D, dtype=np.complex128), np.asarray(S, dtype=np.complex128)
     if D.ndim < 2 or S.ndim < 1 or S.shape[0] != D.shape[0] or D.shape[0] < 1 or D.size == 0:
         raise ValueError(f"nnls_host: D [nrec, *grid], S [nrec, *shape]: got {D.shape}, {S.shape}")
     reg, tol = _nnls_reg_tol(reg, tol)
+    chi2, chi2_rtol = _nnls_chi2(chi2, chi2_rtol, reg)
     nrec, shape = D.shape[0], S.shape[1:]
     axis, A, nouter, ninner, groups = _component_axis(axis, D.shape[1:])
     G = nouter * ninner
@@ -1028,15 +1136,24 @@ def nnls_host(D, S, axis, *, reg=NNLS_REG, tol=NNLS_TOL, group=None):
     chosen, status = np.full(nmeas, -1, dtype=np.int64), np.full(nmeas, 2, dtype=np.int32)
     residual = np.full(nmeas, np.nan)
     solves, left = np.zeros(nmeas, dtype=np.int64), np.zeros(nmeas, dtype=np.int64)
+    ridge, ratio, evals = np.full(nmeas, np.nan), np.full(nmeas, np.nan), np.zeros(nmeas, dtype=np.int32)
     for m in range(nmeas):
-        best = np.inf
+        best, base = np.inf, None
         todo = range(G) if grp is None else ([int(grp.reshape(-1)[m])] if 0 <= grp.reshape(-1)[m] < G else [])
         for g in todo:
             with np.errstate(all="ignore"):
-                x, J, Jd, st, ns, nl = _nnls_task(H[g], valid[g], mu[g], F[g, m], E[m], tol)
+                task = _nnls_task(H[g], valid[g], mu[g], F[g, m], E[m], tol, _cap)
+            x, J, Jd, st, ns, nl = task
             if st != 2 and J < best:
-                best = J
+                best, base = J, task
                 weights[:, m], chosen[m], status[m], solves[m], left[m] = x, g, st, ns, nl
                 residual[m] = np.sqrt(max(Jd, 0.0))
+        if chi2 is not None and base is not None:
+            g = chosen[m]
+            with np.errstate(all="ignore"):
+                x, Jd, st, ridge[m], ratio[m], evals[m] = _nnls_chi2_task(H[g], valid[g], mu[g], F[g, m], E[m], tol, nrec, base, chi2,
+                                                                         chi2_rtol, _max_evals, _cap)
+            weights[:, m], status[m], residual[m] = x, st, np.sqrt(max(Jd, 0.0))
+    more = {} if chi2 is None else dict(mu=ridge.reshape(shape), chi2=ratio.reshape(shape), evals=evals.reshape(shape))
     return NnlsResult(weights.reshape((A,) + shape), chosen.reshape(shape), residual.reshape(shape), status.reshape(shape), groups,
-                      solves.reshape(shape), left.reshape(shape))
+                      solves.reshape(shape), left.reshape(shape), **more)

@@ -827,6 +827,41 @@ int epgx_signal_nnls(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_
                      int64_t nmeas, double reg, double tol, const void *group, void *out_weights, void *out_group,
                      void *out_residual, void *out_status);
 
+/* The chi^2-driven ridge of the non-negative mixtures (csrc/epgx_nnls_chi2.hip; within ABI 11): the discrepancy principle of
+ * multi-component T2 analysis (Whittall and MacKay; DECAES).  Per voxel, with the notation of epgx_signal_nnls, J(x; mu) =
+ * x^T (H_g + mu I) x - 2 f^T x + E at its minimiser x(mu) >= 0 and Jd(mu) = J - mu |x(mu)|^2 the data misfit:
+ *   1. Group and baseline: exactly epgx_signal_nnls at mu_0 = reg * mean valid H_g[a,a] -- every group (group = NULL) or group[m],
+ *      the g of the smallest finite J, the lowest among equal.  x_0 its weights, Jd_0 = Jd(mu_0).  Regularisation never changes
+ *      the group.  Status 1 and 2 of this fit pass through: its weights (NaN), residual, mu = mu_0 (NaN), chi2 = 1 (NaN), evals 0.
+ *   2. Status 4 where Jd_0 <= 0 or Jd_0 < 4 * 8 (nrec + ncomp) 2^-53 E / chi2_rtol, four times the rounding of the Gram-form J over
+ *      chi2_rtol: the ratio cannot be resolved; x_0, mu = mu_0, chi2 = 1, evals 0.  (An all-zero signal is such a voxel.)
+ *   3. Target T = chi2 * Jd_0.  |Jd_0 / T - 1| <= chi2_rtol: status 0 at mu_0, evals 0.  T >= E (x = 0 has the misfit E: no ridge
+ *      reaches T): status 3 at mu_0, evals 0.
+ *   4. Search, every evaluation one COLD fit (x = 0, empty passive set) at its mu, r(mu) = Jd(mu) / T - 1:
+ *      bracket: mu = 16 mu_lo from mu_lo = mu_0 while r(mu) < -chi2_rtol; then Illinois regula falsi in log mu,
+ *        mu = mu_lo exp(r_lo / (r_lo - r_hi) log(mu_hi / mu_lo)),
+ *      the new point replaces the end of its sign, and where the same end is replaced twice running the r of the other end is
+ *      halved.  |r(mu)| <= chi2_rtol ends the search: status 0, the weights at that mu.  After max_evals fits, at a fit that is not
+ *      status 0 (the cap of 3 ncomp solves, a pivot) or a mu that is not finite the search ends with status 3 at the evaluated
+ *      point of the largest Jd <= T, the baseline if no other.
+ * Jd is non-decreasing in mu for the constrained problem, so the root is bracketed from mu_0 upward.
+ * Per voxel: weights, group, residual = sqrt(max(Jd, 0)) of the returned weights, status (0, 1, 2 as above; 3, 4), out_mu the
+ * ridge of the returned weights, out_chi2 = Jd / Jd_0, out_evals the fits of step 4 (the baseline is not counted).
+ * Invariance as for epgx_signal_nnls: one wavefront (one block) per voxel, the sums of the fit in their fixed order, the search a
+ * fixed function of the voxel's Jd values; exp and log are the device's.
+ *   group     : DEVICE int64 [nmeas], or NULL: nnls_kernel runs first and its out_group is read on the device
+ *   max_evals : the cap of step 4, 0 .. 40 (NNLS_CHI2_EVALS of csrc/epgx_nnls.h; smaller values are for tests)
+ *   out_mu, out_chi2 : DEVICE float64 [nmeas];  out_evals : DEVICE int32 [nmeas];  the others as for epgx_signal_nnls
+ * Stream-ordered; nothing is uploaded or synchronised.
+ * Errors (nothing is launched): those of epgx_signal_nnls; NULL or misaligned out_mu, out_chi2 (8 bytes), out_evals (4); reg = 0
+ * (the bracket grows from mu_0); chi2 not a finite number > 1; chi2_rtol outside (0, 1); max_evals outside [0, 40].  nmeas = 0:
+ * nothing to do. */
+int epgx_signal_nnls_chi2(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int32_t ncomp, int64_t axis_stride,
+                          int64_t nouter, int64_t ninner, const void *gram, const void *mask, const void *sig, int64_t sig_row_stride,
+                          int64_t nmeas, double reg, double tol, const void *group, double chi2, double chi2_rtol, int32_t max_evals,
+                          void *out_weights, void *out_group, void *out_residual, void *out_status, void *out_mu, void *out_chi2,
+                          void *out_evals);
+
 /* Convenience for bindings that only have host arrays (what a ctypes/NumPy binding inside
  * the reference would call once per simulate()): builds the plan, runs the whole sequence
  * state-resident over the full grid, copies signal (and optionally the final state) back. */
