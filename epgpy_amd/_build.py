@@ -15,8 +15,9 @@ CSRC = os.path.join(HERE, "csrc")
 OBJDIR = os.path.join(CSRC, "build")
 LIBPATH = os.path.join(CSRC, "libepgx.so")
 # (object name, source, extra flags)
-UNITS = [("epgx_api.o", "epgx_api.hip", []), ("epgx_planner.o", "epgx_planner.cpp", []),
-         ("epgx_plan_check.o", "epgx_plan_check.cpp", []), ("epgx_run_check.o", "epgx_run_check.cpp", [])] + \
+UNITS = [("epgx_api.o", "epgx_api.hip", []), ("epgx_signal.o", "epgx_signal.hip", []), ("epgx_planner.o", "epgx_planner.cpp", []),
+         ("epgx_plan_check.o", "epgx_plan_check.cpp", []), ("epgx_run_check.o", "epgx_run_check.cpp", []),
+         ("epgx_signal_check.o", "epgx_signal_check.cpp", [])] + \
         [(f"epgx_split_p{part}.o", "epgx_split.hip", [f"-DEPGX_PART={part}"]) for part in (16, 0, 8, 4, 2)] + \
         [(f"epgx_cgrow_m{m}.o", "epgx_cgrow.hip", [f"-DEPGX_M={m}"]) for m in (16, 8, 4, 2)] + \
         [(f"epgx_packed_v{v}_k{k}.o", "epgx_packed.hip", [f"-DEPGX_V={v}", f"-DEPGX_KP={k}"]) for v in (3, 2, 1) for k in (32, 16)] + \
@@ -49,8 +50,8 @@ FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
          "-mllvm", "-structurizecfg-skip-uniform-regions=1",
          # the first 16 dwords of run_kernel's arguments are preloaded into SGPRs at wave launch
          "-mllvm", "-amdgpu-kernarg-preload-count=16"]
-# epgx_planner.cpp, epgx_plan_check.cpp and epgx_run_check.cpp are plain C++ (launch planning, plan and run analysis, no HIP):
-# the host compiler alone
+# epgx_planner.cpp, epgx_plan_check.cpp, epgx_run_check.cpp and epgx_signal_check.cpp are plain C++ (launch planning, plan and run
+# analysis, the argument checks of the signal consumers; no HIP): the host compiler alone
 HOST_FLAGS = ["-x", "c++", "-O3", "-std=c++17", "-fPIC"]
 
 
@@ -84,14 +85,15 @@ def include_closure(src):
 
 
 PUBLIC_HEADER = os.path.normpath("../../include/epgx.h")
+ENTRY_UNITS = {"epgx_api.hip", "epgx_signal.hip"}     # the units that define the C entry points
 _COMMENT = re.compile(r"/\*.*?\*/|//[^\n]*", re.S)
 _PROTOTYPE = re.compile(r"(?m)^[ \t]*(?:const[ \t]+)?[A-Za-z_][\w \t\*]*\bepgx_\w+[ \t]*\([^;{}]*\)[ \t]*;")
 
 
 def kernel_view(text):
     """what a KERNEL translation unit sees of include/epgx.h: constants, enums and structs -- comments and the prototypes of
-    the C entry points (which only epgx_api.hip defines) removed, white space collapsed.  A new entry point or a reworded
-    comment then rebuilds epgx_api.o, not the 45 kernel units (5.5 minutes on 8 cores)"""
+    the C entry points (which only ENTRY_UNITS define) removed, white space collapsed.  A new entry point or a reworded
+    comment then rebuilds epgx_api.o and epgx_signal.o, not the 45 kernel units (5.5 minutes on 8 cores)"""
     text = _PROTOTYPE.sub("", _COMMENT.sub("", text))
     return " ".join(text.split())
 
@@ -99,7 +101,7 @@ def kernel_view(text):
 def _dep_bytes(dep, unit_src):
     with open(os.path.join(CSRC, dep), "rb") as fh:
         raw = fh.read()
-    if os.path.normpath(dep) == PUBLIC_HEADER and unit_src != "epgx_api.hip":
+    if os.path.normpath(dep) == PUBLIC_HEADER and unit_src not in ENTRY_UNITS:
         return kernel_view(raw.decode()).encode()
     return raw
 

@@ -3,7 +3,8 @@
 // Every entry point validates its operands against what the kernels and their grids assume
 // BEFORE anything is launched (shapes, opcode range, coefficient-table bounds, shift range,
 // signal slots), returns a negative status instead of throwing, and records a thread-local
-// message for epgx_last_error().  There is no CPU execution path in this library.
+// message for epgx_last_error().  There is no CPU execution path in this library.  (The entry points that read a signal, a
+// dictionary or a Jacobian left in HBM -- crlb, match, refine, nnls, gram, project -- are epgx_signal.hip.)
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types only: librccl.so.1 is loaded on first use (rccl_api)
 #include <dlfcn.h>
@@ -33,6 +34,7 @@
 #include <utility>
 #include <vector>
 
+#include "epgx_ctx.h"
 #include "epgx_kernels.hip.h"
 #include "epgx_small_kernels.hip.h"
 #include "epgx_exchange_kernels.hip.h"
@@ -46,12 +48,6 @@
 #include "epgx_run_check.h"
 #include "epgx_chain.h"
 #include "epgx_dft.h"
-#include "epgx_stats.h"
-#include "epgx_match.h"
-#include "epgx_match32.h"
-#include "epgx_compress.h"
-#include "epgx_refine.h"
-#include "epgx_nnls.h"
 #include "epgx_merge.h"
 #include "epgx_prune.h"
 #include "epgx_launch_grow.h"
@@ -60,16 +56,7 @@
 using namespace epgx;
 
 // ------------------------------------------------------------------------------ errors
-// (fail and the thread-local message behind epgx_last_error: epgx_error.h)
-
-#define HIP_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return fail(e_ == hipErrorOutOfMemory ? EPGX_ERR_NOMEM : EPGX_ERR_HIP,           \
-                        "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__,     \
-                        __LINE__);                                                           \
-    } while (0)
+// (fail and the thread-local message behind epgx_last_error: epgx_error.h; HIP_TRY: epgx_ctx.h)
 
 // Measurement knobs of the selection (Knobs, epgx_planner.h), read from the environment ONCE per process, here and nowhere else.
 namespace {
@@ -93,38 +80,7 @@ const Knobs &knobs() {
 }  // namespace
 
 // ------------------------------------------------------------------------------ objects
-struct epgx_ctx {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    hipStream_t own = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipDeviceProp_t prop;
-    // caching device allocator: freed blocks are kept and handed out again.  hipMalloc / hipFree
-    // cost 1-25 ms each at the sizes of a plan (measured; hipFree also synchronises the device),
-    // which dominated a repeated simulate() of the same shape.  Every use of a block is ordered on
-    // ctx->stream, so a block can be recycled without waiting for the work that last touched it.
-    // (`mem` guards the three containers: ctypes releases the GIL during calls, and one context may be
-    // shared by several host threads -- their launches then interleave on the one stream, which is legal)
-    std::mutex mem;
-    // page-locked host blocks (epgx_host_alloc), recycled the same way; copy stream + events of epgx_run_to_host
-    std::vector<std::pair<void *, size_t>> host_cache;
-    std::unordered_map<void *, size_t> host_live;
-    size_t host_cached_bytes = 0;
-    hipStream_t copy_stream = nullptr;
-    std::vector<hipEvent_t> slab_events;
-    // one slab pipeline at a time per CONTEXT (copy stream, events and staging ring are shared by its host threads);
-    // pipelines of different contexts / GPUs run side by side
-    std::mutex pipeline;
-    // ring of page-locked staging blocks for downloads into ordinary (pageable) host memory (epgx_run_to_host)
-    struct Stage { void *host = nullptr; hipEvent_t done = nullptr; };
-    std::vector<Stage> stages;
-    size_t stage_bytes = 0;
-    std::vector<std::pair<void *, size_t>> cache;
-    std::unordered_map<void *, size_t> live;
-    size_t cached_bytes = 0;
-};
-
+// (struct epgx_ctx: epgx_ctx.h, with the declarations of dev_alloc, dev_free and set_device for epgx_signal.hip)
 static void dev_release_cache_locked(epgx_ctx *ctx) {
     if (ctx->cache.empty()) return;
     (void)hipStreamSynchronize(ctx->stream);
@@ -138,7 +94,7 @@ static void dev_release_cache(epgx_ctx *ctx) {
     dev_release_cache_locked(ctx);
 }
 
-static hipError_t dev_alloc(epgx_ctx *ctx, void **out, size_t bytes) {
+hipError_t epgx::dev_alloc(epgx_ctx *ctx, void **out, size_t bytes) {
     std::lock_guard<std::mutex> guard(ctx->mem);
     bytes = std::max<size_t>((bytes + 255) & ~(size_t)255, 256);
     int best = -1;
@@ -165,7 +121,7 @@ static hipError_t dev_alloc(epgx_ctx *ctx, void **out, size_t bytes) {
     return e;
 }
 
-static void dev_free(epgx_ctx *ctx, void *p) {
+void epgx::dev_free(epgx_ctx *ctx, void *p) {
     if (!p) return;
     std::lock_guard<std::mutex> guard(ctx->mem);
     auto it = ctx->live.find(p);
@@ -257,7 +213,7 @@ struct epgx_coords {   // per-voxel coordinates next to a state of 64 stored ord
     int32_t *nlive = nullptr;   // [nvox]
 };
 
-static int set_device(const epgx_ctx *ctx) {
+int epgx::set_device(const epgx_ctx *ctx) {
     HIP_TRY(hipSetDevice(ctx->device));
     return EPGX_OK;
 }
@@ -864,576 +820,6 @@ extern "C" int epgx_signal_reduce(epgx_ctx *ctx, const void *signal, int64_t sig
     else
         hipLaunchKernelGGL(reduce_thread_kernel, dim3((unsigned)((a.n_out + 255) / 256), (unsigned)n_rows), dim3(256), 0, ctx->stream, a);
     HIP_TRY(hipGetLastError());
-    return EPGX_OK;
-}
-
-// ------------------------------------------------------------------------------ Cramer-Rao bounds (epgx_stats.hip)
-// the Jacobian block, weights, sigma2 and flags of epgx_signal_crlb / epgx_signal_crlb_grad (`who`), checked and put into `a`
-// (everything but `out`); nothing here touches the device
-static int crlb_jacobian_args(const char *who, const void *signal, int64_t record_stride, int64_t row_stride, int32_t nrow, int32_t nrec,
-                              int32_t nparam, const int32_t *rows, int64_t vox0, int64_t nvox, const double *weights, double sigma2,
-                              int32_t flags, int32_t known_flags, CrlbArgs &a) {
-    if ((uintptr_t)signal & 15) return fail(EPGX_ERR_INVALID, "%s: signal must be aligned to 16 bytes", who);
-    if (nparam < 1 || nparam > CRLB_MAX_P)
-        return fail(EPGX_ERR_INVALID, "%s: nparam = %d not in [1, %d]", who, nparam, CRLB_MAX_P);
-    if (nrec < 1 || nrow < 1) return fail(EPGX_ERR_INVALID, "%s: nrec = %d, nrow = %d: both must be >= 1", who, nrec, nrow);
-    if (vox0 < 0 || nvox < 0 || row_stride < 1 || nvox > row_stride - vox0)
-        return fail(EPGX_ERR_INVALID, "%s: voxels [%lld, %lld + %lld) outside a row of %lld", who, (long long)vox0,
-                    (long long)vox0, (long long)nvox, (long long)row_stride);
-    if (record_stride / nrow < row_stride)
-        return fail(EPGX_ERR_INVALID, "%s: record_stride = %lld holds fewer than nrow = %d rows of %lld", who,
-                    (long long)record_stride, nrow, (long long)row_stride);
-    int64_t span, last;      // elements from `signal` to the end of the last record: must be expressible (the kernel's pointer arithmetic)
-    if (__builtin_mul_overflow((int64_t)(nrec - 1), record_stride, &span) || __builtin_mul_overflow((int64_t)nrow, row_stride, &last) ||
-        __builtin_add_overflow(span, last, &span) || span > INT64_MAX / 16)
-        return fail(EPGX_ERR_INVALID, "%s: nrec = %d records of record_stride = %lld elements overflow the address range", who,
-                    nrec, (long long)record_stride);
-    if (flags & ~known_flags) return fail(EPGX_ERR_INVALID, "%s: unknown flags 0x%x", who, flags);
-    if (!(sigma2 > 0.0) || !std::isfinite(sigma2)) return fail(EPGX_ERR_INVALID, "%s: sigma2 = %g is not a positive finite number", who, sigma2);
-    memset(&a, 0, sizeof(a));
-    for (int c = 0; c < nparam; ++c) {
-        if (rows[c] < 0 || rows[c] >= nrow)
-            return fail(EPGX_ERR_INVALID, "%s: rows[%d] = %d not in [0, nrow = %d)", who, c, rows[c], nrow);
-        if (weights && !std::isfinite(weights[c])) return fail(EPGX_ERR_INVALID, "%s: weights[%d] is not finite", who, c);
-        a.rows[c] = rows[c];
-        a.w[c] = weights ? weights[c] : 1.0;
-    }
-    if (nvox / 64 >= 0x7fffffff) return fail(EPGX_ERR_INVALID, "%s: %lld voxels in one call", who, (long long)nvox);
-    a.signal = (const d2 *)signal;
-    a.record_stride = record_stride;
-    a.row_stride = row_stride;
-    a.nrec = nrec;
-    a.vox0 = vox0;
-    a.nvox = nvox;
-    a.inv_sigma2 = 1.0 / sigma2;
-    a.flags = flags;
-    crlb_slices(nrec, &a.slices, &a.slice_len);
-    return EPGX_OK;
-}
-
-extern "C" int epgx_signal_crlb(epgx_ctx *ctx, const void *signal, int64_t record_stride, int64_t row_stride, int32_t nrow,
-                                int32_t nrec, int32_t nparam, const int32_t *rows, int64_t vox0, int64_t nvox,
-                                const double *weights, double sigma2, int32_t flags, void *out) {
-    if (!ctx || !signal || !rows || !out) return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: NULL argument");
-    if ((uintptr_t)out & 7) return fail(EPGX_ERR_INVALID, "epgx_signal_crlb: out must be aligned to 8 bytes");
-    CrlbArgs a;
-    if (int rc = crlb_jacobian_args("epgx_signal_crlb", signal, record_stride, row_stride, nrow, nrec, nparam, rows, vox0, nvox, weights,
-                                    sigma2, flags, EPGX_CRLB_SPLIT | EPGX_CRLB_LOG10, a))
-        return rc;
-    if (nvox == 0) return EPGX_OK;
-    if (int rc = set_device(ctx)) return rc;
-    a.out = (double *)out;
-    hipError_t e = epgx_launch_crlb(ctx->stream, nparam, a);
-    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "epgx_signal_crlb: %s", hipGetErrorString(e));
-    return EPGX_OK;
-}
-
-extern "C" int epgx_signal_crlb_grad(epgx_ctx *ctx, const void *signal, int64_t record_stride, int64_t row_stride, int32_t nrow,
-                                     int32_t nrec, int32_t nparam, const int32_t *rows, int64_t vox0, int64_t nvox,
-                                     const void *hess, int64_t hess_len, int32_t nx, const int64_t *offsets,
-                                     const int64_t *record_strides, const double *weights, double sigma2, int32_t flags,
-                                     void *out_cost, void *out_grad) {
-    const char *who = "epgx_signal_crlb_grad";
-    if (!ctx || !signal || !rows || !hess || !offsets || !record_strides || !out_cost || !out_grad)
-        return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
-    if (((uintptr_t)hess & 15) || ((uintptr_t)out_cost & 7) || ((uintptr_t)out_grad & 7))
-        return fail(EPGX_ERR_INVALID, "%s: hess must be aligned to 16 bytes, out_cost and out_grad to 8", who);
-    CrlbArgs a;
-    if (int rc = crlb_jacobian_args(who, signal, record_stride, row_stride, nrow, nrec, nparam, rows, vox0, nvox, weights, sigma2, flags,
-                                    EPGX_CRLB_LOG10, a))
-        return rc;
-    if (nx < 1) return fail(EPGX_ERR_INVALID, "%s: nx = %d must be >= 1", who, nx);
-    if (hess_len < 0 || hess_len > INT64_MAX / 16) return fail(EPGX_ERR_INVALID, "%s: hess_len = %lld", who, (long long)hess_len);
-    int64_t grad_len;
-    if (__builtin_mul_overflow((int64_t)nx, nvox, &grad_len) || grad_len > INT64_MAX / 8)
-        return fail(EPGX_ERR_INVALID, "%s: nx = %d maps of %lld voxels overflow the address range", who, nx, (long long)nvox);
-    // every entry of H that is read lies inside [hess, hess + hess_len): the kernel reads elements
-    // offset + r * stride + vox0 + j,  r < nrec, j < nvox
-    for (int64_t i = 0; i < (int64_t)nparam * nx; ++i) {
-        const int64_t off = offsets[i], step = record_strides[i];
-        if (off < 0) continue;
-        int64_t end;
-        if (step < 0 || (nrec > 1 && step < nvox) || __builtin_mul_overflow((int64_t)(nrec - 1), step, &end) ||
-            __builtin_add_overflow(end, off, &end) || __builtin_add_overflow(end, vox0, &end) || __builtin_add_overflow(end, nvox, &end) ||
-            end > hess_len)
-            return fail(EPGX_ERR_INVALID, "%s: entry (%lld, %lld) of H: offset = %lld, record stride = %lld, %d records of voxels [%lld, %lld + %lld) "
-                        "do not lie inside hess_len = %lld elements (or the records overlap)", who, (long long)(i / nx), (long long)(i % nx),
-                        (long long)off, (long long)step, nrec, (long long)vox0, (long long)vox0, (long long)nvox, (long long)hess_len);
-    }
-    if (nvox == 0) return EPGX_OK;
-    if (int rc = set_device(ctx)) return rc;
-    a.out = (double *)out_cost;
-    for (int32_t x0 = 0; x0 < nx; x0 += CRLB_GRAD_XB) {      // one launch per chunk of design variables
-        CrlbGradArgs h;
-        memset(&h, 0, sizeof(h));
-        h.hess = (const d2 *)hess;
-        h.nx = std::min<int32_t>(CRLB_GRAD_XB, nx - x0);
-        h.write_cost = x0 == 0;
-        h.grad = (double *)out_grad + (int64_t)x0 * nvox;
-        for (int x = 0; x < CRLB_GRAD_XB; ++x)
-            for (int c = 0; c < CRLB_MAX_P; ++c) {
-                const bool used = x < h.nx && c < nparam;
-                h.off[x][c] = used ? offsets[(int64_t)c * nx + x0 + x] : -1;
-                h.stride[x][c] = used ? record_strides[(int64_t)c * nx + x0 + x] : 0;
-            }
-        hipError_t e = epgx_launch_crlb_grad(ctx->stream, nparam, a, h);
-        if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    }
-    return EPGX_OK;
-}
-
-// ------------------------------------------------------------------------------ dictionary matching (epgx_match.hip)
-// records [nrec][row_stride] complex128 of which the first `cols` columns are read: false when row_stride < cols or the extent
-// (nrec - 1) * row_stride + cols cannot be addressed
-static bool match_extent_ok(int32_t nrec, int64_t row_stride, int64_t cols) {
-    int64_t span;
-    return row_stride >= cols && !__builtin_mul_overflow((int64_t)(nrec - 1), row_stride, &span) &&
-           !__builtin_add_overflow(span, cols, &span) && span <= INT64_MAX / 16;
-}
-
-extern "C" int epgx_signal_norms(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int64_t natoms, void *out) {
-    const char *who = "epgx_signal_norms";
-    if (!ctx || !dict || !out) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
-    if (((uintptr_t)dict & 15) || ((uintptr_t)out & 7)) return fail(EPGX_ERR_INVALID, "%s: dict must be aligned to 16 bytes, out to 8", who);
-    if (nrec < 1 || natoms < 1) return fail(EPGX_ERR_INVALID, "%s: nrec = %d, natoms = %lld: both must be >= 1", who, nrec, (long long)natoms);
-    if (!match_extent_ok(nrec, row_stride, natoms) || natoms / 256 >= 0x7fffffff)
-        return fail(EPGX_ERR_INVALID, "%s: %d records of row_stride = %lld do not hold %lld atoms each (or overflow the address range)", who,
-                    nrec, (long long)row_stride, (long long)natoms);
-    if (int rc = set_device(ctx)) return rc;
-    hipError_t e = epgx_launch_norms(ctx->stream, dict, row_stride, nrec, natoms, (double *)out);
-    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return EPGX_OK;
-}
-
-extern "C" int epgx_signal_match(epgx_ctx *ctx, const void *dict, int64_t dict_row_stride, const void *norms, int64_t natoms,
-                                 const void *sig, int64_t sig_row_stride, int32_t nrec, int64_t nmeas, int32_t nsplit,
-                                 void *out_index, void *out_scale, void *out_score) {
-    const char *who = "epgx_signal_match";
-    if (!ctx || !dict || !norms || !sig || !out_index || !out_scale || !out_score) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
-    if (((uintptr_t)dict & 15) || ((uintptr_t)sig & 15) || ((uintptr_t)out_scale & 15) || ((uintptr_t)norms & 7) ||
-        ((uintptr_t)out_index & 7) || ((uintptr_t)out_score & 7))
-        return fail(EPGX_ERR_INVALID, "%s: dict, sig and out_scale must be aligned to 16 bytes, norms, out_index and out_score to 8", who);
-    if (nrec < 1 || natoms < 1 || nmeas < 0)
-        return fail(EPGX_ERR_INVALID, "%s: nrec = %d, natoms = %lld (both >= 1), nmeas = %lld (>= 0)", who, nrec, (long long)natoms, (long long)nmeas);
-    if (nsplit < 0 || nsplit > natoms) return fail(EPGX_ERR_INVALID, "%s: nsplit = %d not in [0, natoms = %lld]", who, nsplit, (long long)natoms);
-    if (!match_extent_ok(nrec, dict_row_stride, natoms))
-        return fail(EPGX_ERR_INVALID, "%s: %d records of dict_row_stride = %lld do not hold %lld atoms each (or overflow the address range)", who,
-                    nrec, (long long)dict_row_stride, (long long)natoms);
-    if (!match_extent_ok(nrec, sig_row_stride, nmeas))
-        return fail(EPGX_ERR_INVALID, "%s: %d records of sig_row_stride = %lld do not hold %lld voxels each (or overflow the address range)", who,
-                    nrec, (long long)sig_row_stride, (long long)nmeas);
-    if (nmeas == 0) return EPGX_OK;
-    MatchArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nvt = (nmeas + MATCH_VOX - 1) / MATCH_VOX;
-    if (nsplit == 0) {
-        // enough workgroups for four per compute unit, every split at least one pass of the workgroup (by the launch shape
-        // alone: the result does not depend on it)
-        const int64_t want = 4 * (int64_t)std::max(ctx->prop.multiProcessorCount, 1);
-        const int64_t most = std::max<int64_t>(natoms / (MATCH_WAVES * MATCH_TILE), 1);
-        nsplit = (int32_t)std::min<int64_t>(std::min<int64_t>((want + a.nvt - 1) / a.nvt, most), 1 << 16);
-    }
-    int64_t scratch_len;
-    if (a.nvt > (int64_t)0x7fffffff / nsplit || __builtin_mul_overflow((int64_t)nsplit, nmeas, &scratch_len) ||
-        scratch_len > INT64_MAX / (int64_t)sizeof(MatchPartial))
-        return fail(EPGX_ERR_INVALID, "%s: nsplit = %d splits of %lld voxels in one call", who, nsplit, (long long)nmeas);
-    if (int rc = set_device(ctx)) return rc;
-    void *part = nullptr;
-    hipError_t e = dev_alloc(ctx, &part, sizeof(MatchPartial) * (size_t)scratch_len);
-    if (e != hipSuccess) return fail(EPGX_ERR_NOMEM, "%s: scratch for %d splits of %lld voxels: %s", who, nsplit, (long long)nmeas, hipGetErrorString(e));
-    a.dict = (const d2 *)dict;
-    a.dict_stride = dict_row_stride;
-    a.norms = (const double *)norms;
-    a.natoms = natoms;
-    a.sig = (const d2 *)sig;
-    a.sig_stride = sig_row_stride;
-    a.nmeas = nmeas;
-    a.nrec = nrec;
-    a.nsplit = nsplit;
-    a.chunk = std::min((nrec + MATCH_STEP - 1) / MATCH_STEP * MATCH_STEP, MATCH_CHUNK);
-    a.nchunk = (nrec + a.chunk - 1) / a.chunk;
-    a.part = (MatchPartial *)part;
-    e = epgx_launch_match(ctx->stream, a);
-    if (e == hipSuccess) {
-        MatchMergeArgs g;
-        memset(&g, 0, sizeof(g));
-        g.part = a.part;
-        g.norms = a.norms;
-        g.sig = a.sig;
-        g.sig_stride = sig_row_stride;
-        g.nmeas = nmeas;
-        g.nrec = nrec;
-        g.nsplit = nsplit;
-        g.index = (int64_t *)out_index;
-        g.scale = (d2 *)out_scale;
-        g.score = (double *)out_score;
-        e = epgx_launch_match_merge(ctx->stream, g);
-    }
-    dev_free(ctx, part);      // (stream-ordered: the block is recycled behind the kernels that use it)
-    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return EPGX_OK;
-}
-
-// ------------------------------------------------------------------------------ single-precision matching (epgx_match32.hip)
-// match_extent_ok for elements of `bytes` bytes
-static bool match_extent_ok_bytes(int64_t rows, int64_t row_stride, int64_t cols, int64_t bytes) {
-    int64_t span;
-    return row_stride >= cols && !__builtin_mul_overflow(rows - 1, row_stride, &span) && !__builtin_add_overflow(span, cols, &span) &&
-           span <= INT64_MAX / bytes;
-}
-
-extern "C" int epgx_signal_norms_c64(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int64_t natoms, void *out) {
-    const char *who = "epgx_signal_norms_c64";
-    if (!ctx || !dict || !out) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
-    if (((uintptr_t)dict & 7) || ((uintptr_t)out & 7)) return fail(EPGX_ERR_INVALID, "%s: dict and out must be aligned to 8 bytes", who);
-    if (nrec < 1 || natoms < 1) return fail(EPGX_ERR_INVALID, "%s: nrec = %d, natoms = %lld: both must be >= 1", who, nrec, (long long)natoms);
-    if (!match_extent_ok_bytes(nrec, row_stride, natoms, 8) || natoms / 256 >= 0x7fffffff)
-        return fail(EPGX_ERR_INVALID, "%s: %d records of row_stride = %lld do not hold %lld atoms each (or overflow the address range)", who,
-                    nrec, (long long)row_stride, (long long)natoms);
-    if (int rc = set_device(ctx)) return rc;
-    hipError_t e = epgx_launch_norms32(ctx->stream, dict, row_stride, nrec, natoms, (double *)out);
-    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return EPGX_OK;
-}
-
-extern "C" int epgx_signal_match_c64(epgx_ctx *ctx, const void *dict, int64_t dict_row_stride, const void *norms, int64_t natoms,
-                                     const void *sig, int64_t sig_row_stride, int32_t nrec, int64_t nmeas, int32_t nsplit,
-                                     void *out_index, void *out_scale, void *out_score) {
-    const char *who = "epgx_signal_match_c64";
-    if (!ctx || !dict || !norms || !sig || !out_index || !out_scale || !out_score) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
-    if (((uintptr_t)out_scale & 15) || ((uintptr_t)dict & 7) || ((uintptr_t)sig & 7) || ((uintptr_t)norms & 7) ||
-        ((uintptr_t)out_index & 7) || ((uintptr_t)out_score & 7))
-        return fail(EPGX_ERR_INVALID, "%s: out_scale must be aligned to 16 bytes, dict, sig, norms, out_index and out_score to 8", who);
-    if (nrec < 1 || natoms < 1 || nmeas < 0)
-        return fail(EPGX_ERR_INVALID, "%s: nrec = %d, natoms = %lld (both >= 1), nmeas = %lld (>= 0)", who, nrec, (long long)natoms, (long long)nmeas);
-    if (nsplit < 0 || nsplit > natoms) return fail(EPGX_ERR_INVALID, "%s: nsplit = %d not in [0, natoms = %lld]", who, nsplit, (long long)natoms);
-    if (!match_extent_ok_bytes(nrec, dict_row_stride, natoms, 8))
-        return fail(EPGX_ERR_INVALID, "%s: %d records of dict_row_stride = %lld do not hold %lld atoms each (or overflow the address range)", who,
-                    nrec, (long long)dict_row_stride, (long long)natoms);
-    if (!match_extent_ok_bytes(nrec, sig_row_stride, nmeas, 8))
-        return fail(EPGX_ERR_INVALID, "%s: %d records of sig_row_stride = %lld do not hold %lld voxels each (or overflow the address range)", who,
-                    nrec, (long long)sig_row_stride, (long long)nmeas);
-    if (nmeas == 0) return EPGX_OK;
-    Match32Args a;
-    memset(&a, 0, sizeof(a));
-    a.nvt = (nmeas + MATCH_VOX - 1) / MATCH_VOX;
-    if (nsplit == 0) {
-        // the rule of epgx_signal_match (by the launch shape alone: the result does not depend on it)
-        const int64_t want = 4 * (int64_t)std::max(ctx->prop.multiProcessorCount, 1);
-        const int64_t most = std::max<int64_t>(natoms / (MATCH_WAVES * MATCH_TILE), 1);
-        nsplit = (int32_t)std::min<int64_t>(std::min<int64_t>((want + a.nvt - 1) / a.nvt, most), 1 << 16);
-    }
-    int64_t scratch_len;
-    if (a.nvt > (int64_t)0x7fffffff / nsplit || __builtin_mul_overflow((int64_t)nsplit, nmeas, &scratch_len) ||
-        scratch_len > INT64_MAX / (int64_t)sizeof(MatchPartial))
-        return fail(EPGX_ERR_INVALID, "%s: nsplit = %d splits of %lld voxels in one call", who, nsplit, (long long)nmeas);
-    if (int rc = set_device(ctx)) return rc;
-    void *part = nullptr;
-    hipError_t e = dev_alloc(ctx, &part, sizeof(MatchPartial) * (size_t)scratch_len);
-    if (e != hipSuccess) return fail(EPGX_ERR_NOMEM, "%s: scratch for %d splits of %lld voxels: %s", who, nsplit, (long long)nmeas, hipGetErrorString(e));
-    a.dict = (const f2 *)dict;
-    a.dict_stride = dict_row_stride;
-    a.norms = (const double *)norms;
-    a.natoms = natoms;
-    a.sig = (const f2 *)sig;
-    a.sig_stride = sig_row_stride;
-    a.nmeas = nmeas;
-    a.nrec = nrec;
-    a.nsplit = nsplit;
-    a.chunk = std::min((nrec + MATCH_STEP - 1) / MATCH_STEP * MATCH_STEP, MATCH32_CHUNK);
-    a.nchunk = (nrec + a.chunk - 1) / a.chunk;
-    a.part = (MatchPartial *)part;
-    e = epgx_launch_match32(ctx->stream, a);
-    if (e == hipSuccess) {
-        Match32MergeArgs g;
-        memset(&g, 0, sizeof(g));
-        g.part = a.part;
-        g.norms = a.norms;
-        g.sig = a.sig;
-        g.sig_stride = sig_row_stride;
-        g.nmeas = nmeas;
-        g.nrec = nrec;
-        g.nsplit = nsplit;
-        g.index = (int64_t *)out_index;
-        g.scale = (d2 *)out_scale;
-        g.score = (double *)out_score;
-        e = epgx_launch_match32_merge(ctx->stream, g);
-    }
-    dev_free(ctx, part);      // (stream-ordered: the block is recycled behind the kernels that use it)
-    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return EPGX_OK;
-}
-
-// ------------------------------------------------------------------------------ Gauss-Newton refinement (epgx_refine.hip)
-extern "C" int epgx_signal_refine(epgx_ctx *ctx, const void *jac, int64_t record_stride, int64_t row_stride, int32_t nrow, int32_t nrec,
-                                  int32_t nparam, const int32_t *rows, int64_t natoms, const void *sig, int64_t sig_row_stride,
-                                  int64_t nmeas, const void *index, const double *limit, double rcond, void *out_delta, void *out_scale,
-                                  void *out_score) {
-    const char *who = "epgx_signal_refine";
-    if (!ctx || !jac || !rows || !sig || !index || !out_delta || !out_scale || !out_score) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
-    if (((uintptr_t)jac & 15) || ((uintptr_t)sig & 15) || ((uintptr_t)out_scale & 15) || ((uintptr_t)index & 7) ||
-        ((uintptr_t)out_delta & 7) || ((uintptr_t)out_score & 7))
-        return fail(EPGX_ERR_INVALID, "%s: jac, sig and out_scale must be aligned to 16 bytes, index, out_delta and out_score to 8", who);
-    if (nparam < 1 || nparam > REFINE_MAX_P) return fail(EPGX_ERR_INVALID, "%s: nparam = %d not in [1, %d]", who, nparam, REFINE_MAX_P);
-    if (nrec < 1 || nrow < 1) return fail(EPGX_ERR_INVALID, "%s: nrec = %d, nrow = %d: both must be >= 1", who, nrec, nrow);
-    if (natoms < 1 || nmeas < 0) return fail(EPGX_ERR_INVALID, "%s: natoms = %lld (>= 1), nmeas = %lld (>= 0)", who, (long long)natoms, (long long)nmeas);
-    if (row_stride < 1 || natoms > row_stride)
-        return fail(EPGX_ERR_INVALID, "%s: %lld atoms outside a row of %lld", who, (long long)natoms, (long long)row_stride);
-    if (record_stride / nrow < row_stride)
-        return fail(EPGX_ERR_INVALID, "%s: record_stride = %lld holds fewer than nrow = %d rows of %lld", who, (long long)record_stride, nrow,
-                    (long long)row_stride);
-    int64_t span, last;      // elements from `jac` to the end of the last record: must be expressible (the kernel's pointer arithmetic)
-    if (__builtin_mul_overflow((int64_t)(nrec - 1), record_stride, &span) || __builtin_mul_overflow((int64_t)nrow, row_stride, &last) ||
-        __builtin_add_overflow(span, last, &span) || span > INT64_MAX / 16)
-        return fail(EPGX_ERR_INVALID, "%s: nrec = %d records of record_stride = %lld elements overflow the address range", who, nrec,
-                    (long long)record_stride);
-    if (!match_extent_ok(nrec, sig_row_stride, nmeas))
-        return fail(EPGX_ERR_INVALID, "%s: %d records of sig_row_stride = %lld do not hold %lld voxels each (or overflow the address range)", who,
-                    nrec, (long long)sig_row_stride, (long long)nmeas);
-    if (nmeas / 64 >= 0x7fffffff) return fail(EPGX_ERR_INVALID, "%s: %lld voxels in one call", who, (long long)nmeas);
-    if (!(rcond >= 0.0 && rcond < 1.0)) return fail(EPGX_ERR_INVALID, "%s: rcond = %g not in [0, 1)", who, rcond);
-    RefineArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int c = 0; c < nparam; ++c) {
-        if (rows[c] < 1 || rows[c] >= nrow)
-            return fail(EPGX_ERR_INVALID, "%s: rows[%d] = %d not in [1, nrow = %d) (row 0 is the state)", who, c, rows[c], nrow);
-        for (int k = 0; k < c; ++k)
-            if (rows[k] == rows[c]) return fail(EPGX_ERR_INVALID, "%s: rows[%d] = rows[%d] = %d: a repeated row", who, k, c, rows[c]);
-        if (limit && !(limit[c] > 0.0)) return fail(EPGX_ERR_INVALID, "%s: limit[%d] = %g is not positive", who, c, limit[c]);
-        a.rows[c] = rows[c];
-        a.limit[c] = limit ? limit[c] : (double)INFINITY;
-    }
-    if (nmeas == 0) return EPGX_OK;
-    if (int rc = set_device(ctx)) return rc;
-    a.jac = (const d2 *)jac;
-    a.record_stride = record_stride;
-    a.row_stride = row_stride;
-    a.nrec = nrec;
-    a.natoms = natoms;
-    a.sig = (const d2 *)sig;
-    a.sig_stride = sig_row_stride;
-    a.nmeas = nmeas;
-    a.index = (const int64_t *)index;
-    a.rcond = rcond;
-    refine_slices(nrec, &a.slices, &a.slice_len);
-    a.delta = (double *)out_delta;
-    a.scale = (d2 *)out_scale;
-    a.score = (double *)out_score;
-    hipError_t e = epgx_launch_refine(ctx->stream, nparam, a);
-    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return EPGX_OK;
-}
-
-// ------------------------------------------------------------------------------ non-negative mixtures (epgx_nnls.hip)
-// the checks both entries share; 0, or the error already recorded by fail()
-static int component_args(const char *who, const void *dict, int64_t row_stride, int32_t nrec, int32_t ncomp, int64_t axis_stride,
-                          int64_t nouter, int64_t ninner, ComponentArgs *c) {
-    if (ncomp < 1 || ncomp > NNLS_MAX_A) return fail(EPGX_ERR_INVALID, "%s: ncomp = %d not in [1, %d]", who, ncomp, NNLS_MAX_A);
-    if (nrec < 1) return fail(EPGX_ERR_INVALID, "%s: nrec = %d must be >= 1", who, nrec);
-    if (nouter < 1 || ninner < 1)
-        return fail(EPGX_ERR_INVALID, "%s: nouter = %lld, ninner = %lld: both must be >= 1", who, (long long)nouter, (long long)ninner);
-    if (axis_stride < ninner)
-        return fail(EPGX_ERR_INVALID, "%s: axis_stride = %lld below ninner = %lld", who, (long long)axis_stride, (long long)ninner);
-    int64_t groups, cols;      // cols: one past the last column an atom lies at
-    if (__builtin_mul_overflow(nouter, ninner, &groups) || groups > 0x7fffffff)
-        return fail(EPGX_ERR_INVALID, "%s: nouter = %lld times ninner = %lld groups in one call", who, (long long)nouter, (long long)ninner);
-    if (__builtin_mul_overflow(nouter, (int64_t)ncomp, &cols) || __builtin_mul_overflow(cols - 1, axis_stride, &cols) ||
-        __builtin_add_overflow(cols, ninner, &cols) || !match_extent_ok(nrec, row_stride, cols))
-        return fail(EPGX_ERR_INVALID, "%s: %d records of row_stride = %lld do not hold %lld x %d atoms of stride %lld (or overflow the address range)",
-                    who, nrec, (long long)row_stride, (long long)nouter, ncomp, (long long)axis_stride);
-    c->dict = (const d2 *)dict;
-    c->row_stride = row_stride;
-    c->nrec = nrec;
-    c->ncomp = ncomp;
-    c->axis_stride = axis_stride;
-    c->nouter = nouter;
-    c->ninner = ninner;
-    return 0;
-}
-
-extern "C" int epgx_signal_component_gram(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int32_t ncomp,
-                                          int64_t axis_stride, int64_t nouter, int64_t ninner, void *out_gram, void *out_mask) {
-    const char *who = "epgx_signal_component_gram";
-    if (!ctx || !dict || !out_gram || !out_mask) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
-    if (((uintptr_t)dict & 15) || ((uintptr_t)out_gram & 7) || ((uintptr_t)out_mask & 7))
-        return fail(EPGX_ERR_INVALID, "%s: dict must be aligned to 16 bytes, out_gram and out_mask to 8", who);
-    ComponentGramArgs a;
-    memset(&a, 0, sizeof(a));
-    if (int rc = component_args(who, dict, row_stride, nrec, ncomp, axis_stride, nouter, ninner, &a.c)) return rc;
-    if (int rc = set_device(ctx)) return rc;
-    a.gram = (double *)out_gram;
-    a.mask = (unsigned long long *)out_mask;
-    hipError_t e = epgx_launch_component_gram(ctx->stream, a);
-    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return EPGX_OK;
-}
-
-// the checks epgx_signal_nnls and epgx_signal_nnls_chi2 share; 0 with *a filled (nothing launched, no device set), or the error
-// already recorded by fail()
-static int nnls_args(const char *who, epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int32_t ncomp, int64_t axis_stride,
-                     int64_t nouter, int64_t ninner, const void *gram, const void *mask, const void *sig, int64_t sig_row_stride,
-                     int64_t nmeas, double reg, double tol, const void *group, void *out_weights, void *out_group, void *out_residual,
-                     void *out_status, NnlsArgs *a) {
-    if (!ctx || !dict || !gram || !mask || !sig || !out_weights || !out_group || !out_residual || !out_status)
-        return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
-    if (((uintptr_t)dict & 15) || ((uintptr_t)sig & 15) || ((uintptr_t)gram & 7) || ((uintptr_t)mask & 7) || ((uintptr_t)group & 7) ||
-        ((uintptr_t)out_weights & 7) || ((uintptr_t)out_group & 7) || ((uintptr_t)out_residual & 7) || ((uintptr_t)out_status & 3))
-        return fail(EPGX_ERR_INVALID, "%s: dict and sig must be aligned to 16 bytes, out_status to 4, the others to 8", who);
-    memset(a, 0, sizeof(*a));
-    if (int rc = component_args(who, dict, row_stride, nrec, ncomp, axis_stride, nouter, ninner, &a->c)) return rc;
-    if (nmeas < 0) return fail(EPGX_ERR_INVALID, "%s: nmeas = %lld must be >= 0", who, (long long)nmeas);
-    if (!match_extent_ok(nrec, sig_row_stride, nmeas))
-        return fail(EPGX_ERR_INVALID, "%s: %d records of sig_row_stride = %lld do not hold %lld voxels each (or overflow the address range)", who,
-                    nrec, (long long)sig_row_stride, (long long)nmeas);
-    if (nmeas >= 0x7fffffff) return fail(EPGX_ERR_INVALID, "%s: %lld voxels in one call", who, (long long)nmeas);
-    if (!(reg >= 0.0 && reg < (double)INFINITY)) return fail(EPGX_ERR_INVALID, "%s: reg = %g is not a finite number >= 0", who, reg);
-    if (!(tol >= 0.0 && tol < (double)INFINITY)) return fail(EPGX_ERR_INVALID, "%s: tol = %g is not a finite number >= 0", who, tol);
-    a->gram = (const double *)gram;
-    a->mask = (const unsigned long long *)mask;
-    a->sig = (const d2 *)sig;
-    a->sig_stride = sig_row_stride;
-    a->nmeas = nmeas;
-    a->reg = reg;
-    a->tol = tol;
-    a->group = (const int64_t *)group;
-    a->weights = (double *)out_weights;
-    a->out_group = (int64_t *)out_group;
-    a->residual = (double *)out_residual;
-    a->status = (int32_t *)out_status;
-    return 0;
-}
-
-extern "C" int epgx_signal_nnls(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int32_t ncomp, int64_t axis_stride,
-                                int64_t nouter, int64_t ninner, const void *gram, const void *mask, const void *sig,
-                                int64_t sig_row_stride, int64_t nmeas, double reg, double tol, const void *group, void *out_weights,
-                                void *out_group, void *out_residual, void *out_status) {
-    const char *who = "epgx_signal_nnls";
-    NnlsArgs a;
-    if (int rc = nnls_args(who, ctx, dict, row_stride, nrec, ncomp, axis_stride, nouter, ninner, gram, mask, sig, sig_row_stride, nmeas, reg,
-                           tol, group, out_weights, out_group, out_residual, out_status, &a))
-        return rc;
-    if (nmeas == 0) return EPGX_OK;
-    if (int rc = set_device(ctx)) return rc;
-    hipError_t e = epgx_launch_nnls(ctx->stream, a);
-    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return EPGX_OK;
-}
-
-extern "C" int epgx_signal_nnls_chi2(epgx_ctx *ctx, const void *dict, int64_t row_stride, int32_t nrec, int32_t ncomp, int64_t axis_stride,
-                                     int64_t nouter, int64_t ninner, const void *gram, const void *mask, const void *sig,
-                                     int64_t sig_row_stride, int64_t nmeas, double reg, double tol, const void *group, double chi2,
-                                     double chi2_rtol, int32_t max_evals, void *out_weights, void *out_group, void *out_residual,
-                                     void *out_status, void *out_mu, void *out_chi2, void *out_evals) {
-    const char *who = "epgx_signal_nnls_chi2";
-    NnlsChi2Args a;
-    memset(&a, 0, sizeof(a));
-    if (!out_mu || !out_chi2 || !out_evals) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
-    if (((uintptr_t)out_mu & 7) || ((uintptr_t)out_chi2 & 7) || ((uintptr_t)out_evals & 3))
-        return fail(EPGX_ERR_INVALID, "%s: out_mu and out_chi2 must be aligned to 8 bytes, out_evals to 4", who);
-    if (int rc = nnls_args(who, ctx, dict, row_stride, nrec, ncomp, axis_stride, nouter, ninner, gram, mask, sig, sig_row_stride, nmeas, reg,
-                           tol, group, out_weights, out_group, out_residual, out_status, &a.n))
-        return rc;
-    if (!(reg > 0.0)) return fail(EPGX_ERR_INVALID, "%s: reg = %g must be > 0: the bracket grows from mu_0 = reg * mean H_aa", who, reg);
-    if (!(chi2 > 1.0 && chi2 < (double)INFINITY)) return fail(EPGX_ERR_INVALID, "%s: chi2 = %g is not a finite number > 1", who, chi2);
-    if (!(chi2_rtol > 0.0 && chi2_rtol < 1.0)) return fail(EPGX_ERR_INVALID, "%s: chi2_rtol = %g not in (0, 1)", who, chi2_rtol);
-    if (max_evals < 0 || max_evals > NNLS_CHI2_EVALS)
-        return fail(EPGX_ERR_INVALID, "%s: max_evals = %d not in [0, %d]", who, max_evals, NNLS_CHI2_EVALS);
-    if (nmeas == 0) return EPGX_OK;
-    if (int rc = set_device(ctx)) return rc;
-    a.chi2 = chi2;
-    a.rtol = chi2_rtol;
-    a.max_evals = max_evals;
-    a.mu = (double *)out_mu;
-    a.ratio = (double *)out_chi2;
-    a.evals = (int32_t *)out_evals;
-    if (!group) {      // the group search first; its out_group stays on the device and is what the second launch reads
-        hipError_t e = epgx_launch_nnls(ctx->stream, a.n);
-        if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-        a.n.group = a.n.out_group;
-    }
-    hipError_t e = epgx_launch_nnls_chi2(ctx->stream, a);
-    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return EPGX_OK;
-}
-
-// ------------------------------------------------------------------------------ dictionary compression (epgx_compress.hip)
-extern "C" int epgx_signal_gram(epgx_ctx *ctx, const void *dict, int64_t dict_row_stride, const void *norms, int32_t nrec, int64_t natoms,
-                                int32_t nsplit, void *out) {
-    const char *who = "epgx_signal_gram";
-    if (!ctx || !dict || !norms || !out) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
-    if (((uintptr_t)dict & 15) || ((uintptr_t)out & 15) || ((uintptr_t)norms & 7))
-        return fail(EPGX_ERR_INVALID, "%s: dict and out must be aligned to 16 bytes, norms to 8", who);
-    if (nrec < 1 || natoms < 1) return fail(EPGX_ERR_INVALID, "%s: nrec = %d, natoms = %lld: both must be >= 1", who, nrec, (long long)natoms);
-    if (nsplit < 0 || nsplit > natoms) return fail(EPGX_ERR_INVALID, "%s: nsplit = %d not in [0, natoms = %lld]", who, nsplit, (long long)natoms);
-    if (!match_extent_ok(nrec, dict_row_stride, natoms))
-        return fail(EPGX_ERR_INVALID, "%s: %d records of dict_row_stride = %lld do not hold %lld atoms each (or overflow the address range)", who,
-                    nrec, (long long)dict_row_stride, (long long)natoms);
-    if (nsplit == 0) nsplit = gram_default_nsplit(nrec, natoms);
-    GramArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nblock = gram_nblock(nrec);
-    const int64_t npair = (int64_t)a.nblock * (a.nblock + 1) / 2;
-    int64_t scratch_len;
-    if (npair > (int64_t)0x7fffffff / nsplit || __builtin_mul_overflow((int64_t)nrec * nrec, (int64_t)nsplit, &scratch_len) ||
-        scratch_len > INT64_MAX / (int64_t)sizeof(d2))
-        return fail(EPGX_ERR_INVALID, "%s: nsplit = %d partial Gram matrices of %d x %d in one call", who, nsplit, nrec, nrec);
-    if (int rc = set_device(ctx)) return rc;
-    void *part = nullptr;
-    hipError_t e = dev_alloc(ctx, &part, sizeof(d2) * (size_t)scratch_len);
-    if (e != hipSuccess) return fail(EPGX_ERR_NOMEM, "%s: scratch for %d partial Gram matrices of %d x %d: %s", who, nsplit, nrec, nrec, hipGetErrorString(e));
-    a.dict = (const d2 *)dict;
-    a.dict_stride = dict_row_stride;
-    a.norms = (const double *)norms;
-    a.natoms = natoms;
-    a.nrec = nrec;
-    a.nsplit = nsplit;
-    a.npair = (int32_t)npair;
-    a.part = (d2 *)part;
-    e = epgx_launch_gram(ctx->stream, a);
-    if (e == hipSuccess) {
-        GramReduceArgs g;
-        memset(&g, 0, sizeof(g));
-        g.part = a.part;
-        g.nrec = nrec;
-        g.nsplit = nsplit;
-        g.out = (d2 *)out;
-        e = epgx_launch_gram_reduce(ctx->stream, g);
-    }
-    dev_free(ctx, part);      // (stream-ordered: the block is recycled behind the kernels that use it)
-    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return EPGX_OK;
-}
-
-extern "C" int epgx_signal_project(epgx_ctx *ctx, const void *basis, int32_t rank, const void *src, int64_t src_row_stride, int32_t nrec,
-                                   int64_t ncol, void *out, int64_t out_row_stride) {
-    const char *who = "epgx_signal_project";
-    if (!ctx || !basis || !src || !out) return fail(EPGX_ERR_INVALID, "%s: NULL argument", who);
-    if (((uintptr_t)basis & 15) || ((uintptr_t)src & 15) || ((uintptr_t)out & 15))
-        return fail(EPGX_ERR_INVALID, "%s: basis, src and out must be aligned to 16 bytes", who);
-    if (nrec < 1 || ncol < 0) return fail(EPGX_ERR_INVALID, "%s: nrec = %d (>= 1), ncol = %lld (>= 0)", who, nrec, (long long)ncol);
-    if (rank < 1 || rank > PROJ_MAX_RANK || rank > nrec)
-        return fail(EPGX_ERR_INVALID, "%s: rank = %d not in [1, min(%d, nrec = %d)]", who, rank, PROJ_MAX_RANK, nrec);
-    if (!match_extent_ok(nrec, src_row_stride, ncol))
-        return fail(EPGX_ERR_INVALID, "%s: %d records of src_row_stride = %lld do not hold %lld columns each (or overflow the address range)", who,
-                    nrec, (long long)src_row_stride, (long long)ncol);
-    if (!match_extent_ok(rank, out_row_stride, ncol))
-        return fail(EPGX_ERR_INVALID, "%s: %d rows of out_row_stride = %lld do not hold %lld columns each (or overflow the address range)", who,
-                    rank, (long long)out_row_stride, (long long)ncol);
-    if (ncol / (PROJ_WAVES * PROJ_TILE) >= 0x7fffffff) return fail(EPGX_ERR_INVALID, "%s: ncol = %lld columns in one call", who, (long long)ncol);
-    if (ncol == 0) return EPGX_OK;
-    if (int rc = set_device(ctx)) return rc;
-    ProjectArgs a;
-    memset(&a, 0, sizeof(a));
-    a.basis = (const d2 *)basis;
-    a.src = (const d2 *)src;
-    a.src_stride = src_row_stride;
-    a.ncol = ncol;
-    a.out = (d2 *)out;
-    a.out_stride = out_row_stride;
-    a.nrec = nrec;
-    a.rank = rank;
-    hipError_t e = epgx_launch_project(ctx->stream, a);
-    if (e != hipSuccess) return fail(EPGX_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return EPGX_OK;
 }
 

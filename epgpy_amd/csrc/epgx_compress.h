@@ -5,27 +5,10 @@
 
 namespace epgx {
 
-constexpr int GRAM_TILE = 16;              // records (rows and columns) of one v_mfma_f64_16x16x4_f64 tile of G
+// (GRAM_TILE, GRAM_WAVES, GRAM_BLOCK, gram_nblock and the library's own choice of nsplit, gram_default_nsplit: epgx_signal_limits.h)
 constexpr int GRAM_STEP = 4;               // atoms one MFMA consumes; the atoms of a split are taken in steps from its first atom
-constexpr int GRAM_WAVES = 4;              // wavefronts of a workgroup: wavefront w owns row tile w of the workgroup's record block
-constexpr int GRAM_BLOCK = GRAM_WAVES * GRAM_TILE;      // records of a record block: a workgroup computes a 64 x 64 block of G
 constexpr int GRAM_KC = 16;                // atoms of a record block that LDS holds at a time
 constexpr int GRAM_LD = GRAM_KC + 1;       // row pitch of the LDS image in elements (the pad: see epgx_compress.hip)
-// The library's own choice of nsplit (epgx_signal_gram with nsplit = 0), a function of (nrec, natoms) alone:
-//      nblock = ceil(nrec / 64),  npair = nblock (nblock + 1) / 2      (the 64 x 64 blocks I <= J of G, one workgroup each per split)
-//      nsplit = min(ceil(GRAM_WORKGROUPS / npair), max(natoms / GRAM_MIN_ATOMS, 1))
-// i.e. about GRAM_WORKGROUPS workgroups as long as every split keeps GRAM_MIN_ATOMS atoms.  Neither the number of compute
-// units nor the state of the pool enters: the same dictionary gives the same bits of G on every machine.
-constexpr int GRAM_WORKGROUPS = 2048;
-constexpr int GRAM_MIN_ATOMS = 1024;
-
-__host__ __device__ inline int32_t gram_nblock(int32_t nrec) { return (nrec + GRAM_BLOCK - 1) / GRAM_BLOCK; }
-
-inline int32_t gram_default_nsplit(int32_t nrec, int64_t natoms) {
-    const int64_t nblock = gram_nblock(nrec), npair = nblock * (nblock + 1) / 2;
-    const int64_t want = (GRAM_WORKGROUPS + npair - 1) / npair, most = natoms / GRAM_MIN_ATOMS > 1 ? natoms / GRAM_MIN_ATOMS : 1;
-    return (int32_t)(want < most ? want : most);
-}
 
 struct GramArgs {
     const d2 *dict;               // D[t][a] at dict[t * dict_stride + a]
@@ -43,12 +26,10 @@ struct GramReduceArgs {
     d2 *out;                      // G [nrec][nrec]
 };
 
-constexpr int PROJ_TILE = 16;              // basis vectors (rows) and columns of one MFMA tile
+// (PROJ_TILE, PROJ_WAVES, PROJ_MAX_RANK: epgx_signal_limits.h)
 constexpr int PROJ_STEP = 4;               // records one MFMA consumes, from t = 0, the tail padded with zeros
 constexpr int PROJ_TILES = 4;              // accumulator tiles of a wavefront: NR rank tiles x NC column tiles, NR * NC = 4
-constexpr int PROJ_WAVES = 4;              // wavefronts of a workgroup, each with column tiles of its own
 constexpr int PROJ_UNROLL = 4;             // steps whose loads are issued before their MFMAs
-constexpr int PROJ_MAX_RANK = 64;
 
 struct ProjectArgs {
     const d2 *basis;              // B[t][r] at basis[t * rank + r]

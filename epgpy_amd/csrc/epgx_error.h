@@ -1,5 +1,6 @@
 // epgx_error.h -- the thread-local message behind epgx_last_error() and the helper that sets it.  Shared by the entry
-// points (epgx_api.hip) and the launch planner (epgx_planner.cpp); plain C++17.
+// points (epgx_api.hip, epgx_signal.hip) and the device-free units behind them (epgx_planner.cpp, epgx_plan_check.cpp,
+// epgx_run_check.cpp, epgx_signal_check.cpp); plain C++17.
 #pragma once
 #include <cstdarg>
 #include <cstdio>

@@ -2,22 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "epgx_kernels.hip.h"
+#include "epgx_signal_limits.h"   // the MATCH_ constants and MatchPartial
 
 namespace epgx {
-
-constexpr int MATCH_TILE = 16;             // atoms (rows) and voxels (columns) of one v_mfma_f64_16x16x4_f64 tile
-constexpr int MATCH_STEP = 4;              // records one MFMA consumes; the records of a voxel are taken in steps from t = 0
-constexpr int MATCH_VT = 4;                // voxel tiles a wavefront keeps accumulators for: a workgroup owns MATCH_VT * 16 voxels
-constexpr int MATCH_VOX = MATCH_VT * MATCH_TILE;
-constexpr int MATCH_WAVES = 4;             // wavefronts of a workgroup, one atom tile each per pass
-constexpr int MATCH_CHUNK = 32;            // records of the voxel tile that LDS holds at a time (32 KiB); nrec <= 32: staged once per workgroup
-
-// what one (split, voxel) leaves in scratch: the best atom of the split's range (a < 0: none), 32 bytes
-struct MatchPartial {
-    double q;
-    int64_t a;
-    double cr, ci;
-};
 
 struct MatchArgs {
     const d2 *dict;               // D[t][a] at dict[t * dict_stride + a]

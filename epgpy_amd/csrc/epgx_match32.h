@@ -6,9 +6,7 @@
 
 namespace epgx {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-constexpr int MATCH32_CHUNK = 64;          // records of the voxel tile that LDS holds at a time: [64][MATCH_VOX] complex64, 32 KiB
+typedef float f2 __attribute__((ext_vector_type(2)));      // (MATCH32_CHUNK: epgx_signal_limits.h)
 
 struct Match32Args {
     const f2 *dict;               // D32[t][a] at dict[t * dict_stride + a]

@@ -3,10 +3,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "epgx_kernels.hip.h"
+#include "epgx_signal_limits.h"   // NNLS_MAX_A, NNLS_CHI2_EVALS
 
 namespace epgx {
 
-constexpr int NNLS_MAX_A = 64;             // atoms along the component axis: one lane of a wavefront each
 constexpr int NNLS_WAVES = 4;              // wavefronts (voxels) of a block in the group search; they share the staged H_g
 constexpr int NNLS_GRAM_THREADS = 256;     // threads of a block of component_gram_kernel (one block per group)
 
@@ -40,9 +40,8 @@ struct NnlsArgs {
 };
 
 // the chi^2-driven ridge (include/epgx.h epgx_signal_nnls_chi2): the bracket grows by this factor per evaluation from mu_0, and a
-// voxel's search ends after this many fits (DESIGN 4.17 has the counts both come from)
+// voxel's search ends after NNLS_CHI2_EVALS fits (DESIGN 4.17 has the counts both come from)
 constexpr double NNLS_CHI2_FACTOR = 16.0;
-constexpr int NNLS_CHI2_EVALS = 40;
 
 struct NnlsChi2Args {
     NnlsArgs n;                   // group is never NULL here: the caller's, or what nnls_kernel wrote to out_group just before

@@ -3,10 +3,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "epgx_kernels.hip.h"
+#include "epgx_signal_limits.h"   // REFINE_MAX_P
 
 namespace epgx {
 
-constexpr int REFINE_MAX_P = 4;            // columns of the Jacobian one call takes (the limit of epgx_signal_crlb)
 constexpr int REFINE_UNROLL = 2;           // records whose loads a lane has in flight (REFINE_UNROLL x (2 + P) loads of 16 bytes)
 constexpr int REFINE_SLICE = 16;           // up to this many records one wavefront sums all records of its voxels
 constexpr int REFINE_MAX_SLICES = 8;       // wavefronts that share the records of a voxel (1, 2, 4 or 8)

@@ -2,10 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "epgx_kernels.hip.h"
+#include "epgx_signal_limits.h"   // CRLB_MAX_P
 
 namespace epgx {
 
-constexpr int CRLB_MAX_P = 4;              // columns of a Jacobian on the device: 1 + EPGX_MAX_VARS rows per record
 constexpr int CRLB_UNROLL = 4;             // records whose loads a lane has in flight (CRLB_UNROLL x P loads of 16 bytes)
 constexpr int CRLB_SLICE = 64;             // up to this many records one wavefront sums all records of its voxels
 constexpr int CRLB_MAX_SLICES = 8;         // wavefronts that share the records of a voxel (1, 2, 4 or 8)

@@ -23,7 +23,7 @@ from tests import match_cases as mc
 U32 = 2.0 ** -24
 U64 = 2.0 ** -53
 LD, CLD = np.longdouble, np.clongdouble
-CHUNK = 64           # records of one LDS chunk of match32_kernel (csrc/epgx_match32.h MATCH32_CHUNK)
+CHUNK = 64           # records of one LDS chunk of match32_kernel (csrc/epgx_signal_limits.h MATCH32_CHUNK)
 KSTEP = 4            # records one v_mfma_f32_16x16x4_f32 consumes
 
 

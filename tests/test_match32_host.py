@@ -31,7 +31,7 @@ def test_boundary_agrees():
     assert _lib.SYMBOLS["epgx_signal_norms_c64"] == _lib.SYMBOLS["epgx_signal_norms"]
     assert _lib.SYMBOLS["epgx_signal_match_c64"] == _lib.SYMBOLS["epgx_signal_match"]
     assert any(src == "epgx_match32.hip" for _, src, _ in _build.UNITS)
-    assert "epgx_match32.h" in _build.include_closure("epgx_api.hip")
+    assert "epgx_match32.h" in _build.include_closure("epgx_signal.hip")
     import inspect
     assert inspect.signature(_lib.signal_match).parameters["c64"].default is False
     assert inspect.signature(_lib.signal_norms).parameters["c64"].default is False
@@ -126,7 +126,7 @@ def cases():
 
 def test_every_gpu_case_is_decisive(cases):
     assert m32.CHUNK == 64 and m32.KSTEP == 4
-    header = open(os.path.join(ROOT, "epgpy_amd", "csrc", "epgx_match32.h")).read()
+    header = open(os.path.join(ROOT, "epgpy_amd", "csrc", "epgx_signal_limits.h")).read()
     assert re.search(r"MATCH32_CHUNK\s*=\s*64\b", header)
     names = set(cases)
     for nrec in (63, 64, 65, 129, 6):

@@ -24,7 +24,7 @@ def test_boundary_agrees():
     lib = _lib.load()
     assert lib.epgx_abi_version() == 11 and hasattr(lib, "epgx_signal_crlb_grad")
     assert "epgx_signal_crlb_grad" in open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    stats_h = open(os.path.join(ROOT, "epgpy_amd", "csrc", "epgx_stats.h")).read()
+    stats_h = open(os.path.join(ROOT, "epgpy_amd", "csrc", "epgx_signal_limits.h")).read()
     assert re.search(rf"CRLB_MAX_P = {stats.MAX_DEVICE_PARAMS};", stats_h)
 
 
